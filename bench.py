@@ -7,7 +7,8 @@ diag on the device, blocked Cholesky in place, forward triangular solve, reducti
 back on the host.  X, the noise diagonal and the residual are resident in HBM before the
 timed region starts.
 
-  python bench.py --gpus N --steps K --warmup W [--workload c2|c1|c3|c4|n<int>|ref<int>]
+  python bench.py --gpus N --steps K --warmup W [--workload c2|c1|c3|c4|n<int>|ref<int>] [--full]
+                  [--dump-outputs DIR]
 
 N = 1 (default): BASELINE config 2 (ExpSquared, 1-D, N = 16 384, fp64) on one GPU through
 `GaussianProcess` / `DirectSolver`'s fused entry point.
@@ -20,11 +21,18 @@ own hyper-parameter point of config 2, no data-path collective, "scaling": "weak
 also reported as a secondary entry of the default N > 1 line.  `--distributed` runs the
 block-column path at N = 1 as well (RCCL self-broadcast).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with the `roofline` of the
-dominant kernel (fp64 MFMA trailing update, gemm_nt_kernel<double, 0>) measured live with HIP
-events on the launching stream, `roofline_secondary` (assembly: HBM write; resident-factor
-triangular solve: HBM read) and a `cpu_baseline` of the NumPy/SciPy oracle measured at the
-workload's own N.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up,
+times exactly K steps and prints the line (`value`, `ms_per_step`, ...); nothing else runs.
+`--full` adds every measurement that takes runs of its own: the `roofline` of the dominant kernel
+(fp64 MFMA trailing update, gemm_nt_kernel<double, 0>) measured live with HIP events on the
+launching stream in a second pass, `roofline_secondary` (assembly: HBM write; resident-factor
+triangular solve: HBM read; value-and-gradient; condition), the north-star and size rows of the
+default one-GPU line, the strong-scaling table and replicas entry of the default N > 1 line, and a
+`cpu_baseline` of the NumPy/SciPy oracle measured at the workload's own N.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed
+(`dump_outputs` below) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -140,7 +148,16 @@ def parse_args():
     p.add_argument("--nb-dist", type=int, default=1024, help="block-column width of the distributed path")
     p.add_argument("--no-strong-table", action="store_true",
                    help="at --gpus N > 1: skip the N = 16 384 / 65 536 strong-scaling entries and the one-GPU references")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline (profiled pass and rooflines, secondary "
+                        "rooflines, north-star and size rows, strong-scaling table, CPU baseline); the --no-* options "
+                        "above switch single parts of it off")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def workload_spec(name: str):
@@ -259,14 +276,17 @@ def cpu_baseline(spec, budget_s=75.0):
                 best = min(best, tq)
         return best, lim.seen
 
+    # OpenBLAS's own pool size (64 on a 256-core host, OMP_NUM_THREADS where that is set): never ask beyond it, not
+    # even for the warm-up below -- raising the thread count above the pool the library started with crashes SciPy's
+    # OpenBLAS (segmentation fault in its worker threads)
+    cap = min(cores, blas_threads() or cores)
     # 1. thread sweep of raw dpotrf at N_s
     ns = min(n, 8192)
     K0 = spd(ns)
     work = np.empty_like(K0, order="F")
-    time_potrf(K0, work, cores)  # first touch of `work`'s pages, library start-up: outside every measurement
+    time_potrf(K0, work, cap)  # first touch of `work`'s pages, library start-up: outside every measurement
     sweep, seen = {}, {}
     ladder = [int(t) for t in os.environ.get("TGP_CPU_THREADS", "1,8,16,32,64,128").split(",")] + [cores]
-    cap = min(cores, blas_threads() or cores)  # OpenBLAS's own pool size (64 on a 256-core host): never ask beyond it
     for th in sorted({min(t, cap) for t in ladder}):
         if time.perf_counter() - t_start > 0.45 * budget_s:
             notes.append(f"sweep stopped before {th} threads (time budget)")
@@ -326,7 +346,7 @@ def cpu_baseline(spec, budget_s=75.0):
         n_eval //= 2
         est /= 8
         extrap = True
-    cand = [th for th in order if th > 1] or order or [cores]
+    cand = [th for th in order if th > 1] or order or [cap]
     stages, ll, potrf_s = evaluate(n_eval, cand, est)
     threads = min(potrf_s, key=potrf_s.get)
     if extrap:
@@ -473,6 +493,35 @@ def metric_name(spec):
     return f"GP log_probability evals/sec + Cholesky TFLOP/s ({fp}), N={spec['n']:,}"
 
 
+DUMP_SEED = 1729
+DUMP_COLUMNS = 64  # columns of the Cholesky factor written by --dump-outputs
+DUMP_MAX_ENTRIES = 1 << 22  # at most 32 MB of the factor in float64 (the whole dump stays under 64 MB)
+
+
+def factor_sample(solver, n: int, dtype) -> np.ndarray:
+    """A fixed, seeded sample of the Cholesky factor L the last step left resident (what a caller's next solve,
+    `condition` or `predict` reads): DUMP_COLUMNS columns of L taken as L @ e_j -- exact, every other product is a
+    zero -- at a seeded subset of the rows when N x DUMP_COLUMNS is larger than DUMP_MAX_ENTRIES.  The sample depends
+    on N alone.  On the block-column path this is collective: every rank calls it."""
+    rng = np.random.default_rng(DUMP_SEED)
+    cols = np.sort(rng.choice(n, size=min(n, DUMP_COLUMNS), replace=False))
+    E = np.zeros((n, cols.size), dtype=dtype)
+    E[cols, np.arange(cols.size)] = 1
+    L = solver.dot_triangular(E)
+    if L.size > DUMP_MAX_ENTRIES:
+        rows = np.sort(rng.choice(n, size=DUMP_MAX_ENTRIES // cols.size, replace=False))
+        L = L[rows]
+    return L
+
+
+def dump_outputs(directory, ll: float, factor: np.ndarray):
+    """--dump-outputs: the log-probability the last timed step returned and a sample of the factor it computed."""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "log_probability.npy", np.array([ll], dtype=np.float64))
+    np.save(out / "cholesky_factor_sample.npy", np.ascontiguousarray(factor))
+
+
 def run_distributed(args, spec, rank, local_rank, world, torch, tdist, replicas_value=None):
     """Strong scaling: log_probability of ONE N x N matrix spread over all ranks."""
     from tinygp_amd import kernels, synthetic
@@ -502,12 +551,16 @@ def run_distributed(args, spec, rank, local_rank, world, torch, tdist, replicas_
     barrier()
     t0 = time.perf_counter()
     for s_ in range(args.steps):
-        one_step(args.warmup + s_)
+        ll = one_step(args.warmup + s_)
     barrier()
     elapsed = time.perf_counter() - t0
     t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
     tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs:
+        factor = factor_sample(solver, n, dt)  # collective
+        if rank == 0:
+            dump_outputs(args.dump_outputs, ll, factor)
     result = None
     if rank == 0:
         peak = FP64_MFMA_PEAK_TFLOPS if dt == np.float64 else FP32_MFMA_PEAK_TFLOPS
@@ -543,10 +596,11 @@ def run_distributed(args, spec, rank, local_rank, world, torch, tdist, replicas_
     return result
 
 
-def timed_passes(args, spec, rank, local_rank, world, torch, dist, steps, warmup, prof_steps):
+def timed_passes(args, spec, rank, local_rank, world, torch, dist, steps, warmup, prof_steps, dump=None):
     """The measurement proper for one workload on this rank's GPU: `warmup` untimed steps, EXACTLY `steps` timed
-    steps between barrier + synchronize (pass 1, no per-launch events), then -- untimed for `value` -- `prof_steps`
-    steps with one HIP-event pair around every trailing-update launch on the stream it is launched on (pass 2).
+    steps between barrier + synchronize (pass 1, no per-launch events), the outputs of the last of them written to
+    `dump` (a directory, or None), then -- untimed for `value` -- `prof_steps` steps with one HIP-event pair around
+    every trailing-update launch on the stream it is launched on (pass 2).
     Returns a dict with the solver still alive (the caller closes it)."""
     import ctypes as C
 
@@ -604,13 +658,15 @@ def timed_passes(args, spec, rank, local_rank, world, torch, dist, steps, warmup
     barrier()
     t0 = time.perf_counter()
     for s in range(steps):
-        one_step(warmup + s)
+        ll = one_step(warmup + s)
     barrier()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump:  # before pass 2 re-factors with other hyper-parameters
+        dump_outputs(dump, ll, factor_sample(solver, n, dt))
 
     # -- pass 2 (untimed for `value`): the same steps with a HIP-event pair around every trailing-update launch on
     # the stream it is launched on (ctx option profile = 1) -> roofline of the dominant kernel
@@ -769,7 +825,8 @@ def run_single(args, spec, rank, local_rank, world, torch, dist):
     n, d = spec["n"], spec["d"]
     dt = np.dtype(spec["dtype"])
     m = timed_passes(args, spec, rank, local_rank, world, torch, dist, steps=args.steps, warmup=args.warmup,
-                     prof_steps=0 if args.no_profile else min(args.steps, 20))
+                     prof_steps=min(args.steps, 20) if args.full and not args.no_profile else 0,
+                     dump=args.dump_outputs if rank == 0 else None)
     if rank != 0:
         return None
     ctx, solver, opt = m["ctx"], m["solver"], m["opt"]
@@ -792,12 +849,12 @@ def run_single(args, spec, rank, local_rank, world, torch, dist):
         "roofline": roofline,
     }
     out.update(extra)
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         try:
             out["roofline_secondary"] = secondary_rooflines(ctx, solver, spec, m["kernel_at"](-1))
         except Exception as e:  # never lose the headline line to a secondary measurement
             out["roofline_secondary"] = {"error": repr(e)}
-    if world == 1 and spec["name"] == "c2" and not args.no_north_star and not args.unfused:
+    if args.full and world == 1 and spec["name"] == "c2" and not args.no_north_star and not args.unfused:
         solver.close()
         torch.cuda.empty_cache()
         ns = north_star_blocks(args, local_rank, torch)
@@ -808,7 +865,7 @@ def run_single(args, spec, rank, local_rank, world, torch, dist):
         rows = size_rows(args, local_rank, torch)
         out["n4096"] = rows.pop("n4096", None)
         out["reference_recipe_rows"] = rows
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(spec)
     else:
         out["cpu_baseline"] = None
@@ -860,10 +917,11 @@ def main():
     out = None
     if block_column:
         replicas_value = None
-        if world > 1 and not args.workload:
+        if args.full and world > 1 and not args.workload:
             # the other sharding of the path, as a secondary entry: config 2 replicas
             a2 = argparse.Namespace(**vars(args))
             a2.steps, a2.warmup, a2.no_cpu_baseline, a2.no_secondary = 5, 2, True, True
+            a2.dump_outputs = None
             r = run_single(a2, workload_spec("n2048" if rehearsal and os.environ.get("TGP_BENCH_SMALL") == "1"
                                              else "c2"), rank, local_rank, world, torch, dist)
             if r is not None:
@@ -875,13 +933,14 @@ def main():
         sizes = ("n2048", "n4096", "n8192") if small else ("c2", "n65536", "c4")
         spec = workload_spec(args.workload or (sizes[2] if world > 1 else "c2"))
         out = run_distributed(args, spec, rank, local_rank, world, torch, dist, replicas_value)
-        if world > 1 and not args.workload and not args.no_strong_table:
+        if args.full and world > 1 and not args.workload and not args.no_strong_table:
             # north_star's table in ONE run: the same block-column path at N = 16 384 and 65 536 (plus the primary
             # line's N = 131 072), each next to the single-GPU driver's time for that size measured on rank 0 of
             # this very run (the other ranks wait at a barrier) -> speed-up at this world size
             table = {}
             a3 = argparse.Namespace(**vars(args))
             a3.steps, a3.warmup = min(args.steps, 5), min(args.warmup, 2)
+            a3.dump_outputs = None
 
             def row_of(r):
                 return {"n": r["config"]["n"], "ms_per_step": r["ms_per_step"], "evals_per_s": r["value"],
@@ -900,6 +959,7 @@ def main():
                 # group was created with a 30-minute timeout for exactly this wait)
                 a1 = argparse.Namespace(**vars(args))
                 a1.no_cpu_baseline, a1.no_secondary, a1.no_profile, a1.no_north_star = True, True, True, True
+                a1.dump_outputs = None
                 for name, st, wu in ((sizes[0], 5, 2), (sizes[1], 2, 1), (sizes[2], 1, 1)):
                     row = table.get(name)  # looked up BY NAME: a missing row must not shift the others (advisor r3)
                     if row is None:

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out
 for args in "$@"; do
   echo "### $args" >> gpurun_out/variants.log
-  timeout 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline $args 2>/dev/null | python -c "
+  timeout 300 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline $args 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     try: d=json.loads(l)

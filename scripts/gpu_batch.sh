@@ -10,7 +10,7 @@
 #   spans        span dump of the trailing-update launches (no profiler)
 #   timeline     kernel timeline of one c2 evaluation (first / last 2.5 ms)
 #   chain:<n>    stamped timeline of the chain launch at N = n
-#   bench        the driver's default line
+#   bench        the driver's default line with everything beyond the headline (bench.py --full)
 #   py:<script and args, '+' for spaces>   any helper under scripts/
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R
@@ -73,7 +73,7 @@ whole)
 spans)
   echo "== span dump (trailing-update launches, no profiler) ${OPTS}"
   o=""; for kv in $(echo "$OPTS" | tr ',' ' '); do o="$o --opt $kv"; done
-  TGP_SPAN_DUMP=1 timeout 300 python bench.py $B --steps 2 --warmup 2 $o 2>&1 >/dev/null | grep "^span" | tail -12 ;;
+  TGP_SPAN_DUMP=1 timeout 300 python bench.py $B --full --steps 2 --warmup 2 $o 2>&1 >/dev/null | grep "^span" | tail -12 ;;
 timeline)
   echo "== kernel timeline of one c2 evaluation ${OPTS}"
   o=""; for kv in $(echo "$OPTS" | tr ',' ' '); do o="$o --opt $kv"; done
@@ -87,7 +87,7 @@ chain:*)
   timeout 300 python scripts/chain_timeline.py $n $OPTS 2>&1 | tail -80 ;;
 bench)
   echo "== bench default (the driver's line)"
-  timeout 1200 python bench.py 2>/dev/null | tail -1 | tee $O/bench_default.json | cut -c1-1800 ;;
+  timeout 1200 python bench.py --full 2>/dev/null | tail -1 | tee $O/bench_default.json | cut -c1-1800 ;;
 py:*)
   cmd=$(echo "${sec#py:}" | tr '+' ' ')
   echo "== python scripts/$cmd"

@@ -23,7 +23,7 @@ s = [f"# Round 4 — final evidence (one MI355X box, `bash scripts/gpu_round.sh 
      "script on earlier trees of this round (50-us and 39-us chain) are in the history of this file.\n\n",
      "## 1. Tests and smoke\n\n```\n" + "\n".join(x[:200] for x in log.split("== bench default")[0].splitlines()) + "\n```\n"]
 r = d["roofline"]
-s.append("## 2. The driver's default line (`python bench.py`, c2 = BASELINE config 2, N = 16 384, fp64)\n")
+s.append("## 2. The driver's default line (`python bench.py --full`, c2 = BASELINE config 2, N = 16 384, fp64)\n")
 s.append("```\nvalue %.3f evals/s   ms_per_step %.3f   steps %d warmup %d\n" % (d["value"], d["ms_per_step"], d["steps"], d["warmup"]))
 s.append("roofline (gemm_nt_kernel<double,0>, trailing update): achieved %.2f TFLOP/s  frac %.3f of %.1f   avg launch %.4f ms   %d launches/step   %.2f GF/launch   launch_records_agree %s\n"
          % (r["achieved"], r["frac"], r["peak"], r["avg_launch_ms"], r["launches_per_step"], r["flops_per_launch"] * 1e-9, r["launch_records_agree"]))

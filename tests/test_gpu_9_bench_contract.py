@@ -52,11 +52,11 @@ def test_replicas_line_at_two_ranks():
 
 
 def test_default_multi_gpu_line_carries_the_strong_scaling_table():
-    """The driver's N > 1 line with NO workload override: primary = the block-column path (BASELINE config 4),
-    `replicas` = the other sharding, `strong_scaling.rows` = N in {16 384, 65 536, 131 072} through the same path,
-    each with the single-GPU driver's time measured on rank 0 of the same run -- rehearsed here at shrunken sizes
-    (TGP_BENCH_SMALL=1: 2 048 / 4 096 / 8 192) so that it takes seconds."""
-    d = _launch(2, ["--no-cpu-baseline"], 29815, TGP_BENCH_SMALL="1")
+    """The driver's N > 1 line with NO workload override and `--full`: primary = the block-column path (BASELINE
+    config 4), `replicas` = the other sharding, `strong_scaling.rows` = N in {16 384, 65 536, 131 072} through the
+    same path, each with the single-GPU driver's time measured on rank 0 of the same run -- rehearsed here at
+    shrunken sizes (TGP_BENCH_SMALL=1: 2 048 / 4 096 / 8 192) so that it takes seconds."""
+    d = _launch(2, ["--full", "--no-cpu-baseline"], 29815, TGP_BENCH_SMALL="1")
     assert d["rehearsal"] is True and d["scaling"] == "strong" and d["config"]["n"] == 8192
     assert d["replicas"]["scaling"] == "weak" and d["replicas"]["value"] > 0
     rows = d["strong_scaling"]["rows"]
@@ -72,7 +72,7 @@ def test_default_line_at_eight_ranks_through_the_host_staged_transport():
     eight on the ONE GPU of a test box (every collective staged through host memory and gloo -- RCCL refuses two ranks
     on one device): the launch line of the contract, the block-column path with seven peers per panel, the replicas
     mode, the strong-scaling table with the one-GPU references on rank 0 -- at shrunken sizes (TGP_BENCH_SMALL=1)."""
-    d = _launch(8, ["--no-cpu-baseline"], 29819, timeout=1500, TGP_BENCH_SMALL="1")
+    d = _launch(8, ["--full", "--no-cpu-baseline"], 29819, timeout=1500, TGP_BENCH_SMALL="1")
     assert d["rehearsal"] is True and d["n_gpus"] == 8 and d["scaling"] == "strong" and d["config"]["n"] == 8192
     assert d["config"]["parallelism"] == "block-cyclic columns x8"
     assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
@@ -88,11 +88,12 @@ def test_default_line_at_eight_ranks_through_the_host_staged_transport():
 
 
 def test_default_one_gpu_line_carries_the_north_star_blocks():
-    """Round-3 judge, item 1: the default one-GPU line (BASELINE config 2) also measures north_star's target size
+    """Round-3 judge, item 1: the `--full` one-GPU line (BASELINE config 2) also measures north_star's target size
     (N = 65 536 with config 2's kernel) and BASELINE config 3 in the same run and reports their trailing-update
     rooflines as `roofline_n65536` / `roofline_c3` -- rehearsed at small sizes (TGP_BENCH_SMALL=1)."""
     env = dict(os.environ, TGP_BENCH_SMALL="1", OMP_NUM_THREADS="4")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+                        "--no-cpu-baseline"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -127,3 +128,52 @@ def test_default_one_gpu_line_carries_the_north_star_blocks():
     assert vg["bound"] == "mfma" and 0 < vg["frac"] < 1 and vg["algorithmic_flops"] == 16384.0**3
     cd = sec[kinds.index("condition")]
     assert cd["bound"] == "mfma" and 0 < cd["frac"] < 1 and cd["m_test"] == 4096
+
+
+def test_plain_one_gpu_line_and_dumped_outputs(tmp_path):
+    """A plain run (no `--full`) times exactly `--steps` steps and measures nothing else; `--dump-outputs` writes what
+    the last timed step computed: its log-probability and a seeded sample of the Cholesky factor it left resident,
+    both checked against LAPACK at that step's hyper-parameters on the same seeded inputs."""
+    import importlib.util
+
+    import numpy as np
+
+    from oracle import tinygp_np as o
+    from tinygp_amd import synthetic
+
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--workload", "n2048", "--dump-outputs", str(out)],
+                       cwd=ROOT, env=dict(os.environ, OMP_NUM_THREADS="4"), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["config"]["n"] == 2048
+    assert d["unit"] == "evals/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["value"] > 0
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    # nothing beyond the headline ran
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert not {"roofline_secondary", "north_star_workloads", "n4096", "stage_ms_profiled_pass"} & set(d)
+
+    assert sorted(p.name for p in out.iterdir()) == ["cholesky_factor_sample.npy", "log_probability.npy"]
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    ll, sample = np.load(out / "log_probability.npy"), np.load(out / "cholesky_factor_sample.npy")
+    assert ll.dtype == np.float64 and ll.shape == (1,) and sample.dtype == np.float64
+    # the last timed step is step warmup + steps - 1 = 4 of bench.py's hyper-parameter trajectory
+    u = ((4 * 7) % 11 - 5) / 5.0
+    kern = synthetic.config_kernel(o, "expsq", amp=1.5 * (1 + 0.02 * u), scale=2.5 * (1 + 0.03 * u))
+    X, y = synthetic.make_inputs(2048, 1)
+    np.testing.assert_allclose(ll[0], o.GaussianProcess(kern, X, diag=0.01).log_probability(y), rtol=1e-8)
+    L = np.linalg.cholesky(kern(X, X) + 0.01 * np.eye(2048))
+    spec = importlib.util.spec_from_file_location("bench", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Host:
+        def dot_triangular(self, E):
+            return L @ E
+
+    want = bench.factor_sample(Host(), 2048, np.float64)
+    assert sample.shape == want.shape == (2048, bench.DUMP_COLUMNS)
+    np.testing.assert_allclose(sample, want, rtol=5e-7, atol=5e-7)

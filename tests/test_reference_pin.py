@@ -1,29 +1,26 @@
 """Parity pin to the reference's OWN execution.
 
-``tests/golden/ref_*.npz`` were produced by importing ``/root/reference/src/tinygp``
-unmodified on top of the NumPy stand-ins for jax / equinox in ``oracle/refshim``
-(``oracle/refshim/make_ref_golden.py``).  Here:
+``tests/golden/ref_*.npz`` were produced by importing the reference package unmodified on
+top of the NumPy stand-ins for jax / equinox in ``oracle/refshim``
+(``oracle/refshim/make_ref_golden.py``; the reference's source is not part of this
+repository, so the suite checks the committed fixtures only).  Here:
 
 * the stand-ins are unit-tested (they are the only thing between the reference's source and
   its numbers);
 * the NumPy oracle is checked against those reference outputs (so "oracle == reference" is
-  a tested statement, and the GPU parity tests can use either);
-* where the reference tree exists (the build container), the generation is re-run and must
-  reproduce the committed fixtures.
+  a tested statement, and the GPU parity tests can use either).
 """
 import subprocess
 import sys
 from pathlib import Path
 
 import numpy as np
-import pytest
 
 import _cases
 from oracle import tinygp_np as o
 
 ROOT = Path(__file__).resolve().parent.parent
 SHIM = ROOT / "oracle" / "refshim"
-REFERENCE = Path("/root/reference/src/tinygp")
 
 
 # ---- the stand-ins ----------------------------------------------------------------------------
@@ -195,20 +192,3 @@ def test_transforms_dense_noise_and_matmul_equal_reference(golden_dir):
         np.testing.assert_allclose(kk.matmul(T, y=V), r[f"matmul_{name}__x1_y"], rtol=1e-12, atol=1e-14)
         np.testing.assert_allclose(kk.matmul(T, V[:, 0]), r[f"matmul_{name}__x1_vec"], rtol=1e-12, atol=1e-14)
 
-
-# ---- reproducibility of the fixtures (build container only) ------------------------------------
-@pytest.mark.skipif(not REFERENCE.exists(), reason="the reference tree only exists in the build container")
-def test_reference_rerun_reproduces_the_committed_fixtures(tmp_path, golden_dir):
-    r = subprocess.run([sys.executable, str(SHIM / "make_ref_golden.py"), "--fast", "--out", str(tmp_path)],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr
-    for fname in ("ref_kernels.npz", "ref_gp.npz", "ref_configs.npz", "ref_transforms.npz"):
-        new, old = np.load(tmp_path / fname), np.load(golden_dir / fname)
-        assert set(new.files) <= set(old.files)
-        for k in new.files:
-            if fname == "ref_kernels.npz":
-                np.testing.assert_array_equal(new[k], old[k], err_msg=k)
-            else:  # LAPACK thread count may move the last bits
-                np.testing.assert_allclose(new[k], old[k], rtol=1e-10, atol=1e-12, err_msg=k)
-    # nothing was written into the reference tree
-    assert not list(REFERENCE.rglob("__pycache__"))
