@@ -61,9 +61,10 @@ extern "C" {
 #define TGP_TILE 128
 
 /* ---- kernel program -------------------------------------------------------------
- * A tinygp kernel tree (kernels/base.py:170-209 Sum/Product/Constant over the stationary
- * leaves of kernels/stationary.py:59-235) flattened to postfix.  Leaves push a value,
- * ADD/MUL pop two and push one.  `metric` selects kernels/distance.py:41-59.
+ * A tinygp kernel tree (kernels/base.py:170-256 Sum/Product/Constant/DotProduct/Polynomial
+ * over the stationary leaves of kernels/stationary.py:59-235) flattened to postfix.  Leaves
+ * push a value, ADD/MUL pop two and push one, POW replaces the top of the stack.  `metric`
+ * selects kernels/distance.py:41-59.
  *   CONST : p0 = value                               (base.py:205-209)
  *   EXP   : exp(-dist/p0)                            (stationary.py:76-82)
  *   EXPSQ : exp(-0.5 * sqdist/p0^2)                  (stationary.py:104-106)
@@ -72,11 +73,15 @@ extern "C" {
  *   COS   : cos(2 pi dist/p0)                        (stationary.py:173-175)
  *   ESS   : exp(-p1 sin^2(pi dist/p0))               (stationary.py:202-205)
  *   RQ    : (1 + 0.5 sqdist/p0^2 / p1)^(-p1)         (stationary.py:232-235)
+ *   DOT   : sum_k (x_ik/p0)(x_jk/p0) + p1^2          (base.py:212-256; metric must be L1, ignored)
+ *   POW   : v -> pow(v, p0), v the top of the stack  (base.py:231-256; unary)
+ * DotProduct() = [DOT(1, 0)];  Polynomial(order, scale, sigma) = [DOT(scale, sigma), POW(order)].
  * dist / sqdist: L1 -> sum|d|, (sum|d|)^2 ; L2 -> zero-safe sqrt(sum d^2), sum d^2.
  */
 enum {
   TGP_K_CONST = 0, TGP_K_EXP = 1, TGP_K_EXPSQ = 2, TGP_K_M32 = 3, TGP_K_M52 = 4,
-  TGP_K_COS = 5, TGP_K_ESS = 6, TGP_K_RQ = 7, TGP_K_ADD = 16, TGP_K_MUL = 17
+  TGP_K_COS = 5, TGP_K_ESS = 6, TGP_K_RQ = 7, TGP_K_DOT = 8, TGP_K_ADD = 16, TGP_K_MUL = 17,
+  TGP_K_POW = 18
 };
 enum { TGP_METRIC_L1 = 0, TGP_METRIC_L2 = 1 };
 

@@ -1052,8 +1052,8 @@ int tgp_solver_grad(tgp_solver* s, const void* resid_host, double* logprob, doub
     }
     for (int i = 0; i < s->kp.n && fast == 0; ++i) {
       const int op = s->kp.op[i];
-      if (op >= TGP_K_ADD) continue;
-      const int nparam = (op == TGP_K_ESS || op == TGP_K_RQ) ? 2 : 1;
+      if (op == TGP_K_ADD || op == TGP_K_MUL) continue;  // (POW: one parameter, the order)
+      const int nparam = (op == TGP_K_ESS || op == TGP_K_RQ || op == TGP_K_DOT) ? 2 : 1;
       for (int q = 0; q < nparam; ++q) {
         TGP_TRY(launch_kgrad<T>(ctx, s->kp, i, q, s->n, s->d, (const T*)s->X, (const T*)alpha,
                                 Kinv, ldk, ctx->d_scal + 2));

@@ -919,8 +919,8 @@ int tgp_dist_grad_chunk(tgp_dist* h, int64_t c0, int64_t nrhs, const void* kcols
     const T* Kc = (const T*)kcols_dev;
     for (int i = 0; i < h->kp.n; ++i) {
       const int op = h->kp.op[i];
-      if (op >= TGP_K_ADD) continue;
-      const int nparam = (op == TGP_K_ESS || op == TGP_K_RQ) ? 2 : 1;
+      if (op == TGP_K_ADD || op == TGP_K_MUL) continue;  // (POW: one parameter, the order)
+      const int nparam = (op == TGP_K_ESS || op == TGP_K_RQ || op == TGP_K_DOT) ? 2 : 1;
       for (int q = 0; q < nparam; ++q)
         TGP_TRY(launch_kgrad_cols<T>(ctx, h->kp, i, q, h->n, h->d, (const T*)h->X, alpha, Kc, nrhs, c0, h->nb, h->G,
                                      h->rank, h->d_grad + 2 * i + q));

@@ -1,4 +1,5 @@
-// kmat.hip -- pairwise-distance + stationary-kernel evaluator (K1/K2/K3/K9 of SURVEY 2a).
+// kmat.hip -- pairwise-distance + stationary-kernel evaluator (K1/K2/K3/K9 of SURVEY 2a), with the
+// dot-product leaves of reference kernels/base.py:212-256 (DotProduct, Polynomial) in the same loop.
 //
 // Replaces reference kernels/base.py:84-103 (nested vmap of Kernel.evaluate) fused with
 // noise.py:77-78 (diagonal scatter-add).  HBM-write bound: every lane owns one ROW of a
@@ -36,8 +37,14 @@ template <> struct MathC<float> {
 // distance.py:51-56: zero-safe sqrt; distance.py:30-38: L1 "squared" = distance^2
 // FAM = 1: the program holds only Constant / Exp / ExpSquared / Matern leaves (checked on the
 // host): the cosine, sine and power paths -- and their registers -- are compiled out.
+// FAM = 2: the program holds a DOT leaf or a POW (kfamily()): every leaf, plus r3 = sum x_ik x_jk,
+// which only this family's loops accumulate (FAM 0 / 1 callers pass 0 and compile as before).
+// DOT divides the RAW sum once by p0^2 instead of dividing every coordinate first as the
+// reference does ((X1 / scale) @ (X2 / scale), base.py:254-256): one accumulator serves leaves of
+// different scales, at a parity cost of a few ulp of sum |x_ik x_jk| / p0^2 (the rounding of p0^2
+// and of the quotient; the reference's own matmul has no fixed summation order either).
 template <typename T, int FAM = 0>
-__device__ __forceinline__ T leaf_value(const KProg& kp, int i, T r1, T r2) {
+__device__ __forceinline__ T leaf_value(const KProg& kp, int i, T r1, T r2, T r3 = T(0)) {
   const int op = kp.op[i];
   const bool l2 = kp.metric[i] == TGP_METRIC_L2;
   auto dist = [&]() -> T { return l2 ? ((r2 == T(0)) ? r1 : sqrt(r2)) : r1; };
@@ -53,7 +60,7 @@ __device__ __forceinline__ T leaf_value(const KProg& kp, int i, T r1, T r2) {
                       return (T(1) + a + (a * a) / T(3)) * exp(-a); }
     default: break;
   }
-  if constexpr (FAM == 0) {
+  if constexpr (FAM != 1) {
     switch (op) {
       case TGP_K_COS: return cos(MathC<T>::TWO_PI * (dist() / p0));
       case TGP_K_ESS: { const T s = sin(MathC<T>::PI * (dist() / p0)); return exp(-p1 * (s * s)); }
@@ -61,41 +68,54 @@ __device__ __forceinline__ T leaf_value(const KProg& kp, int i, T r1, T r2) {
       default: break;
     }
   }
+  if constexpr (FAM == 2) {
+    if (op == TGP_K_DOT) return r3 / (p0 * p0) + p1 * p1;
+  }
   (void)p1;
+  (void)r3;
   return T(0);
 }
 
-// Evaluate the postfix program for one pair given r1 = sum|d| and r2 = sum d^2.
-// Programs of one leaf, or of two leaves and one operator (e.g. `amp**2 * ExpSquared(l)`),
-// take a direct path; anything else runs the general stack machine, whose evaluation stack
-// lives in 8 named registers (no runtime-indexed array -> no scratch).  All branches are
-// wave-uniform (the program sits in kernarg / SGPRs).
+// Evaluate the postfix program for one pair given r1 = sum|d|, r2 = sum d^2 (and, FAM = 2,
+// r3 = sum x_ik x_jk).  Programs of one leaf, or of two leaves and one operator (e.g.
+// `amp**2 * ExpSquared(l)`), take a direct path; anything else runs the general stack machine,
+// whose evaluation stack lives in 8 named registers (no runtime-indexed array -> no scratch).
+// All branches are wave-uniform (the program sits in kernarg / SGPRs).  Only FAM = 2 programs
+// hold the unary POW (ops >= TGP_K_ADD are binary everywhere else).
 template <typename T, int FAM = 0>
-__device__ __forceinline__ T eval_kprog(const KProg& kp, T r1, T r2) {
-  if (kp.n == 1) return leaf_value<T, FAM>(kp, 0, r1, r2);
-  if (kp.n == 3 && kp.op[0] < TGP_K_ADD && kp.op[1] < TGP_K_ADD) {
-    const T a = leaf_value<T, FAM>(kp, 0, r1, r2);
-    const T b = leaf_value<T, FAM>(kp, 1, r1, r2);
+__device__ __forceinline__ T eval_kprog(const KProg& kp, T r1, T r2, T r3 = T(0)) {
+  if (kp.n == 1) return leaf_value<T, FAM>(kp, 0, r1, r2, r3);
+  if (kp.n == 3 && kp.op[0] < TGP_K_ADD && kp.op[1] < TGP_K_ADD &&
+      (FAM != 2 || kp.op[2] == TGP_K_ADD || kp.op[2] == TGP_K_MUL)) {
+    const T a = leaf_value<T, FAM>(kp, 0, r1, r2, r3);
+    const T b = leaf_value<T, FAM>(kp, 1, r1, r2, r3);
     return (kp.op[2] == TGP_K_ADD) ? (a + b) : (a * b);
   }
   T s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0;
   for (int i = 0; i < kp.n; ++i) {
     const int op = kp.op[i];
+    if constexpr (FAM == 2) {
+      if (op == TGP_K_POW) {  // base.py:254-256: (dot + sigma^2) ** order
+        s0 = pow(s0, T(kp.p0[i]));
+        continue;
+      }
+    }
     if (op >= TGP_K_ADD) {
       const T r = (op == TGP_K_ADD) ? (s1 + s0) : (s1 * s0);
       s0 = r; s1 = s2; s2 = s3; s3 = s4; s4 = s5; s5 = s6; s6 = s7;
       continue;
     }
-    const T v = leaf_value<T, FAM>(kp, i, r1, r2);
+    const T v = leaf_value<T, FAM>(kp, i, r1, r2, r3);
     s7 = s6; s6 = s5; s5 = s4; s4 = s3; s3 = s2; s2 = s1; s1 = s0; s0 = v;
   }
   return s0;
 }
 
 // d(leaf)/d(param) at the pair's distances: param 0 = p0 (scale or constant), 1 = p1
-// (gamma / alpha).  Derived from the forms of kernels/stationary.py:76-235.
-template <typename T>
-__device__ __forceinline__ T leaf_deriv(const KProg& kp, int i, int param, T r1, T r2) {
+// (gamma / alpha / sigma).  Derived from the forms of kernels/stationary.py:76-235 and (FAM = 2)
+// of DOT, u = s + p1^2 with s = r3 / p0^2:  du/dp0 = -2 s / p0,  du/dp1 = 2 p1.
+template <typename T, int FAM = 0>
+__device__ __forceinline__ T leaf_deriv(const KProg& kp, int i, int param, T r1, T r2, T r3 = T(0)) {
   const int op = kp.op[i];
   const bool l2 = kp.metric[i] == TGP_METRIC_L2;
   // (the derivative passes are not the hot ones: both distances up front)
@@ -119,19 +139,43 @@ __device__ __forceinline__ T leaf_deriv(const KProg& kp, int i, int param, T r1,
     case TGP_K_RQ: { const T q = T(0.5) * (sq / (p0 * p0)) / p1;  // r^2 / (2 alpha l^2)
                      const T u = T(1) + q, v = pow(u, -p1);
                      return param == 0 ? v / u * sq / (p0 * p0 * p0) : v * (q / u - log(u)); }
-    default: return T(0);
+    default: break;
   }
+  if constexpr (FAM == 2) {
+    if (op == TGP_K_DOT) return param == 0 ? T(-2) * (r3 / (p0 * p0)) / p0 : T(2) * p1;
+  }
+  (void)r3;
+  return T(0);
+}
+
+// POW on the stack: (v, dv) -> (v^p, p v^(p-1) dv [+ v^p log v when p itself is differentiated]).
+// The log is taken of v with v == 0 replaced by 1 -- JAX's rule for x ** y (a zero base gives 0,
+// not NaN); a negative base gives NaN there, as in the reference.
+template <typename T>
+__device__ __forceinline__ void pow_deriv(T p, bool seed, T& v, T& dv) {
+  const T w = pow(v, p);
+  T d = p * pow(v, p - T(1)) * dv;
+  if (seed) d += w * log(v == T(0) ? T(1) : v);
+  v = w;
+  dv = d;
 }
 
 // Forward-mode derivative of the whole program with respect to ONE leaf parameter: the stack
-// carries (value, derivative) pairs; only leaf `which_op` seeds a non-zero derivative.
-template <typename T>
+// carries (value, derivative) pairs; only op `which_op` (a leaf, or FAM = 2 a POW) seeds a
+// non-zero derivative.
+template <typename T, int FAM = 0>
 __device__ __forceinline__ T eval_kprog_deriv(const KProg& kp, int which_op, int which_param, T r1,
-                                              T r2) {
+                                              T r2, T r3 = T(0)) {
   T s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0;
   T d0 = 0, d1 = 0, d2 = 0, d3 = 0, d4 = 0, d5 = 0, d6 = 0, d7 = 0;
   for (int i = 0; i < kp.n; ++i) {
     const int op = kp.op[i];
+    if constexpr (FAM == 2) {
+      if (op == TGP_K_POW) {
+        pow_deriv<T>(T(kp.p0[i]), i == which_op, s0, d0);
+        continue;
+      }
+    }
     if (op >= TGP_K_ADD) {
       const T v = (op == TGP_K_ADD) ? (s1 + s0) : (s1 * s0);
       const T dv = (op == TGP_K_ADD) ? (d1 + d0) : (d1 * s0 + s1 * d0);
@@ -139,8 +183,8 @@ __device__ __forceinline__ T eval_kprog_deriv(const KProg& kp, int which_op, int
       d0 = dv; d1 = d2; d2 = d3; d3 = d4; d4 = d5; d5 = d6; d6 = d7;
       continue;
     }
-    const T v = leaf_value<T>(kp, i, r1, r2);
-    const T dv = (i == which_op) ? leaf_deriv<T>(kp, i, which_param, r1, r2) : T(0);
+    const T v = leaf_value<T, FAM == 2 ? 2 : 0>(kp, i, r1, r2, r3);
+    const T dv = (i == which_op) ? leaf_deriv<T, FAM>(kp, i, which_param, r1, r2, r3) : T(0);
     s7 = s6; s6 = s5; s5 = s4; s4 = s3; s3 = s2; s2 = s1; s1 = s0; s0 = v;
     d7 = d6; d6 = d5; d5 = d4; d4 = d3; d3 = d2; d2 = d1; d1 = d0; d0 = dv;
   }
@@ -153,12 +197,20 @@ __device__ __forceinline__ T eval_kprog_deriv(const KProg& kp, int which_op, int
 // coordinates through dist / p0 resp. sq / p0^2 only, so
 //   d leaf / d log s_d = -p0 * (d leaf / d p0) * w_d,   w_d = dx_d^2 / r2 (L2 metric) or |dx_d| / r1 (L1),
 // (the w_d sum to one: scaling every dimension is scaling 1 / p0).  w1 / w2 are this pair's weights.
-template <typename T>
-__device__ __forceinline__ T eval_kprog_deriv_dim(const KProg& kp, T r1, T r2, T w1, T w2) {
+// FAM = 2: a DOT leaf contributes 2 (z_id / p0)(z_jd / p0), zz = z_id z_jd, and POW chains.
+template <typename T, int FAM = 0>
+__device__ __forceinline__ T eval_kprog_deriv_dim(const KProg& kp, T r1, T r2, T w1, T w2, T r3 = T(0),
+                                                  T zz = T(0)) {
   T s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0;
   T d0 = 0, d1 = 0, d2 = 0, d3 = 0, d4 = 0, d5 = 0, d6 = 0, d7 = 0;
   for (int i = 0; i < kp.n; ++i) {
     const int op = kp.op[i];
+    if constexpr (FAM == 2) {
+      if (op == TGP_K_POW) {
+        pow_deriv<T>(T(kp.p0[i]), false, s0, d0);
+        continue;
+      }
+    }
     if (op >= TGP_K_ADD) {
       const T v = (op == TGP_K_ADD) ? (s1 + s0) : (s1 * s0);
       const T dv = (op == TGP_K_ADD) ? (d1 + d0) : (d1 * s0 + s1 * d0);
@@ -166,9 +218,13 @@ __device__ __forceinline__ T eval_kprog_deriv_dim(const KProg& kp, T r1, T r2, T
       d0 = dv; d1 = d2; d2 = d3; d3 = d4; d4 = d5; d5 = d6; d6 = d7;
       continue;
     }
-    const T v = leaf_value<T>(kp, i, r1, r2);
+    const T v = leaf_value<T, FAM == 2 ? 2 : 0>(kp, i, r1, r2, r3);
     const T w = kp.metric[i] == TGP_METRIC_L2 ? w2 : w1;
-    const T dv = (op == TGP_K_CONST) ? T(0) : -T(kp.p0[i]) * leaf_deriv<T>(kp, i, 0, r1, r2) * w;
+    T dv = (op == TGP_K_CONST) ? T(0) : -T(kp.p0[i]) * leaf_deriv<T, FAM>(kp, i, 0, r1, r2, r3) * w;
+    if constexpr (FAM == 2) {
+      if (op == TGP_K_DOT) { const T p0 = T(kp.p0[i]); dv = T(2) * (zz / (p0 * p0)); }
+    }
+    (void)zz;
     s7 = s6; s6 = s5; s5 = s4; s4 = s3; s3 = s2; s2 = s1; s1 = s0; s0 = v;
     d7 = d6; d6 = d5; d5 = d4; d4 = d3; d3 = d2; d2 = d1; d1 = d0; d0 = dv;
   }
@@ -394,22 +450,24 @@ __global__ __launch_bounds__(256) void kmat_kernel(KProg kp, int64_t n1, int64_t
     if (gj >= cols_out) break;
     T v;
     if (gi < n1 && gj < n2) {
-      T r1 = 0, r2 = 0;
+      T r1 = 0, r2 = 0, r3 = 0;
       if constexpr (D > 0) {
 #pragma unroll
         for (int t = 0; t < D; ++t) {
           const T dx = xr[t] - s2[jl * D + t];
           r1 += fabs(dx);
           r2 += dx * dx;
+          if constexpr (FAM == 2) r3 += xr[t] * s2[jl * D + t];
         }
       } else {
         for (int t = 0; t < d; ++t) {
           const T dx = s1[il * d + t] - s2[jl * d + t];
           r1 += fabs(dx);
           r2 += dx * dx;
+          if constexpr (FAM == 2) r3 += s1[il * d + t] * s2[jl * d + t];
         }
       }
-      v = eval_kprog<T, FAM>(kp, r1, r2);
+      v = eval_kprog<T, FAM>(kp, r1, r2, r3);
       if (diag != nullptr && gi == gj) v += dg;  // noise.py:77-78 fused
     } else {
       v = ((flags & KMAT_PAD_IDENTITY) && gi == gj) ? T(1) : T(0);
@@ -420,8 +478,8 @@ __global__ __launch_bounds__(256) void kmat_kernel(KProg kp, int64_t n1, int64_t
 
 // One lower 128x128 tile: sum of w_ij (alpha_i alpha_j - Kinv_ij) dK_ij/dtheta, w = 1/2 on the
 // diagonal, 1 strictly below it, 0 above (the 1/2 of 1/2 tr(G dK) folded with symmetry).
-// partial[tile] gets the tile's sum; fixed LDS tree -> deterministic.
-template <typename T>
+// partial[tile] gets the tile's sum; fixed LDS tree -> deterministic.  FAM: 0, or 2 (kfamily()).
+template <typename T, int FAM>
 __global__ __launch_bounds__(256) void kgrad_kernel(KProg kp, int which_op, int which_param,
                                                     int64_t n, int d, const T* __restrict__ X,
                                                     const T* __restrict__ alpha,
@@ -453,16 +511,20 @@ __global__ __launch_bounds__(256) void kgrad_kernel(KProg kp, int which_op, int 
       const int jl = g * (KT / 2) + c;
       const int64_t gj = c0 + jl;
       if (gj >= n || gj > gi) continue;
-      T r1 = 0, r2 = 0, dxd = 0;
+      T r1 = 0, r2 = 0, r3 = 0, dxd = 0, zz = 0;
       for (int t = 0; t < d; ++t) {
         const T dx = s1[il * d + t] - s2[jl * d + t];
         r1 += fabs(dx);
         r2 += dx * dx;
+        if constexpr (FAM == 2) r3 += s1[il * d + t] * s2[jl * d + t];
         if (t == -1 - which_op) dxd = dx;  // (which_op < 0: the log-scale of input dimension -1 - which_op)
+        if constexpr (FAM == 2) {
+          if (t == -1 - which_op) zz = s1[il * d + t] * s2[jl * d + t];
+        }
       }
-      const T dk = which_op >= 0 ? eval_kprog_deriv<T>(kp, which_op, which_param, r1, r2)
-                                 : eval_kprog_deriv_dim<T>(kp, r1, r2, r1 > T(0) ? fabs(dxd) / r1 : T(0),
-                                                           r2 > T(0) ? dxd * dxd / r2 : T(0));
+      const T dk = which_op >= 0 ? eval_kprog_deriv<T, FAM>(kp, which_op, which_param, r1, r2, r3)
+                                 : eval_kprog_deriv_dim<T, FAM>(kp, r1, r2, r1 > T(0) ? fabs(dxd) / r1 : T(0),
+                                                                r2 > T(0) ? dxd * dxd / r2 : T(0), r3, zz);
       const T gij = ai * alpha[gj] - Kinv[gj * ld + gi];
       acc += double(gij) * double(dk) * (gi == gj ? 0.5 : 1.0);
     }
@@ -480,7 +542,7 @@ __global__ __launch_bounds__(256) void kgrad_kernel(KProg kp, int which_op, int 
 // (n_pad, R) ROW-major -- K^-1[i, c0 + r] at i * R + r, the layout of the distributed solves' right-hand sides --, and
 // only row tiles inside block rows THIS RANK owns contribute (block row b = row / nb belongs to rank b mod G): the ranks'
 // partial sums add up to the lower triangle of the chunk.  Tile (tr, tc): rows tr * 128 .., columns c0 + tc * 128 ...
-template <typename T>
+template <typename T, int FAM>
 __global__ __launch_bounds__(256) void kgrad_cols_kernel(KProg kp, int which_op, int which_param, int64_t n, int d,
                                                          const T* __restrict__ X, const T* __restrict__ alpha,
                                                          const T* __restrict__ Kc, int64_t R, int64_t c0, int64_t nb,
@@ -512,16 +574,20 @@ __global__ __launch_bounds__(256) void kgrad_cols_kernel(KProg kp, int which_op,
       const int jl = g * (KT / 2) + c;
       const int64_t gj = cc0 + jl;
       if (gj >= n || gj > gi) continue;
-      T r1 = 0, r2 = 0, dxd = 0;
+      T r1 = 0, r2 = 0, r3 = 0, dxd = 0, zz = 0;
       for (int t = 0; t < d; ++t) {
         const T dx = s1[il * d + t] - s2[jl * d + t];
         r1 += fabs(dx);
         r2 += dx * dx;
+        if constexpr (FAM == 2) r3 += s1[il * d + t] * s2[jl * d + t];
         if (t == -1 - which_op) dxd = dx;
+        if constexpr (FAM == 2) {
+          if (t == -1 - which_op) zz = s1[il * d + t] * s2[jl * d + t];
+        }
       }
-      const T dk = which_op >= 0 ? eval_kprog_deriv<T>(kp, which_op, which_param, r1, r2)
-                                 : eval_kprog_deriv_dim<T>(kp, r1, r2, r1 > T(0) ? fabs(dxd) / r1 : T(0),
-                                                           r2 > T(0) ? dxd * dxd / r2 : T(0));
+      const T dk = which_op >= 0 ? eval_kprog_deriv<T, FAM>(kp, which_op, which_param, r1, r2, r3)
+                                 : eval_kprog_deriv_dim<T, FAM>(kp, r1, r2, r1 > T(0) ? fabs(dxd) / r1 : T(0),
+                                                                r2 > T(0) ? dxd * dxd / r2 : T(0), r3, zz);
       const T gij = ai * alpha[gj] - Kc[gi * R + (gj - c0)];
       acc += double(gij) * double(dk) * (gi == gj ? 0.5 : 1.0);
     }
@@ -581,13 +647,20 @@ __global__ __launch_bounds__(256) void noise_grad_kernel(int64_t n, const T* __r
   if (i < n) out[i] = T(0.5) * (alpha[i] * alpha[i] - Kinv[i * ld + i]);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void kdiag_kernel(KProg kp, int64_t n, const T* __restrict__ add,
-                                                    T* __restrict__ out) {
+// FAM: 0, or 2 (kfamily()): the dot-product leaves read the point itself, r3 = sum x_ik^2
+template <typename T, int FAM>
+__global__ __launch_bounds__(256) void kdiag_kernel(KProg kp, int64_t n, int d, const T* __restrict__ X,
+                                                    const T* __restrict__ add, T* __restrict__ out) {
   const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
   if (i >= n) return;
   // evaluate_diag = evaluate(x, x) (base.py:59-66): every distance is exactly zero
-  T v = eval_kprog<T>(kp, T(0), T(0));
+  T r3 = 0;
+  if constexpr (FAM == 2) {
+    for (int t = 0; t < d; ++t) r3 += X[i * d + t] * X[i * d + t];
+  }
+  (void)d;
+  (void)X;
+  T v = eval_kprog<T, FAM>(kp, T(0), T(0), r3);
   if (add != nullptr) v += add[i];
   out[i] = v;
 }
@@ -625,16 +698,17 @@ __global__ __launch_bounds__(256) void kmat_gemv_kernel(KProg kp, int64_t n1, in
     }
     __syncthreads();
     for (int jj = 0; jj < cnt; ++jj) {
-      T r1 = 0, r2 = 0;
+      T r1 = 0, r2 = 0, r3 = 0;
 #pragma unroll
       for (int t = 0; t < TGP_MAX_DIM; ++t) {
         if (t < d) {
           const T dx = xi[t] - sx[jj * d + t];
           r1 += fabs(dx);
           r2 += dx * dx;
+          if constexpr (FAM == 2) r3 += xi[t] * sx[jj * d + t];
         }
       }
-      const T kv = eval_kprog<T, FAM>(kp, r1, r2);
+      const T kv = eval_kprog<T, FAM>(kp, r1, r2, r3);
 #pragma unroll
       for (int r = 0; r < GV_NV; ++r) acc[r] += kv * sv[jj * GV_NV + r];
     }
@@ -803,10 +877,14 @@ int make_kprog(const tgp_kop* prog, int nops, KProg* out) {
     if (op == TGP_K_ADD || op == TGP_K_MUL) {
       TGP_ARG_CHECK(depth >= 2, "kernel program: stack underflow at op %d", i);
       depth -= 1;
+    } else if (op == TGP_K_POW) {  // unary: replaces the top of the stack
+      TGP_ARG_CHECK(depth >= 1, "kernel program: stack underflow at op %d", i);
     } else {
-      TGP_ARG_CHECK(op >= TGP_K_CONST && op <= TGP_K_RQ, "kernel program: bad opcode %d at %d", op, i);
+      TGP_ARG_CHECK(op >= TGP_K_CONST && op <= TGP_K_DOT, "kernel program: bad opcode %d at %d", op, i);
       TGP_ARG_CHECK(prog[i].metric == TGP_METRIC_L1 || prog[i].metric == TGP_METRIC_L2,
                     "kernel program: bad metric at op %d", i);
+      TGP_ARG_CHECK(op != TGP_K_DOT || prog[i].metric == TGP_METRIC_L1,
+                    "kernel program: DOT takes no metric (TGP_METRIC_L1) at op %d", i);
       depth += 1;
       TGP_ARG_CHECK(depth <= TGP_KSTACK_MAX, "kernel program: stack deeper than %d", TGP_KSTACK_MAX);
     }
@@ -824,10 +902,18 @@ static bool exp_family(const KProg& kp) {
   for (int i = 0; i < kp.n; ++i) {
     const int op = kp.op[i];
     if (!(op == TGP_K_CONST || op == TGP_K_EXP || op == TGP_K_EXPSQ || op == TGP_K_M32 ||
-          op == TGP_K_M52 || op >= TGP_K_ADD))
+          op == TGP_K_M52 || op == TGP_K_ADD || op == TGP_K_MUL))
       return false;
   }
   return true;
+}
+
+// the program family of the general kernels: 2 with a DOT leaf or a POW (the only family whose
+// loops accumulate sum x_ik x_jk and know a unary op), else 1 for exp_family, else 0
+static int kfamily(const KProg& kp) {
+  for (int i = 0; i < kp.n; ++i)
+    if (kp.op[i] == TGP_K_DOT || kp.op[i] == TGP_K_POW) return 2;
+  return exp_family(kp) ? 1 : 0;
 }
 
 template <typename T>
@@ -892,10 +978,13 @@ int launch_kmat_cols(tgp_ctx* ctx, hipStream_t st, const KProg& kp, int64_t n1, 
   }
   dim3 grid((unsigned)tr, (unsigned)ntc);
   const size_t shmem = 2 * size_t(KT) * d * sizeof(T);
-  const bool fam = exp_family(kp);
+  const int fam = kfamily(kp);
 #define TGP_KMAT_LAUNCH(DD)                                                                      \
   do {                                                                                           \
-    if (fam)                                                                                     \
+    if (fam == 2)                                                                                \
+      hipLaunchKernelGGL((kmat_kernel<T, DD, 2>), grid, dim3(256), shmem, st, kp, n1, n2, d, X1, \
+                         X2, diag, out, ld, rows_out, cols_out, flags, (int)tc0, ftr, ftc);      \
+    else if (fam == 1)                                                                           \
       hipLaunchKernelGGL((kmat_kernel<T, DD, 1>), grid, dim3(256), shmem, st, kp, n1, n2, d, X1, \
                          X2, diag, out, ld, rows_out, cols_out, flags, (int)tc0, ftr, ftc);      \
     else                                                                                         \
@@ -924,10 +1013,14 @@ int launch_kmat(tgp_ctx* ctx, const KProg& kp, int64_t n1, int64_t n2, int d, co
 
 template <typename T>
 int launch_kdiag(tgp_ctx* ctx, const KProg& kp, int64_t n, int d, const T* X, const T* add, T* out) {
-  (void)X; (void)d;
   if (n == 0) return TGP_OK;
-  hipLaunchKernelGGL((kdiag_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     ctx->stream, kp, n, add, out);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (kfamily(kp) == 2) {
+    TGP_ARG_CHECK(X != nullptr && d >= 1 && d <= TGP_MAX_DIM, "kdiag: a DOT program needs the points");
+    hipLaunchKernelGGL((kdiag_kernel<T, 2>), grid, dim3(256), 0, ctx->stream, kp, n, d, X, add, out);
+  } else {
+    hipLaunchKernelGGL((kdiag_kernel<T, 0>), grid, dim3(256), 0, ctx->stream, kp, n, d, X, add, out);
+  }
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
@@ -968,6 +1061,9 @@ int launch_kmat_gemv_multi(tgp_ctx* ctx, const KProg& kp, int64_t n1, int64_t n2
     else if (fp.op == TGP_K_M52) TGP_GV2(TGP_K_M52);
 #undef TGP_GV2
 #undef TGP_GV3
+    else if (kfamily(kp) == 2)
+      hipLaunchKernelGGL((kmat_gemv_kernel<T, 2>), dim3((unsigned)rb, (unsigned)nch), dim3(256), shmem,
+                         ctx->stream, kp, n1, n2, d, X1, X2, v + r0 * n2, nv, partial, jchunk);
     else if (exp_family(kp))
       hipLaunchKernelGGL((kmat_gemv_kernel<T, 1>), dim3((unsigned)rb, (unsigned)nch), dim3(256), shmem,
                          ctx->stream, kp, n1, n2, d, X1, X2, v + r0 * n2, nv, partial, jchunk);
@@ -995,8 +1091,12 @@ int launch_kgrad(tgp_ctx* ctx, const KProg& kp, int which_op, int which_param, i
   TGP_TRY(ensure_work(ctx, size_t(tiles) * tiles * sizeof(double)));
   double* partial = static_cast<double*>(ctx->d_work);
   const size_t shmem = 2 * size_t(KT) * d * sizeof(T);
-  hipLaunchKernelGGL((kgrad_kernel<T>), dim3((unsigned)tiles, (unsigned)tiles), dim3(256), shmem,
-                     ctx->stream, kp, which_op, which_param, n, d, X, alpha, Kinv, ld, partial);
+  if (kfamily(kp) == 2)
+    hipLaunchKernelGGL((kgrad_kernel<T, 2>), dim3((unsigned)tiles, (unsigned)tiles), dim3(256), shmem,
+                       ctx->stream, kp, which_op, which_param, n, d, X, alpha, Kinv, ld, partial);
+  else
+    hipLaunchKernelGGL((kgrad_kernel<T, 0>), dim3((unsigned)tiles, (unsigned)tiles), dim3(256), shmem,
+                       ctx->stream, kp, which_op, which_param, n, d, X, alpha, Kinv, ld, partial);
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles * tiles, partial,
                      out_dev);
   TGP_HIP_TRY(hipGetLastError());
@@ -1014,8 +1114,12 @@ int launch_kgrad_cols(tgp_ctx* ctx, const KProg& kp, int which_op, int which_par
   TGP_TRY(ensure_work(ctx, size_t(tr) * tc * sizeof(double)));
   double* partial = static_cast<double*>(ctx->d_work);
   const size_t shmem = 2 * size_t(KT) * d * sizeof(T);
-  hipLaunchKernelGGL((kgrad_cols_kernel<T>), dim3((unsigned)tr, (unsigned)tc), dim3(256), shmem, ctx->stream, kp,
-                     which_op, which_param, n, d, X, alpha, Kc, R, c0, nb, G, rank, partial);
+  if (kfamily(kp) == 2)
+    hipLaunchKernelGGL((kgrad_cols_kernel<T, 2>), dim3((unsigned)tr, (unsigned)tc), dim3(256), shmem, ctx->stream,
+                       kp, which_op, which_param, n, d, X, alpha, Kc, R, c0, nb, G, rank, partial);
+  else
+    hipLaunchKernelGGL((kgrad_cols_kernel<T, 0>), dim3((unsigned)tr, (unsigned)tc), dim3(256), shmem, ctx->stream,
+                       kp, which_op, which_param, n, d, X, alpha, Kc, R, c0, nb, G, rank, partial);
   hipLaunchKernelGGL(add_partials_kernel, dim3(1), dim3(1024), 0, ctx->stream, tr * tc, partial, out_accum);
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;

@@ -1,9 +1,11 @@
 """Kernel building blocks (mirror of ``tinygp.kernels`` for the dense hot path).
 
-Kernels are built as sums and products of the stationary leaves below, exactly as in
-the reference; calling a kernel evaluates it on the MI355X through the HIP tile
-evaluator.  ``Custom``, ``DotProduct`` and ``Polynomial`` are arbitrary / non-stationary
-functions: their matrix is evaluated on the host and handed to the solver through the
+Kernels are built as sums and products of the stationary leaves below and of the
+dot-product kernels ``DotProduct`` / ``Polynomial``, exactly as in the reference; calling
+a kernel evaluates it on the MI355X through the HIP tile evaluator.  A bare
+``DotProduct`` / ``Polynomial`` called directly is one host GEMM; inside a tree, a
+transform or a solver it runs on the device.  ``Custom`` is an arbitrary Python function:
+its matrix is evaluated on the host and handed to the solver through the
 ``covariance=`` channel (the factorisation still runs on the device).  The ``quasisep``
 family is outside the hot path this package replaces.
 """

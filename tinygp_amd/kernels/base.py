@@ -4,7 +4,8 @@ Where the reference evaluates ``vmap(vmap(evaluate))`` through XLA (reference
 ``kernels/base.py:84-103``), a kernel here *compiles* to a small postfix
 "kernel program" (``tgp_kop`` array, ``include/tgp_hip.h``) that the HIP tile
 evaluator runs for every pair of points.  ``Sum`` / ``Product`` / ``Constant``
-(reference ``base.py:170-209``) are the ADD / MUL / CONST ops of that program.
+(reference ``base.py:170-209``) are the ADD / MUL / CONST ops of that program;
+``DotProduct`` / ``Polynomial`` (``base.py:212-256``) its DOT leaf and unary POW.
 """
 
 from __future__ import annotations
@@ -20,7 +21,18 @@ __all__ = ["Kernel", "Conditioned", "Custom", "Sum", "Product", "Constant", "Dot
 
 # op codes of include/tgp_hip.h
 K_CONST, K_EXP, K_EXPSQ, K_M32, K_M52, K_COS, K_ESS, K_RQ, K_ADD, K_MUL = 0, 1, 2, 3, 4, 5, 6, 7, 16, 17
+K_DOT, K_POW = 8, 18
 KPROG_MAX, KSTACK_MAX = 32, 8
+
+
+def _stack_peak(ops) -> int:
+    """Deepest evaluation stack of a postfix program: ADD / MUL pop two and push one, the
+    unary POW leaves the depth unchanged, every other op is a leaf."""
+    depth = peak = 0
+    for op, *_ in ops:
+        depth += -1 if op in (K_ADD, K_MUL) else 0 if op == K_POW else 1
+        peak = max(peak, depth)
+    return peak
 
 
 class Kernel:
@@ -45,10 +57,7 @@ class Kernel:
         self._emit(ops)
         if len(ops) > KPROG_MAX:
             raise _device.DeviceLimit(f"kernel expression too large for the device evaluator: {len(ops)} ops > {KPROG_MAX}")
-        depth = peak = 0
-        for op, *_ in ops:
-            depth += -1 if op in (K_ADD, K_MUL) else 1
-            peak = max(peak, depth)
+        peak = _stack_peak(ops)
         if peak > KSTACK_MAX:
             raise _device.DeviceLimit(f"kernel expression too deep for the device evaluator: stack {peak} > {KSTACK_MAX}")
         return ops
@@ -180,8 +189,8 @@ def _lower_binary(node, op, X):
     """Both operands must see the same device coordinates (one X per kernel matrix)."""
     p1, X1 = node.kernel1._lower(X)
     p2, X2 = node.kernel2._lower(X)
-    const1 = all(o[0] in (K_CONST, K_ADD, K_MUL) for o in p1)
-    const2 = all(o[0] in (K_CONST, K_ADD, K_MUL) for o in p2)
+    const1 = all(o[0] in (K_CONST, K_ADD, K_MUL, K_POW) for o in p1)
+    const2 = all(o[0] in (K_CONST, K_ADD, K_MUL, K_POW) for o in p2)
     if not (X1 is X2 or const1 or const2 or
             (np.shape(X1) == np.shape(X2) and np.array_equal(X1, X2))):
         raise NotImplementedError(
@@ -190,10 +199,7 @@ def _lower_binary(node, op, X):
     ops = p1 + p2 + [(op, 0, 0.0, 0.0)]
     if len(ops) > KPROG_MAX:
         raise _device.DeviceLimit(f"kernel expression too large for the device evaluator: {len(ops)} ops > {KPROG_MAX}")
-    depth = peak = 0
-    for o, *_ in ops:
-        depth += -1 if o in (K_ADD, K_MUL) else 1
-        peak = max(peak, depth)
+    peak = _stack_peak(ops)
     if peak > KSTACK_MAX:
         raise _device.DeviceLimit(f"kernel expression too deep for the device evaluator: stack {peak} > {KSTACK_MAX}")
     return ops, (X2 if const1 and not const2 else X1)
@@ -300,8 +306,33 @@ class Custom(Kernel):
         return self.function(X1, X2)
 
 
-class DotProduct(Kernel):
-    """``x_i . x_j`` (reference ``base.py:212-228``); host-evaluated (one GEMM)."""
+class _DotLeaf(Kernel):
+    """A dot-product leaf.  It lowers to a device program (the DOT op) wherever a program is
+    lowered -- the solvers, a tree with a device operand, an input transform -- but the bare
+    leaf called directly keeps the host formulas: ``DotProduct()(X1, X2)`` is one GEMM, and
+    needs no device."""
+
+    def __call__(self, X1, X2=None):
+        return self._host_diag(X1) if X2 is None else self._host_matrix(X1, X2)
+
+    def matmul(self, X1, X2=None, y=None):
+        if y is None:
+            assert X2 is not None
+            y = X2
+            X2 = None
+        if X2 is None:
+            X2 = X1
+        return np.dot(self._host_matrix(X1, X2), y)
+
+
+class DotProduct(_DotLeaf):
+    """``x_i . x_j`` (reference ``base.py:212-228``): the program ``[DOT(1, 0)]``."""
+
+    def _emit(self, ops):
+        ops.append((K_DOT, 0, 1.0, 0.0))
+
+    def _slots(self, out):
+        out.append([None, None])
 
     def evaluate(self, X1, X2):
         if np.ndim(X1) == 0:
@@ -317,11 +348,23 @@ class DotProduct(Kernel):
         return A * A if A.ndim == 1 else np.einsum("ij,ij->i", A, A)
 
 
-class Polynomial(Kernel):
-    """``[(x_i / l) . (x_j / l) + sigma^2]^P`` (reference ``base.py:231-256``); host-evaluated."""
+class Polynomial(_DotLeaf):
+    """``[(x_i / l) . (x_j / l) + sigma^2]^P`` (reference ``base.py:231-256``): the program
+    ``[DOT(scale, sigma), POW(order)]``; ``parameters()`` is scale, sigma, order."""
 
     def __init__(self, order, scale=1.0, sigma=0.0):
         self.order, self.scale, self.sigma = order, scale, sigma
+
+    def _emit(self, ops):
+        for name in ("order", "scale", "sigma"):
+            if np.ndim(getattr(self, name)) != 0:
+                raise ValueError(f"The {name} of a polynomial kernel must be a scalar")
+        ops.append((K_DOT, 0, float(self.scale), float(self.sigma)))
+        ops.append((K_POW, 0, float(self.order), 0.0))
+
+    def _slots(self, out):
+        out.append([(self, "scale"), (self, "sigma")])
+        out.append([(self, "order"), None])
 
     def evaluate(self, X1, X2):
         a, b = np.asarray(X1) / self.scale, np.asarray(X2) / self.scale

@@ -74,7 +74,7 @@ class DirectSolver(Solver):
         self._noise_diag = np.ascontiguousarray(noise_diag, dtype=dt)
 
         if covariance is None and (self._prog is None or not isinstance(noise, Diagonal)):
-            # noise.Dense, or a host-evaluated kernel (Custom / DotProduct / Conditioned ...):
+            # noise.Dense, or a host-evaluated kernel (Custom / Conditioned / D > 16 ...):
             # K + noise is formed on the host exactly like reference direct.py:50-52 and
             # shipped through the covariance channel; the factorisation runs on the device
             covariance = kernel(X, X) + noise
