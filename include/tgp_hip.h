@@ -576,6 +576,41 @@ int tgp_stream_sync(tgp_ctx* ctx, int which);
  * tests/test_host_logic.py checks that every order is a bijection onto the tiles. */
 int tgp_tile_order(int64_t tm, int64_t tn, int32_t lower, int32_t band, int64_t id, int32_t* ti, int32_t* tj, int64_t* n_tiles);
 
+/* ---- quasiseparable solver (kernels.quasisep / solvers.QuasisepSolver) --------------------------------------
+ * Sorted 1-D inputs t, a state-space kernel k(t_i, t_j) = h^T A(|t_i - t_j|) P h of state dimension J <= 8, diagonal
+ * noise.  The handle keeps t, the noise and the factor (c_n, w_n: n (1 + J) doubles) resident; A is regenerated on
+ * the device from t.  Host arrays are float64.  The model: `leaves` (nleaves x 5 doubles: kind TGP_QS_*, then 4
+ * parameters), `state_map` (J x nleaves int32: the index into leaf l's state of global state r, -1 where leaf l is
+ * not a factor of r's term), `hvec` (J), `Pinf` (J x J, row-major).  A non-positive pivot is reported in *info as
+ * its 1-based step (0: positive definite); the call still succeeds and the affected results are NaN. */
+#define TGP_QSEP_MAX_J 8
+#define TGP_QSEP_MAX_LEAVES 8
+#define TGP_QS_EXP 0      /* p0 = 1 / scale                     A = exp(-p0 dt) */
+#define TGP_QS_M32 1      /* p0 = sqrt(3) / scale */
+#define TGP_QS_M52 2      /* p0 = sqrt(5) / scale */
+#define TGP_QS_COS 3      /* p0 = 2 pi / scale */
+#define TGP_QS_CELERITE 4 /* p0 = c, p1 = d */
+#define TGP_QS_SHO_UNDER 5 /* p0 = omega, p1 = quality, p2 = sqrt(4 Q^2 - 1) */
+#define TGP_QS_SHO_CRIT 6  /* p0 = omega */
+#define TGP_QS_SHO_OVER 7  /* p0 = omega, p1 = quality, p2 = sqrt(1 - 4 Q^2) */
+#define TGP_QS_FWD 0 /* affine recurrences of the solves: L^-1 y */
+#define TGP_QS_BWD 1 /* L^-T y */
+#define TGP_QS_DOT 2 /* L z */
+typedef struct tgp_qsep tgp_qsep;
+int tgp_qsep_create(tgp_ctx* ctx, int64_t n, const double* t_host, tgp_qsep** out);
+int tgp_qsep_destroy(tgp_qsep* q);
+int tgp_qsep_factor(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t* state_map, int32_t J,
+                    const double* hvec, const double* Pinf, const double* noise_host, int32_t* info);
+/* factor, then -1/2 |L^-1 r|^2 - 1/2 sum log c_n - n/2 log(2 pi) in *out */
+int tgp_qsep_factor_logprob(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                            int32_t J, const double* hvec, const double* Pinf, const double* noise_host,
+                            const double* resid_host, int32_t* info, double* out);
+int tgp_qsep_normalization(tgp_qsep* q, double* out); /* 1/2 sum log c_n + n/2 log(2 pi) */
+/* y, out: n x nrhs row-major; transpose 0: L^-1 y, 1: L^-T y */
+int tgp_qsep_solve_tri(tgp_qsep* q, int transpose, int64_t nrhs, const double* y_host, double* out_host);
+int tgp_qsep_dot_tri(tgp_qsep* q, int64_t nrhs, const double* y_host, double* out_host); /* L y */
+int tgp_qsep_factor_data(tgp_qsep* q, double* c_host, double* w_host); /* c (n), w (n x J); either may be NULL */
+
 #ifdef __cplusplus
 }
 #endif

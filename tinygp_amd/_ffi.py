@@ -153,6 +153,14 @@ SIGNATURES = {
     "tgp_stream_d2d": [_vp, _int, _vp, _vp, _i64],
     "tgp_stream_memset": [_vp, _int, _vp, _int, _i64],
     "tgp_stream_sync": [_vp, _int],
+    "tgp_qsep_create": [_vp, _i64, _vp, _pvp],
+    "tgp_qsep_destroy": [_vp],
+    "tgp_qsep_factor": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _pi32],
+    "tgp_qsep_factor_logprob": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _pi32, _pdbl],
+    "tgp_qsep_normalization": [_vp, _pdbl],
+    "tgp_qsep_solve_tri": [_vp, _int, _i64, _vp, _vp],
+    "tgp_qsep_dot_tri": [_vp, _i64, _vp, _vp],
+    "tgp_qsep_factor_data": [_vp, _vp, _vp],
 }
 
 

@@ -1,0 +1,759 @@
+// qsep.hip -- quasiseparable (state-space) GP solver for sorted 1-D inputs, state dimension J <= 8.
+//
+// K + diag(noise) for a kernel k(t_i, t_j) = h^T A(|t_i - t_j|) P h has the lower Cholesky factor
+//   L[n,n] = sqrt(c_n),  L[i,j] = h^T A_i ... A_{j+1} w_j  (i > j)
+// with c_n, w_n from the Riccati (Kalman covariance) recursion over the filtered covariance P_n:
+//   P^-_n = A_n (P_{n-1} - P) A_n^T + P,  g = P^-_n h,  c_n = h^T g + noise_n,  w_n = g / sqrt(c_n),
+//   P_n = P^-_n - g g^T / c_n.
+// The factor is computed by a reduce-then-scan over chunks of steps:
+//   1. qs_fold     one wavefront per chunk folds its steps into one associative filtering element (A, C, J) of
+//                  the parallel Kalman filter (Sarkka & Garcia-Fernandez 2021, covariance part).  One scalar
+//                  observation per step: the step's J is rank one and the fold needs no inverse (Sherman-Morrison).
+//   2. qs_reduce / qs_down   hierarchical exclusive scan of the chunk elements, 64 per group; the full combine
+//                  (a J x J solve by Gauss-Jordan with partial pivoting) runs only here.  Going down, only the
+//                  filtered covariance is carried: P <- A (I + P J)^-1 P A^T + C.
+//   3. qs_emit     each chunk re-runs the sequential recursion from its incoming P, writing c_n, w_n and a
+//                  per-chunk sum of log c_n and its first non-positive pivot.
+// L^-1 y, L^-T y and L z are affine recurrences g <- M_n g + v_n over a J-vector per right-hand side (the M_n
+// shared by all columns); they run the same three phases with element (M, V) and combine M = M2 M1, V = M2 V1 + V2.
+// A_n is regenerated from dt_n = t_n - t_{n-1} (dt_0 = 0, A = I) in every kernel instead of being stored.
+//
+// Layout: one wavefront holds a J x J matrix (or a J x 8 block of right-hand sides) as one entry per lane,
+// lane = 8 r + c; entries outside J x J are zero.  Products read operands through __shfl.  Every reduction runs in
+// a fixed order, so results are bit-identical from run to run.  Arithmetic is fp64 throughout.
+#include "tgp_common.h"
+
+#include <climits>
+#include <cmath>
+
+namespace {
+
+constexpr int QJ = TGP_QSEP_MAX_J;          // 8
+constexpr int QL = TGP_QSEP_MAX_LEAVES;     // 8
+constexpr int WAVE = 64;
+constexpr int WPB = 4;                      // wavefronts per block
+constexpr int GROUP = 64;                   // scan fan-in per level
+constexpr double kLog2Pi = 1.8378770664093454836;
+
+struct QModel {
+  int32_t J, nleaves;
+  int32_t kind[QL];
+  int32_t map[QJ][QL];
+  double par[QL][4];
+  double h[QJ];
+  double P[QJ * QJ];  // padded 8 x 8
+};
+
+__device__ __forceinline__ double sh(double v, int lane) { return __shfl(v, lane, WAVE); }
+__device__ __forceinline__ double at(double v, int r, int c) { return sh(v, r * 8 + c); }
+
+// X Y, X^T Y, X Y^T for lane-layout matrices (uniform loops: every lane runs every __shfl)
+__device__ __forceinline__ double mm(double x, double y, int J, int r, int c) {
+  double s = 0.0;
+  for (int k = 0; k < J; ++k) s += at(x, r, k) * at(y, k, c);
+  return s;
+}
+__device__ __forceinline__ double mm_tn(double x, double y, int J, int r, int c) {
+  double s = 0.0;
+  for (int k = 0; k < J; ++k) s += at(x, k, r) * at(y, k, c);
+  return s;
+}
+__device__ __forceinline__ double mm_nt(double x, double y, int J, int r, int c) {
+  double s = 0.0;
+  for (int k = 0; k < J; ++k) s += at(x, r, k) * at(y, c, k);
+  return s;
+}
+__device__ __forceinline__ double symm(double x, int r, int c) { return 0.5 * (x + at(x, c, r)); }
+
+// entry (i, j) of one leaf's forward transition A(dt); selects, not arrays, so that nothing lives in scratch
+__device__ __forceinline__ double pick2(int i, int j, double a00, double a01, double a10, double a11) {
+  return i == 0 ? (j == 0 ? a00 : a01) : (j == 0 ? a10 : a11);
+}
+
+__device__ __forceinline__ double leaf_phi(int kind, const double* p, double dt, int i, int j) {
+  switch (kind) {
+    case TGP_QS_EXP:
+      return exp(-p[0] * dt);
+    case TGP_QS_M32: {
+      const double f = p[0], fd = f * dt;
+      return exp(-fd) * pick2(i, j, 1 + fd, dt, -f * fd, 1 - fd);
+    }
+    case TGP_QS_M52: {
+      const double f = p[0], f2 = f * f, fd = f * dt, d2 = dt * dt;
+      double v;
+      switch (i * 3 + j) {
+        case 0: v = 0.5 * f2 * d2 + fd + 1; break;
+        case 1: v = dt * (fd + 1); break;
+        case 2: v = 0.5 * d2; break;
+        case 3: v = -0.5 * f * f2 * d2; break;
+        case 4: v = -f2 * d2 + fd + 1; break;
+        case 5: v = 0.5 * dt * (2 - fd); break;
+        case 6: v = 0.5 * f2 * f * dt * (fd - 2); break;
+        case 7: v = f2 * dt * (fd - 3); break;
+        default: v = 0.5 * f2 * d2 - 2 * fd + 1; break;
+      }
+      return exp(-fd) * v;
+    }
+    case TGP_QS_COS:
+    case TGP_QS_CELERITE: {
+      const double decay = kind == TGP_QS_COS ? 1.0 : exp(-p[0] * dt);
+      const double a = (kind == TGP_QS_COS ? p[0] : p[1]) * dt;
+      const double co = cos(a), si = sin(a);
+      return decay * pick2(i, j, co, -si, si, co);
+    }
+    case TGP_QS_SHO_CRIT: {
+      const double w = p[0], wd = w * dt;
+      return exp(-wd) * pick2(i, j, 1 + wd, dt, -w * wd, 1 - wd);
+    }
+    default: {  // SHO under- / over-damped: p = (omega, quality, f)
+      const double w = p[0], q = p[1], f = p[2];
+      const double arg = 0.5 * f * w * dt / q;
+      const double s = kind == TGP_QS_SHO_UNDER ? sin(arg) : sinh(arg);
+      const double co = kind == TGP_QS_SHO_UNDER ? cos(arg) : cosh(arg);
+      return exp(-0.5 * w * dt / q) * pick2(i, j, co + s / f, 2 * q * s / (w * f), -2 * q * w * s / f, co - s / f);
+    }
+  }
+}
+
+// this lane's entry of the global transition: the product over the leaves of the term that r and c belong to
+__device__ __forceinline__ double phi_entry(const QModel& m, double dt, int r, int c) {
+  if (r >= m.J || c >= m.J) return 0.0;
+  double v = 1.0;
+  for (int l = 0; l < m.nleaves; ++l) {
+    const int a = m.map[r][l], b = m.map[c][l];
+    if ((a < 0) != (b < 0)) return 0.0;
+    if (a >= 0) v *= leaf_phi(m.kind[l], m.par[l], dt, a, b);
+  }
+  return v;
+}
+
+__device__ __forceinline__ double dt_at(const double* t, int64_t n) { return n == 0 ? 0.0 : t[n] - t[n - 1]; }
+
+// row-vector h^T X (one value per column c) and X h (one value per row r)
+__device__ __forceinline__ double hT(const QModel& m, double x, int c) {
+  double s = 0.0;
+  for (int k = 0; k < m.J; ++k) s += m.h[k] * at(x, k, c);
+  return s;
+}
+__device__ __forceinline__ double Xh(const QModel& m, double x, int r) {
+  double s = 0.0;
+  for (int k = 0; k < m.J; ++k) s += at(x, r, k) * m.h[k];
+  return s;
+}
+
+// Solve (G) [X1 | X2] = [X1 | X2] in place, Gauss-Jordan with partial pivoting over the leading J x J block.
+__device__ __forceinline__ void gj_solve(double& G, double& X1, double& X2, int J, int r, int c) {
+  for (int p = 0; p < J; ++p) {
+    int piv = p;
+    double best = fabs(at(G, p, p));
+    for (int i = p + 1; i < J; ++i) {
+      const double v = fabs(at(G, i, p));
+      if (v > best) { best = v; piv = i; }
+    }
+    const int src = (r == p ? piv : r == piv ? p : r) * 8 + c;
+    G = sh(G, src), X1 = sh(X1, src), X2 = sh(X2, src);
+    const double d = at(G, p, p);
+    const double g = at(G, p, c) / d, x1 = at(X1, p, c) / d, x2 = at(X2, p, c) / d;
+    const double f = at(G, r, p);
+    if (r == p) {
+      G = g, X1 = x1, X2 = x2;
+    } else {
+      G -= f * g, X1 -= f * x1, X2 -= f * x2;
+    }
+  }
+}
+
+struct Lane {
+  int lane, r, c;
+  int64_t wave;
+  __device__ Lane() {
+    lane = threadIdx.x & (WAVE - 1);
+    r = lane >> 3;
+    c = lane & 7;
+    wave = int64_t(blockIdx.x) * WPB + (threadIdx.x >> 6);
+  }
+};
+
+// ---- factor, phase 1: fold each chunk into one filtering element (A, C, J) ----------------------------------
+__global__ __launch_bounds__(WAVE * WPB) void qs_fold(const QModel* __restrict__ mp, const double* __restrict__ t,
+                                                      const double* __restrict__ noise, int64_t n, int64_t lc,
+                                                      int64_t nchunks, double* __restrict__ elem) {
+  const Lane L;
+  if (L.wave >= nchunks) return;
+  const QModel& m = *mp;
+  const int J = m.J, r = L.r, c = L.c;
+  const double P = m.P[L.lane];
+  double A = (r == c && r < J) ? 1.0 : 0.0, C = 0.0, Jm = 0.0;
+  const int64_t n0 = L.wave * lc, n1 = min(n, n0 + lc);
+  for (int64_t i = n0; i < n1; ++i) {
+    if (i == 0) {  // the first point absorbs the stationary prior: A = 0, C = filtered covariance, J = 0
+      const double Ph = Xh(m, P, r);
+      const double Ph_c = sh(Ph, c * 8);
+      double s = noise[0];
+      for (int k = 0; k < J; ++k) s += m.h[k] * sh(Ph, k * 8);
+      A = 0.0, Jm = 0.0;
+      C = (r < J && c < J) ? P - Ph * Ph_c / s : 0.0;
+      continue;
+    }
+    const double Phi = phi_entry(m, dt_at(t, i), r, c);
+    const double Q = P - mm_nt(mm(Phi, P, J, r, c), Phi, J, r, c);  // P - A P A^T
+    const double Qh = Xh(m, Q, r), Qh_c = sh(Qh, c * 8);
+    double s = noise[i];
+    for (int k = 0; k < J; ++k) s += m.h[k] * sh(Qh, k * 8);
+    const double v_c = hT(m, Phi, c), v_r = sh(v_c, r);  // v = A^T h
+    const double Aj = Phi - Qh * v_c / s;                // (I - K h^T) A,  K = Q h / s
+    const double Cj = Q - Qh * Qh_c / s;                 // (I - K h^T) Q
+    // fold (A, C, J) o (Aj, Cj, v v^T / s):  M = (I + C v v^T / s)^-1 = I - u v^T / beta
+    double u = 0.0;
+    for (int k = 0; k < J; ++k) u += at(C, r, k) * sh(v_r, k * 8);
+    double beta = s;
+    for (int k = 0; k < J; ++k) beta += sh(v_r, k * 8) * sh(u, k * 8);
+    const double u_c = sh(u, c * 8);
+    double a_c = 0.0;  // a = A^T v
+    for (int k = 0; k < J; ++k) a_c += at(A, k, c) * sh(v_r, k * 8);
+    const double a_r = sh(a_c, r);
+    const double T = A - u * a_c / beta;
+    const double U = C - u * u_c / beta;
+    A = mm(Aj, T, J, r, c);
+    C = symm(mm_nt(mm(Aj, U, J, r, c), Aj, J, r, c) + Cj, r, c);
+    Jm = symm(Jm + a_r * a_c / beta, r, c);
+  }
+  double* e = elem + L.wave * 3 * WAVE;
+  e[L.lane] = A, e[WAVE + L.lane] = C, e[2 * WAVE + L.lane] = Jm;
+}
+
+// ---- factor, phase 2: reduce groups of elements / carry the filtered covariance down --------------------------
+__device__ void ric_combine(double& A, double& C, double& Jm, double A2, double C2, double J2, int J, int r,
+                            int c) {
+  double G = mm(C, J2, J, r, c) + ((r == c && r < J) ? 1.0 : 0.0);
+  double XA = A, XC = C;
+  gj_solve(G, XA, XC, J, r, c);  // (I + C J2)^-1 [A | C]
+  const double An = mm(A2, XA, J, r, c);
+  const double Cn = symm(mm_nt(mm(A2, XC, J, r, c), A2, J, r, c) + C2, r, c);
+  const double Jn = symm(mm_tn(A, mm(J2, XA, J, r, c), J, r, c) + Jm, r, c);
+  A = An, C = Cn, Jm = Jn;
+}
+
+__global__ __launch_bounds__(WAVE * WPB) void qs_reduce(const QModel* __restrict__ mp, const double* __restrict__ in,
+                                                        int64_t count, double* __restrict__ out, int64_t ngroups) {
+  const Lane L;
+  if (L.wave >= ngroups) return;
+  const int J = mp->J;
+  const int64_t b = L.wave * GROUP, e = min(count, b + GROUP);
+  double A = in[b * 3 * WAVE + L.lane], C = in[b * 3 * WAVE + WAVE + L.lane], Jm = in[b * 3 * WAVE + 2 * WAVE + L.lane];
+  for (int64_t i = b + 1; i < e; ++i) {
+    const double* x = in + i * 3 * WAVE;
+    ric_combine(A, C, Jm, x[L.lane], x[WAVE + L.lane], x[2 * WAVE + L.lane], J, L.r, L.c);
+  }
+  double* o = out + L.wave * 3 * WAVE;
+  o[L.lane] = A, o[WAVE + L.lane] = C, o[2 * WAVE + L.lane] = Jm;
+}
+
+// prefix_in: one state per group (nullptr: the top level, start from P = 0); prefix_out: one per element
+__global__ __launch_bounds__(WAVE * WPB) void qs_down(const QModel* __restrict__ mp, const double* __restrict__ elem,
+                                                      int64_t count, const double* __restrict__ prefix_in,
+                                                      double* __restrict__ prefix_out, int64_t ngroups) {
+  const Lane L;
+  if (L.wave >= ngroups) return;
+  const int J = mp->J, r = L.r, c = L.c;
+  double P = prefix_in ? prefix_in[L.wave * WAVE + L.lane] : 0.0;
+  const int64_t b = L.wave * GROUP, e = min(count, b + GROUP);
+  for (int64_t i = b; i < e; ++i) {
+    prefix_out[i * WAVE + L.lane] = P;
+    const double* x = elem + i * 3 * WAVE;
+    const double A2 = x[L.lane], C2 = x[WAVE + L.lane], J2 = x[2 * WAVE + L.lane];
+    double G = mm(P, J2, J, r, c) + ((r == c && r < J) ? 1.0 : 0.0);
+    double X = P, dummy = 0.0;
+    gj_solve(G, X, dummy, J, r, c);  // (I + P J2)^-1 P
+    P = symm(mm_nt(mm(A2, X, J, r, c), A2, J, r, c) + C2, r, c);
+  }
+}
+
+// ---- factor, phase 3: the sequential recursion from each chunk's incoming filtered covariance ------------------
+__global__ __launch_bounds__(WAVE * WPB) void qs_emit(const QModel* __restrict__ mp, const double* __restrict__ t,
+                                                      const double* __restrict__ noise, int64_t n, int64_t lc,
+                                                      int64_t nchunks, const double* __restrict__ prefix,
+                                                      double* __restrict__ cbuf, double* __restrict__ wbuf,
+                                                      double* __restrict__ logsum, int64_t* __restrict__ bad) {
+  const Lane L;
+  if (L.wave >= nchunks) return;
+  const QModel& m = *mp;
+  const int J = m.J, r = L.r, c = L.c;
+  const double Pinf = m.P[L.lane];
+  double P = prefix[L.wave * WAVE + L.lane];
+  double acc = 0.0;
+  int64_t first_bad = INT64_MAX;
+  const int64_t n0 = L.wave * lc, n1 = min(n, n0 + lc);
+  for (int64_t i = n0; i < n1; ++i) {
+    double Pm = Pinf;
+    if (i > 0) {
+      const double Phi = phi_entry(m, dt_at(t, i), r, c);
+      Pm = symm(mm_nt(mm(Phi, P - Pinf, J, r, c), Phi, J, r, c) + Pinf, r, c);
+    }
+    const double g = Xh(m, Pm, r), g_c = sh(g, c * 8);
+    double cv = noise[i];
+    for (int k = 0; k < J; ++k) cv += m.h[k] * sh(g, k * 8);
+    if (!(cv > 0.0) && first_bad == INT64_MAX) first_bad = i;
+    const double sq = sqrt(cv);
+    if (L.lane == 0) cbuf[i] = cv;
+    if (c == 0 && r < J) wbuf[i * J + r] = g / sq;
+    acc += log(cv);
+    P = symm(Pm - g * g_c / cv, r, c);
+  }
+  if (L.lane == 0) logsum[L.wave] = acc, bad[L.wave] = first_bad;
+}
+
+// ---- affine recurrences: L^-1 y (FWD), L^-T y (BWD), L z (DOT) -------------------------------------------------
+// One step on a lane-layout block X (J rows; columns = right-hand sides, or the columns of M when y = 0).
+//   FWD: f = A X; e = y - h^T f; X' = f + (w / sqrt c) e          out z = e / sqrt c
+//   DOT: f = A X; X' = f + w y                                    out sqrt(c) y + h^T f
+//   BWD: x = (y - w^T X) / sqrt c; X' = A^T (X + h x)             out x
+struct StepData {
+  double Phi, w_r, sq, h_r;
+};
+
+__device__ __forceinline__ StepData step_data(const QModel& m, const double* t, const double* cbuf, const double* wbuf,
+                                     int64_t i, int r, int c) {
+  StepData d;
+  d.Phi = phi_entry(m, dt_at(t, i), r, c);
+  d.w_r = r < m.J ? wbuf[i * m.J + r] : 0.0;
+  d.sq = sqrt(cbuf[i]);
+  d.h_r = r < m.J ? m.h[r] : 0.0;
+  return d;
+}
+
+// returns X', writes the step's output value (meaningful in lanes of row 0) to *o
+__device__ __forceinline__ double step_apply(int op, const QModel& m, const StepData& d, double X, double y, double* o, int r,
+                                    int c) {
+  const int J = m.J;
+  if (op == TGP_QS_BWD) {
+    double wx = 0.0;
+    for (int k = 0; k < J; ++k) wx += sh(d.w_r, k * 8) * at(X, k, c);
+    const double x = (y - wx) / d.sq;
+    *o = x;
+    const double B = X + d.h_r * x;
+    return mm_tn(d.Phi, B, J, r, c);
+  }
+  const double f = mm(d.Phi, X, J, r, c);
+  const double hf = hT(m, f, c);
+  if (op == TGP_QS_FWD) {
+    const double z = (y - hf) / d.sq;
+    *o = z;
+    return f + d.w_r * z;
+  }
+  *o = d.sq * y + hf;
+  return f + d.w_r * y;
+}
+
+__device__ __forceinline__ int64_t step_index(int op, int64_t k, int64_t nchunks, int64_t lc, int64_t n, int64_t j,
+                                     int64_t* len) {
+  // scan position k -> chunk; BWD walks the chunks and their steps backwards
+  const int64_t chunk = op == TGP_QS_BWD ? nchunks - 1 - k : k;
+  const int64_t n0 = chunk * lc, n1 = min(n, n0 + lc);
+  *len = n1 - n0;
+  return op == TGP_QS_BWD ? n1 - 1 - j : n0 + j;
+}
+
+__global__ __launch_bounds__(WAVE * WPB) void qs_aff_fold(int op, const QModel* __restrict__ mp,
+                                                          const double* __restrict__ t, const double* __restrict__ cbuf,
+                                                          const double* __restrict__ wbuf, int64_t n, int64_t lc,
+                                                          int64_t nchunks, int64_t nrhs, int64_t ncg,
+                                                          const double* __restrict__ y, double* __restrict__ elem) {
+  const Lane L;
+  if (L.wave >= nchunks * ncg) return;
+  const QModel& m = *mp;
+  const int r = L.r, c = L.c;
+  const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
+  double M = (r == c && r < m.J) ? 1.0 : 0.0, V = 0.0, o;
+  int64_t len;
+  step_index(op, k, nchunks, lc, n, 0, &len);
+  for (int64_t j = 0; j < len; ++j) {
+    const int64_t i = step_index(op, k, nchunks, lc, n, j, &len);
+    const StepData d = step_data(m, t, cbuf, wbuf, i, r, c);
+    const double yv = col < nrhs ? y[i * nrhs + col] : 0.0;
+    M = step_apply(op, m, d, M, 0.0, &o, r, c);
+    V = step_apply(op, m, d, V, yv, &o, r, c);
+  }
+  double* e = elem + L.wave * 2 * WAVE;
+  e[L.lane] = M, e[WAVE + L.lane] = V;
+}
+
+__global__ __launch_bounds__(WAVE * WPB) void qs_aff_reduce(const QModel* __restrict__ mp,
+                                                            const double* __restrict__ in, int64_t count, int64_t ncg,
+                                                            double* __restrict__ out, int64_t ngroups) {
+  const Lane L;
+  if (L.wave >= ngroups * ncg) return;
+  const int J = mp->J;
+  const int64_t g = L.wave / ncg, cg = L.wave % ncg;
+  const int64_t b = g * GROUP, e = min(count, b + GROUP);
+  double M = in[(b * ncg + cg) * 2 * WAVE + L.lane], V = in[(b * ncg + cg) * 2 * WAVE + WAVE + L.lane];
+  for (int64_t i = b + 1; i < e; ++i) {
+    const double* x = in + (i * ncg + cg) * 2 * WAVE;
+    const double M2 = x[L.lane], V2 = x[WAVE + L.lane];
+    const double Mn = mm(M2, M, J, L.r, L.c);
+    V = mm(M2, V, J, L.r, L.c) + V2;
+    M = Mn;
+  }
+  double* o = out + L.wave * 2 * WAVE;
+  o[L.lane] = M, o[WAVE + L.lane] = V;
+}
+
+__global__ __launch_bounds__(WAVE * WPB) void qs_aff_down(const QModel* __restrict__ mp,
+                                                          const double* __restrict__ elem, int64_t count, int64_t ncg,
+                                                          const double* __restrict__ prefix_in,
+                                                          double* __restrict__ prefix_out, int64_t ngroups) {
+  const Lane L;
+  if (L.wave >= ngroups * ncg) return;
+  const int J = mp->J;
+  const int64_t g = L.wave / ncg, cg = L.wave % ncg;
+  double X = prefix_in ? prefix_in[L.wave * WAVE + L.lane] : 0.0;
+  const int64_t b = g * GROUP, e = min(count, b + GROUP);
+  for (int64_t i = b; i < e; ++i) {
+    prefix_out[(i * ncg + cg) * WAVE + L.lane] = X;
+    const double* x = elem + (i * ncg + cg) * 2 * WAVE;
+    X = mm(x[L.lane], X, J, L.r, L.c) + x[WAVE + L.lane];
+  }
+}
+
+__global__ __launch_bounds__(WAVE * WPB) void qs_aff_emit(int op, const QModel* __restrict__ mp,
+                                                          const double* __restrict__ t, const double* __restrict__ cbuf,
+                                                          const double* __restrict__ wbuf, int64_t n, int64_t lc,
+                                                          int64_t nchunks, int64_t nrhs, int64_t ncg,
+                                                          const double* __restrict__ prefix,
+                                                          const double* __restrict__ y, double* __restrict__ out,
+                                                          double* __restrict__ sumsq) {
+  const Lane L;
+  if (L.wave >= nchunks * ncg) return;
+  const QModel& m = *mp;
+  const int r = L.r, c = L.c;
+  const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
+  double X = prefix[L.wave * WAVE + L.lane], o = 0.0, acc = 0.0;
+  int64_t len;
+  step_index(op, k, nchunks, lc, n, 0, &len);
+  for (int64_t j = 0; j < len; ++j) {
+    const int64_t i = step_index(op, k, nchunks, lc, n, j, &len);
+    const StepData d = step_data(m, t, cbuf, wbuf, i, r, c);
+    const double yv = col < nrhs ? y[i * nrhs + col] : 0.0;
+    X = step_apply(op, m, d, X, yv, &o, r, c);
+    if (r == 0 && col < nrhs) {
+      out[i * nrhs + col] = o;
+      acc += o * o;
+    }
+  }
+  if (sumsq) {  // fixed-order sum over the 8 columns of row 0
+    double s = 0.0;
+    for (int q = 0; q < 8; ++q) s += sh(acc, q);
+    if (L.lane == 0) sumsq[L.wave] = s;
+  }
+}
+
+// one wavefront: fixed-order sums of a[0..n) and b[0..nb), minimum of bad[0..n)
+__global__ __launch_bounds__(WAVE) void qs_finish(const double* __restrict__ a, int64_t na,
+                                                  const double* __restrict__ b, int64_t nb,
+                                                  const int64_t* __restrict__ bad, double* __restrict__ out,
+                                                  int64_t* __restrict__ first_bad) {
+  const int lane = threadIdx.x;
+  double sa = 0.0, sb = 0.0;
+  int64_t mb = INT64_MAX;
+  for (int64_t i = lane; i < na; i += WAVE) sa += a[i];
+  for (int64_t i = lane; b && i < nb; i += WAVE) sb += b[i];
+  for (int64_t i = lane; bad && i < na; i += WAVE) mb = min(mb, bad[i]);
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    sa += __shfl_down(sa, off, WAVE);
+    sb += __shfl_down(sb, off, WAVE);
+    const int64_t o = __shfl_down(mb, off, WAVE);
+    mb = min(mb, o);
+  }
+  if (lane == 0) {
+    out[0] = sa, out[1] = sb;
+    if (first_bad) *first_bad = mb;
+  }
+}
+
+inline int64_t blocks_for(int64_t waves) { return (waves + WPB - 1) / WPB; }
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+}  // namespace
+
+struct tgp_qsep {
+  tgp_ctx* ctx = nullptr;
+  int64_t n = 0, lc = 0, nchunks = 0;
+  int32_t J = 0;
+  bool factored = false;
+  int32_t info = 0;
+  double logdet = 0.0;
+  QModel host_model{};
+  QModel* model = nullptr;
+  double *t = nullptr, *noise = nullptr, *c = nullptr, *w = nullptr;
+  double *io = nullptr, *io2 = nullptr;
+  int64_t io_elems = 0, io2_elems = 0;
+  double* work = nullptr;  // elements and prefixes of every scan level
+  int64_t work_elems = 0;
+  double* red = nullptr;   // per-chunk partial sums (2 x nchunks x ncg) + finish output
+  int64_t red_elems = 0;
+  int64_t* bad = nullptr;  // per-chunk first bad pivot + finish output
+};
+
+namespace {
+
+using tgp::set_error;
+
+int grow(double** p, int64_t* have, int64_t want) {
+  if (*have >= want) return TGP_OK;
+  if (*p) hipFree(*p);
+  *p = nullptr;
+  *have = 0;
+  TGP_HIP_TRY(hipMalloc(p, size_t(want) * sizeof(double)));
+  *have = want;
+  return TGP_OK;
+}
+
+// levels of the hierarchical scan over `count` elements: sizes[0] = count, sizes[l+1] = ceil(sizes[l] / GROUP)
+std::vector<int64_t> level_sizes(int64_t count) {
+  std::vector<int64_t> s{count};
+  while (s.back() > GROUP) s.push_back(ceil_div(s.back(), GROUP));
+  return s;
+}
+
+// Exclusive scan over the elements already in `elem0` (esz doubles each, `width` independent scans interleaved):
+// prefixes (WAVE doubles each) of level 0 land in the returned pointer.  Work layout: per level, elements then
+// prefixes.  `ric`: Riccati elements (width 1), else affine (M, V) elements.
+int run_scan(tgp_qsep* q, hipStream_t st, bool ric, int64_t count, int64_t width, double* elem0, double** prefix0) {
+  const int64_t esz = ric ? 3 * WAVE : 2 * WAVE;
+  const std::vector<int64_t> sz = level_sizes(count);
+  std::vector<double*> el(sz.size()), pre(sz.size());
+  el[0] = elem0;
+  double* cur = elem0 + count * width * esz;
+  for (size_t l = 0; l < sz.size(); ++l) {
+    if (l) {
+      el[l] = cur;
+      cur += sz[l] * width * esz;
+    }
+    pre[l] = cur;
+    cur += sz[l] * width * WAVE;
+  }
+  for (size_t l = 0; l + 1 < sz.size(); ++l) {
+    const int64_t g = sz[l + 1];
+    if (ric)
+      qs_reduce<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], el[l + 1], g);
+    else
+      qs_aff_reduce<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, el[l + 1], g);
+  }
+  for (size_t l = sz.size(); l-- > 0;) {
+    const int64_t g = l + 1 < sz.size() ? sz[l + 1] : 1;
+    const double* pin = l + 1 < sz.size() ? pre[l + 1] : nullptr;
+    if (ric)
+      qs_down<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], pin, pre[l], g);
+    else
+      qs_aff_down<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, pin, pre[l], g);
+  }
+  TGP_HIP_TRY(hipGetLastError());
+  *prefix0 = pre[0];
+  return TGP_OK;
+}
+
+int64_t scan_work(bool ric, int64_t count, int64_t width) {
+  const int64_t esz = ric ? 3 * WAVE : 2 * WAVE;
+  int64_t total = 0;
+  for (int64_t s : level_sizes(count)) total += s * width * (esz + WAVE);
+  return total;
+}
+
+int set_model(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t* state_map, int32_t J,
+              const double* hvec, const double* Pinf) {
+  TGP_ARG_CHECK(J >= 1 && J <= QJ, "quasiseparable state dimension must be 1..%d (got %d)", QJ, J);
+  TGP_ARG_CHECK(nleaves >= 1 && nleaves <= QL, "quasiseparable kernels hold 1..%d leaves (got %d)", QL, nleaves);
+  TGP_ARG_CHECK(leaves && state_map && hvec && Pinf, "null model array");
+  QModel m{};
+  m.J = J;
+  m.nleaves = nleaves;
+  for (int l = 0; l < nleaves; ++l) {
+    const int kind = int(leaves[l * 5]);
+    TGP_ARG_CHECK(kind >= TGP_QS_EXP && kind <= TGP_QS_SHO_OVER, "unknown quasiseparable leaf kind %d", kind);
+    m.kind[l] = kind;
+    for (int p = 0; p < 4; ++p) m.par[l][p] = leaves[l * 5 + 1 + p];
+  }
+  for (int r = 0; r < QJ; ++r)
+    for (int l = 0; l < QL; ++l) m.map[r][l] = (r < J && l < nleaves) ? state_map[r * nleaves + l] : -1;
+  for (int r = 0; r < J; ++r) {
+    m.h[r] = hvec[r];
+    for (int c = 0; c < J; ++c) m.P[r * QJ + c] = Pinf[r * J + c];
+  }
+  q->host_model = m;
+  q->J = J;
+  TGP_HIP_TRY(hipMemcpyAsync(q->model, &q->host_model, sizeof(QModel), hipMemcpyHostToDevice, q->ctx->stream));
+  return TGP_OK;
+}
+
+int factor(tgp_qsep* q, const double* noise_host) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks;
+  TGP_ARG_CHECK(noise_host != nullptr, "null noise array");
+  TGP_HIP_TRY(hipMemcpyAsync(q->noise, noise_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(true, nc, 1)));
+  qs_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, n, q->lc, nc, q->work);
+  double* prefix = nullptr;
+  TGP_TRY(run_scan(q, st, true, nc, 1, q->work, &prefix));
+  qs_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, n, q->lc, nc, prefix, q->c, q->w,
+                                                 q->red, q->bad);
+  qs_finish<<<1, WAVE, 0, st>>>(q->red, nc, nullptr, 0, q->bad, q->red + 2 * nc, q->bad + nc);
+  TGP_HIP_TRY(hipGetLastError());
+  double sums[2];
+  int64_t bad = 0;
+  TGP_HIP_TRY(hipMemcpyAsync(sums, q->red + 2 * nc, sizeof(sums), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipMemcpyAsync(&bad, q->bad + nc, sizeof(bad), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  q->logdet = sums[0];
+  q->info = bad == INT64_MAX ? 0 : int32_t(bad + 1);
+  q->factored = true;
+  return TGP_OK;
+}
+
+// out = op(y) for nrhs columns, y / out device buffers (N x nrhs, row-major); sumsq: optional sum of out^2
+int affine(tgp_qsep* q, int op, int64_t nrhs, const double* y, double* out, double* sumsq) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks, ncg = ceil_div(nrhs, 8);
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(false, nc, ncg)));
+  qs_aff_fold<<<blocks_for(nc * ncg), WAVE * WPB, 0, st>>>(op, q->model, q->t, q->c, q->w, n, q->lc, nc, nrhs, ncg,
+                                                            y, q->work);
+  double* prefix = nullptr;
+  TGP_TRY(run_scan(q, st, false, nc, ncg, q->work, &prefix));
+  qs_aff_emit<<<blocks_for(nc * ncg), WAVE * WPB, 0, st>>>(op, q->model, q->t, q->c, q->w, n, q->lc, nc, nrhs, ncg,
+                                                            prefix, y, out, sumsq ? q->red : nullptr);
+  if (sumsq) {
+    qs_finish<<<1, WAVE, 0, st>>>(q->red, nc * ncg, nullptr, 0, nullptr, q->red + 2 * nc * ncg, nullptr);
+    TGP_HIP_TRY(hipMemcpyAsync(sumsq, q->red + 2 * nc * ncg, sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
+int host_affine(tgp_qsep* q, int op, int64_t nrhs, const void* y_host, void* out_host, double* sumsq) {
+  TGP_ARG_CHECK(nrhs >= 1, "need at least one right-hand side (got %lld)", (long long)nrhs);
+  TGP_ARG_CHECK(y_host && out_host, "null array");
+  TGP_ARG_CHECK(q->factored, "the quasiseparable factor has not been computed (call tgp_qsep_factor first)");
+  hipStream_t st = q->ctx->stream;
+  const int64_t elems = q->n * nrhs;
+  TGP_TRY(grow(&q->io, &q->io_elems, elems));
+  TGP_TRY(grow(&q->io2, &q->io2_elems, elems));
+  const int64_t nc_all = q->nchunks * ceil_div(nrhs, 8);
+  TGP_TRY(grow(&q->red, &q->red_elems, 2 * nc_all + 2));
+  TGP_HIP_TRY(hipMemcpyAsync(q->io, y_host, size_t(elems) * sizeof(double), hipMemcpyHostToDevice, st));
+  TGP_TRY(affine(q, op, nrhs, q->io, q->io2, sumsq));
+  TGP_HIP_TRY(hipMemcpyAsync(out_host, q->io2, size_t(elems) * sizeof(double), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  return TGP_OK;
+}
+
+#define QS_GUARD(q)                                                                   \
+  TGP_ARG_CHECK((q) != nullptr && (q)->ctx != nullptr, "null quasiseparable handle"); \
+  std::unique_lock<std::recursive_mutex> _tgp_lock((q)->ctx->mu);                     \
+  TGP_HIP_TRY(hipSetDevice((q)->ctx->device))
+
+}  // namespace
+
+extern "C" {
+
+int tgp_qsep_create(tgp_ctx* ctx, int64_t n, const double* t_host, tgp_qsep** out) {
+  TGP_ARG_CHECK(ctx != nullptr, "null context");
+  std::unique_lock<std::recursive_mutex> lock(ctx->mu);
+  TGP_HIP_TRY(hipSetDevice(ctx->device));
+  TGP_ARG_CHECK(out != nullptr && t_host != nullptr, "null argument");
+  TGP_ARG_CHECK(n >= 1, "need at least one data point (n = %lld)", (long long)n);
+  tgp_qsep* q = new tgp_qsep();
+  q->ctx = ctx;
+  q->n = n;
+  // chunk length: about 4096 chunks, 16..256 steps each (a function of n only: results do not depend on the device)
+  int64_t lc = 16;
+  while (lc < 256 && lc * 4096 < n) lc *= 2;
+  q->lc = lc;
+  q->nchunks = ceil_div(n, lc);
+  auto fail = [&](int code) { tgp_qsep_destroy(q); return code; };
+#define Q_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) {                \
+    set_error("%s failed: %s", #expr, hipGetErrorString(_e));                          \
+    return fail(_e == hipErrorOutOfMemory ? TGP_E_NOMEM : TGP_E_HIP); } } while (0)
+  Q_TRY(hipMalloc(&q->model, sizeof(QModel)));
+  Q_TRY(hipMalloc(&q->t, size_t(n) * sizeof(double)));
+  Q_TRY(hipMalloc(&q->noise, size_t(n) * sizeof(double)));
+  Q_TRY(hipMalloc(&q->c, size_t(n) * sizeof(double)));
+  Q_TRY(hipMalloc(&q->w, size_t(n) * QJ * sizeof(double)));
+  Q_TRY(hipMalloc(&q->bad, size_t(q->nchunks + 1) * sizeof(int64_t)));
+  Q_TRY(hipMemcpyAsync(q->t, t_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  Q_TRY(hipStreamSynchronize(ctx->stream));
+#undef Q_TRY
+  if (int s = grow(&q->red, &q->red_elems, 2 * q->nchunks + 2); s < 0) return fail(s);
+  *out = q;
+  return TGP_OK;
+}
+
+int tgp_qsep_destroy(tgp_qsep* q) {
+  if (!q) return TGP_OK;
+  if (q->ctx) {
+    hipSetDevice(q->ctx->device);
+    hipStreamSynchronize(q->ctx->stream);
+  }
+  void* bufs[] = {q->model, q->t, q->noise, q->c, q->w, q->io, q->io2, q->work, q->red, q->bad};
+  for (void* b : bufs)
+    if (b) hipFree(b);
+  delete q;
+  return TGP_OK;
+}
+
+int tgp_qsep_factor(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t* state_map, int32_t J,
+                    const double* hvec, const double* Pinf, const double* noise_host, int32_t* info) {
+  QS_GUARD(q);
+  TGP_TRY(set_model(q, leaves, nleaves, state_map, J, hvec, Pinf));
+  TGP_TRY(factor(q, noise_host));
+  if (info) *info = q->info;
+  return TGP_OK;
+}
+
+int tgp_qsep_factor_logprob(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                            int32_t J, const double* hvec, const double* Pinf, const double* noise_host,
+                            const double* resid_host, int32_t* info, double* out) {
+  QS_GUARD(q);
+  TGP_ARG_CHECK(resid_host && out, "null argument");
+  TGP_TRY(set_model(q, leaves, nleaves, state_map, J, hvec, Pinf));
+  TGP_TRY(factor(q, noise_host));
+  if (info) *info = q->info;
+  TGP_TRY(grow(&q->io, &q->io_elems, q->n));
+  TGP_TRY(grow(&q->io2, &q->io2_elems, q->n));
+  hipStream_t st = q->ctx->stream;
+  double zz = 0.0;
+  TGP_HIP_TRY(hipMemcpyAsync(q->io, resid_host, size_t(q->n) * sizeof(double), hipMemcpyHostToDevice, st));
+  TGP_TRY(affine(q, TGP_QS_FWD, 1, q->io, q->io2, &zz));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  *out = -0.5 * zz - 0.5 * q->logdet - 0.5 * double(q->n) * kLog2Pi;
+  return TGP_OK;
+}
+
+int tgp_qsep_normalization(tgp_qsep* q, double* out) {
+  QS_GUARD(q);
+  TGP_ARG_CHECK(out != nullptr, "null argument");
+  TGP_ARG_CHECK(q->factored, "the quasiseparable factor has not been computed (call tgp_qsep_factor first)");
+  *out = 0.5 * q->logdet + 0.5 * double(q->n) * kLog2Pi;
+  return TGP_OK;
+}
+
+int tgp_qsep_solve_tri(tgp_qsep* q, int transpose, int64_t nrhs, const double* y_host, double* out_host) {
+  QS_GUARD(q);
+  return host_affine(q, transpose ? TGP_QS_BWD : TGP_QS_FWD, nrhs, y_host, out_host, nullptr);
+}
+
+int tgp_qsep_dot_tri(tgp_qsep* q, int64_t nrhs, const double* y_host, double* out_host) {
+  QS_GUARD(q);
+  return host_affine(q, TGP_QS_DOT, nrhs, y_host, out_host, nullptr);
+}
+
+int tgp_qsep_factor_data(tgp_qsep* q, double* c_host, double* w_host) {
+  QS_GUARD(q);
+  TGP_ARG_CHECK(q->factored, "the quasiseparable factor has not been computed (call tgp_qsep_factor first)");
+  hipStream_t st = q->ctx->stream;
+  if (c_host) TGP_HIP_TRY(hipMemcpyAsync(c_host, q->c, size_t(q->n) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (w_host)
+    TGP_HIP_TRY(hipMemcpyAsync(w_host, q->w, size_t(q->n) * q->J * sizeof(double), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  return TGP_OK;
+}
+
+}  // extern "C"

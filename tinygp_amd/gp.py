@@ -24,7 +24,7 @@ import numpy as np
 
 from tinygp_amd import _device, kernels, means
 from tinygp_amd.noise import Diagonal, Noise
-from tinygp_amd.solvers import DirectSolver
+from tinygp_amd.solvers import DirectSolver, QuasisepSolver
 
 __all__ = ["GaussianProcess", "ConditionResult"]
 
@@ -44,7 +44,8 @@ class GaussianProcess:
             ``sqrt(eps)`` like the reference.
         noise: a :mod:`tinygp_amd.noise` model (overrides ``diag``).
         mean: a scalar, a callable of one coordinate, or a :class:`means.MeanBase`.
-        solver: the solver class, default :class:`solvers.DirectSolver`.
+        solver: the solver class, default :class:`solvers.QuasisepSolver` for a
+            ``kernels.quasisep.Quasisep`` kernel and :class:`solvers.DirectSolver` otherwise.
         mean_value / covariance_value: pre-computed mean vector / covariance matrix.
         **solver_kwargs: forwarded to the solver constructor (e.g. ``ctx=``).
     """
@@ -86,7 +87,9 @@ class GaussianProcess:
                                                   self.mean.shape))
         self.noise = noise
 
-        self._solver_cls = DirectSolver if solver is None else solver
+        if solver is None:  # reference gp.py:101-105
+            solver = QuasisepSolver if isinstance(kernel, kernels.quasisep.Quasisep) else DirectSolver
+        self._solver_cls = solver
         self._solver_args = (covariance_value, solver_kwargs)
         self._solver = None
         if not _lazy:

@@ -7,13 +7,15 @@ a kernel evaluates it on the MI355X through the HIP tile evaluator.  A bare
 transform or a solver it runs on the device.  ``Custom`` is an arbitrary Python function:
 its matrix is evaluated on the host and handed to the solver through the
 ``covariance=`` channel (the factorisation still runs on the device).  The ``quasisep``
-family is outside the hot path this package replaces.
+submodule holds the state-space kernels of 1-D series (``Exp``, ``Matern32``, ``Matern52``,
+``Cosine``, ``Celerite``, ``SHO`` and their sums, products and scalings) that
+``solvers.QuasisepSolver`` factors in O(N J^2) on the device.
 """
 
 __all__ = [
     "Distance", "L1Distance", "L2Distance", "Kernel", "Conditioned", "Custom", "Sum",
     "Product", "Constant", "DotProduct", "Polynomial", "Stationary", "Exp", "ExpSquared", "Matern32", "Matern52", "Cosine",
-    "ExpSineSquared", "RationalQuadratic",
+    "ExpSineSquared", "RationalQuadratic", "quasisep",
 ]
 
 from tinygp_amd.kernels.base import (
@@ -37,3 +39,5 @@ from tinygp_amd.kernels.stationary import (
     RationalQuadratic,
     Stationary,
 )
+
+from tinygp_amd.kernels import quasisep  # noqa: E402

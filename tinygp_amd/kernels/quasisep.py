@@ -1,0 +1,488 @@
+"""Quasiseparable (state-space) kernels for 1-D inputs (mirror of ``tinygp.kernels.quasisep``).
+
+Every kernel here is the covariance of a linear stationary SDE observed through a design vector:
+
+    k(t_i, t_j) = h^T A(|t_i - t_j|) P h,      A(dt) = expm(F dt),
+
+with state dimension ``J = len(h)``, stationary covariance ``P`` (``stationary_covariance()``) and the
+closed-form forward transition ``A``.  (The reference's ``transition_matrix(X1, X2)`` returns ``A^T``; the method
+of the same name here keeps that convention, ``_phi`` returns ``A`` itself.)  Used with
+:class:`tinygp_amd.solvers.QuasisepSolver` the likelihood, solves and samples cost O(N J^2) on the device.
+
+Algebra: a :class:`Sum` is block-diagonal, a :class:`Product` is the Kronecker product of ``A``, ``P`` and ``h``
+(``np.kron`` order: the second operand's index runs fastest), a :class:`Scale` multiplies ``P``.  Mixed with a dense
+kernel the result is the ordinary :class:`tinygp_amd.kernels.Sum` / ``Product``.
+
+Called directly (``k(X1, X2)``, ``matmul``) a quasiseparable kernel is evaluated on the host from the formula above,
+in blocks of rows.  For the dense solvers, ``Exp``, ``Matern32``, ``Matern52`` and ``Cosine`` (sigma^2 times the
+stationary leaves of the same name) and their sums / products lower to the device kernel program; ``Celerite`` and
+``SHO`` have no program and reach :class:`~tinygp_amd.solvers.DirectSolver` through ``covariance=``.
+
+:meth:`Quasisep._lower_ssm` is the compact description the device recursions read (``include/tgp_hip.h``,
+``tgp_qsep_*``): a leaf table, a state map, ``h`` and ``P``.  The device holds ``J <= 8``.
+"""
+
+from __future__ import annotations
+
+from typing import Any, NamedTuple
+
+import numpy as np
+
+from tinygp_amd import _device
+from tinygp_amd.kernels import base
+from tinygp_amd.kernels.distance import L1Distance
+
+__all__ = ["Quasisep", "Sum", "Product", "Scale", "Celerite", "SHO", "Exp", "Matern32", "Matern52", "Cosine",
+           "MAX_STATE", "MAX_LEAVES"]
+
+MAX_STATE = 8   # TGP_QSEP_MAX_J of include/tgp_hip.h
+MAX_LEAVES = 8  # TGP_QSEP_MAX_LEAVES
+
+# leaf kinds of include/tgp_hip.h (TGP_QS_*)
+QS_EXP, QS_M32, QS_M52, QS_COS, QS_CELERITE, QS_SHO_UNDER, QS_SHO_CRIT, QS_SHO_OVER = range(8)
+
+
+class SSM(NamedTuple):
+    """What the device reads.  ``leaves``: (L, 5) float64 rows ``(kind, p0, p1, p2, p3)``; ``state_map``: (J, L)
+    int32, the index into leaf ``l``'s own state of global state ``r``, or -1 when leaf ``l`` is not a factor of
+    the term ``r`` belongs to; ``h``: (J,); ``Pinf``: (J, J)."""
+
+    leaves: np.ndarray
+    state_map: np.ndarray
+    h: np.ndarray
+    Pinf: np.ndarray
+
+    @property
+    def J(self) -> int:
+        return len(self.h)
+
+
+def _coords(X) -> np.ndarray:
+    if _device.is_tree(X):
+        raise NotImplementedError("quasiseparable kernels take 1-D coordinates, not pytrees")
+    X = np.asarray(X)
+    if X.ndim == 2 and X.shape[1] == 1:
+        X = X[:, 0]
+    if X.ndim != 1:
+        raise ValueError(f"quasiseparable kernels take coordinates of shape (N,) or (N, 1); got {X.shape}")
+    return X
+
+
+class Quasisep(base.Kernel):
+    """Base class of the quasiseparable kernels (reference ``kernels/quasisep.py:50-215``)."""
+
+    # -- state-space description --------------------------------------------------
+    def _ssm(self) -> SSM:
+        raise NotImplementedError
+
+    def _phi(self, dt) -> np.ndarray:
+        """A(dt) for an array of lags: shape ``dt.shape + (J, J)``."""
+        raise NotImplementedError
+
+    def stationary_covariance(self) -> np.ndarray:
+        return self._ssm().Pinf
+
+    def observation_model(self, X=None) -> np.ndarray:
+        del X
+        return self._ssm().h
+
+    def transition_matrix(self, X1, X2) -> np.ndarray:
+        """The reference's convention: ``A(X2 - X1)^T``."""
+        return np.swapaxes(self._phi(np.asarray(X2, dtype=np.float64) - np.asarray(X1, dtype=np.float64)), -1, -2)
+
+    def coord_to_sortable(self, X):
+        return X
+
+    def _lower_ssm(self) -> SSM:
+        """The device description; raises :class:`tinygp_amd._device.DeviceLimit` beyond J = 8 or 8 leaves."""
+        s = self._ssm()
+        if s.J > MAX_STATE:
+            raise _device.DeviceLimit(
+                f"the quasiseparable device path holds state dimension J <= {MAX_STATE}; this kernel has J = {s.J}")
+        if len(s.leaves) > MAX_LEAVES:
+            raise _device.DeviceLimit(
+                f"the quasiseparable device path holds at most {MAX_LEAVES} leaf kernels; this one has "
+                f"{len(s.leaves)}")
+        if not (np.all(np.isfinite(s.leaves)) and np.all(np.isfinite(s.h)) and np.all(np.isfinite(s.Pinf))):
+            raise ValueError("non-finite quasiseparable kernel parameters")
+        return s
+
+    # -- dense value on the host ---------------------------------------------------
+    def _k_of_lag(self, tau) -> np.ndarray:
+        """k as a function of the lag ``tau >= 0`` (any shape)."""
+        s = self._ssm()
+        Ph = s.Pinf @ s.h
+        return np.einsum("...ij,i,j->...", self._phi(tau), s.h, Ph)
+
+    def _host_matrix(self, X1, X2):
+        a, b = _coords(X1), _coords(X2)
+        dt = _device.common_dtype(a, b)
+        a64, b64 = a.astype(np.float64), b.astype(np.float64)
+        out = np.empty((a.shape[0], b.shape[0]), dtype=dt)
+        step = max(1, (1 << 20) // max(1, b.shape[0] * self._ssm().J ** 2))
+        for i0 in range(0, a.shape[0], step):
+            out[i0:i0 + step] = self._k_of_lag(np.abs(a64[i0:i0 + step, None] - b64[None, :]))
+        return out
+
+    def _host_diag(self, X):
+        a = _coords(X)
+        s = self._ssm()
+        return np.full(a.shape, s.h @ s.Pinf @ s.h, dtype=_device.common_dtype(a))
+
+    def __call__(self, X1, X2=None):
+        return self._host_diag(X1) if X2 is None else self._host_matrix(X1, X2)
+
+    def evaluate(self, X1, X2):
+        return self._host_matrix(np.reshape(X1, (1,)), np.reshape(X2, (1,)))[0, 0]
+
+    def evaluate_diag(self, X):
+        return self._host_diag(np.reshape(X, (1,)))[0]
+
+    def matmul(self, X1, X2=None, y=None):
+        """``k(X1, X2) @ y`` on the host, a bounded slab of rows of ``X1`` at a time."""
+        if y is None:
+            assert X2 is not None
+            y = X2
+            X2 = None
+        if X2 is None:
+            X2 = X1
+        a, b = _coords(X1), _coords(X2)
+        y = np.asarray(y)
+        if y.shape[0] != b.shape[0]:
+            raise ValueError("dimension mismatch between X2 and y in Kernel.matmul")
+        rows = max(1, (1 << 22) // max(1, b.shape[0]))
+        parts = [self._host_matrix(a[i0:i0 + rows], b) @ y for i0 in range(0, a.shape[0], rows)]
+        if not parts:
+            return np.zeros((0,) + y.shape[1:], dtype=np.result_type(y, _device.common_dtype(b)))
+        return np.concatenate(parts, axis=0)
+
+    # -- dense device program (Exp / Matern / Cosine trees only) --------------------
+    def _lower(self, X):
+        prog = self.program()
+        return prog, _coords(X)
+
+    # -- algebra (reference quasisep.py:164-199) ------------------------------------
+    def __add__(self, other: Any):
+        if isinstance(other, Quasisep):
+            return Sum(self, other)
+        return super().__add__(other)
+
+    def __radd__(self, other: Any):
+        if isinstance(other, Quasisep):
+            return Sum(other, self)
+        return super().__radd__(other)
+
+    def __mul__(self, other: Any):
+        if isinstance(other, Quasisep):
+            return Product(self, other)
+        if isinstance(other, base.Kernel) or np.ndim(other) != 0:
+            return super().__mul__(other)
+        return Scale(kernel=self, scale=other)
+
+    def __rmul__(self, other: Any):
+        if isinstance(other, Quasisep):
+            return Product(other, self)
+        if isinstance(other, base.Kernel) or np.ndim(other) != 0:
+            return super().__rmul__(other)
+        return Scale(kernel=self, scale=other)
+
+
+def _leaf_ssm(kind, params, h, P) -> SSM:
+    p = np.zeros(4)
+    p[:len(params)] = params
+    J = len(h)
+    return SSM(np.array([[kind, *p]], dtype=np.float64), np.arange(J, dtype=np.int32)[:, None],
+               np.asarray(h, dtype=np.float64), np.asarray(P, dtype=np.float64))
+
+
+def _block_diag(a, b):
+    out = np.zeros((a.shape[0] + b.shape[0], a.shape[1] + b.shape[1]), dtype=np.result_type(a, b))
+    out[:a.shape[0], :a.shape[1]] = a
+    out[a.shape[0]:, a.shape[1]:] = b
+    return out
+
+
+class Sum(Quasisep):
+    """k1 + k2: block-diagonal state (reference ``quasisep.py:241-295``)."""
+
+    def __init__(self, kernel1: Quasisep, kernel2: Quasisep, use_block: bool = True):
+        self.kernel1, self.kernel2, self.use_block = kernel1, kernel2, use_block
+
+    def _ssm(self):
+        s1, s2 = self.kernel1._ssm(), self.kernel2._ssm()
+        m = np.full((s1.J + s2.J, len(s1.leaves) + len(s2.leaves)), -1, dtype=np.int32)
+        m[:s1.J, :len(s1.leaves)] = s1.state_map
+        m[s1.J:, len(s1.leaves):] = s2.state_map
+        return SSM(np.concatenate([s1.leaves, s2.leaves]), m, np.concatenate([s1.h, s2.h]),
+                   _block_diag(s1.Pinf, s2.Pinf))
+
+    def _phi(self, dt):
+        a1, a2 = self.kernel1._phi(dt), self.kernel2._phi(dt)
+        j1, j2 = a1.shape[-1], a2.shape[-1]
+        out = np.zeros(np.shape(dt) + (j1 + j2, j1 + j2))
+        out[..., :j1, :j1] = a1
+        out[..., j1:, j1:] = a2
+        return out
+
+    def _k_of_lag(self, tau):
+        return self.kernel1._k_of_lag(tau) + self.kernel2._k_of_lag(tau)
+
+    def _emit(self, ops):
+        self.kernel1._emit(ops)
+        self.kernel2._emit(ops)
+        ops.append((base.K_ADD, 0, 0.0, 0.0))
+
+    def __repr__(self):
+        return f"quasisep.Sum({self.kernel1!r}, {self.kernel2!r})"
+
+
+class Product(Quasisep):
+    """k1 * k2: Kronecker-product state (reference ``quasisep.py:298-331``)."""
+
+    def __init__(self, kernel1: Quasisep, kernel2: Quasisep):
+        self.kernel1, self.kernel2 = kernel1, kernel2
+
+    def _ssm(self):
+        s1, s2 = self.kernel1._ssm(), self.kernel2._ssm()
+        m = np.concatenate([np.repeat(s1.state_map, s2.J, axis=0), np.tile(s2.state_map, (s1.J, 1))], axis=1)
+        return SSM(np.concatenate([s1.leaves, s2.leaves]), m.astype(np.int32), np.kron(s1.h, s2.h),
+                   np.kron(s1.Pinf, s2.Pinf))
+
+    def _phi(self, dt):
+        a1, a2 = self.kernel1._phi(dt), self.kernel2._phi(dt)
+        j1, j2 = a1.shape[-1], a2.shape[-1]
+        return np.einsum("...ik,...jl->...ijkl", a1, a2).reshape(np.shape(dt) + (j1 * j2, j1 * j2))
+
+    def _k_of_lag(self, tau):
+        return self.kernel1._k_of_lag(tau) * self.kernel2._k_of_lag(tau)
+
+    def _emit(self, ops):
+        self.kernel1._emit(ops)
+        self.kernel2._emit(ops)
+        ops.append((base.K_MUL, 0, 0.0, 0.0))
+
+    def __repr__(self):
+        return f"quasisep.Product({self.kernel1!r}, {self.kernel2!r})"
+
+
+class Scale(Quasisep):
+    """``scale * kernel`` (reference ``quasisep.py:334-340``): multiplies the stationary covariance."""
+
+    def __init__(self, kernel: Quasisep, scale):
+        self.kernel, self.scale = kernel, scale
+
+    def _ssm(self):
+        s = self.kernel._ssm()
+        return SSM(s.leaves, s.state_map, s.h, float(self.scale) * s.Pinf)
+
+    def _phi(self, dt):
+        return self.kernel._phi(dt)
+
+    def _k_of_lag(self, tau):
+        return float(self.scale) * self.kernel._k_of_lag(tau)
+
+    def _emit(self, ops):
+        if np.ndim(self.scale) != 0:
+            raise ValueError("Quasisep kernels can only be multiplied by scalars and other Quasisep kernels")
+        self.kernel._emit(ops)
+        ops.append((base.K_CONST, 0, float(self.scale), 0.0))
+        ops.append((base.K_MUL, 0, 0.0, 0.0))
+
+    def __repr__(self):
+        return f"quasisep.Scale({self.kernel!r}, scale={self.scale!r})"
+
+
+def _damped(decay, m):
+    """``exp(-decay) * m`` with m (..., J, J) built from a list of rows of arrays."""
+    return np.exp(-decay)[..., None, None] * np.moveaxis(np.asarray(m, dtype=np.float64), (0, 1), (-2, -1))
+
+
+class _Leaf(Quasisep):
+    _stationary: type | None = None  # the dense leaf this kernel equals sigma^2 times, if any
+
+    def _emit(self, ops):
+        if self._stationary is None:
+            raise NotImplementedError(
+                f"quasisep.{type(self).__name__} has no dense device program: use QuasisepSolver, or pass its matrix "
+                "through covariance=")
+        for name in ("scale", "sigma"):
+            if np.ndim(getattr(self, name)) != 0:
+                raise ValueError(f"the {name} of a quasiseparable kernel must be a scalar")
+        ops.append((self._stationary._op, L1Distance.metric_code, float(self.scale), 0.0))
+        ops.append((base.K_CONST, 0, float(self.sigma) ** 2, 0.0))
+        ops.append((base.K_MUL, 0, 0.0, 0.0))
+
+    def __repr__(self):
+        args = ", ".join(f"{k}={v!r}" for k, v in vars(self).items())
+        return f"quasisep.{type(self).__name__}({args})"
+
+
+class Exp(_Leaf):
+    """sigma^2 exp(-tau / scale) (reference ``quasisep.py:491-525``); J = 1."""
+
+    def __init__(self, scale, sigma=1.0):
+        self.scale, self.sigma = scale, sigma
+
+    @property
+    def _stationary(self):
+        from tinygp_amd.kernels.stationary import Exp as E
+        return E
+
+    def design_matrix(self):
+        return np.array([[-1.0 / self.scale]])
+
+    def _ssm(self):
+        return _leaf_ssm(QS_EXP, [1.0 / float(self.scale)], [float(self.sigma)], [[1.0]])
+
+    def _phi(self, dt):
+        return np.exp(-np.asarray(dt, dtype=np.float64) / float(self.scale))[..., None, None]
+
+
+class Matern32(_Leaf):
+    """sigma^2 (1 + f tau) exp(-f tau), f = sqrt(3)/scale (reference ``quasisep.py:528-569``); J = 2."""
+
+    def __init__(self, scale, sigma=1.0):
+        self.scale, self.sigma = scale, sigma
+
+    @property
+    def _stationary(self):
+        from tinygp_amd.kernels.stationary import Matern32 as M
+        return M
+
+    def noise(self):
+        f = np.sqrt(3) / self.scale
+        return 4 * f ** 3
+
+    def design_matrix(self):
+        f = np.sqrt(3) / self.scale
+        return np.array([[0.0, 1.0], [-f * f, -2 * f]])
+
+    def _ssm(self):
+        f = np.sqrt(3) / float(self.scale)
+        return _leaf_ssm(QS_M32, [f], [float(self.sigma), 0.0], np.diag([1.0, 3.0 / float(self.scale) ** 2]))
+
+    def _phi(self, dt):
+        dt = np.asarray(dt, dtype=np.float64)
+        f = np.sqrt(3) / float(self.scale)
+        fd = f * dt
+        return _damped(fd, [[1 + fd, dt], [-f * fd, 1 - fd]])
+
+
+class Matern52(_Leaf):
+    """sigma^2 (1 + f tau + f^2 tau^2 / 3) exp(-f tau), f = sqrt(5)/scale (reference ``quasisep.py:572-633``)."""
+
+    def __init__(self, scale, sigma=1.0):
+        self.scale, self.sigma = scale, sigma
+
+    @property
+    def _stationary(self):
+        from tinygp_amd.kernels.stationary import Matern52 as M
+        return M
+
+    def design_matrix(self):
+        f = np.sqrt(5) / self.scale
+        return np.array([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [-f ** 3, -3 * f ** 2, -3 * f]])
+
+    def _ssm(self):
+        f = np.sqrt(5) / float(self.scale)
+        f2 = f * f
+        P = np.array([[1.0, 0.0, -f2 / 3], [0.0, f2 / 3, 0.0], [-f2 / 3, 0.0, f2 * f2]])
+        return _leaf_ssm(QS_M52, [f], [float(self.sigma), 0.0, 0.0], P)
+
+    def _phi(self, dt):
+        d = np.asarray(dt, dtype=np.float64)
+        f = np.sqrt(5) / float(self.scale)
+        f2, fd, d2 = f * f, f * d, d * d
+        return _damped(fd, [
+            [0.5 * f2 * d2 + fd + 1, d * (fd + 1), 0.5 * d2],
+            [-0.5 * f * f2 * d2, -f2 * d2 + fd + 1, 0.5 * d * (2 - fd)],
+            [0.5 * f2 * f * d * (fd - 2), f2 * d * (fd - 3), 0.5 * f2 * d2 - 2 * fd + 1],
+        ])
+
+
+class Cosine(_Leaf):
+    """sigma^2 cos(2 pi tau / scale) (reference ``quasisep.py:636-673``); J = 2."""
+
+    def __init__(self, scale, sigma=1.0):
+        self.scale, self.sigma = scale, sigma
+
+    @property
+    def _stationary(self):
+        from tinygp_amd.kernels.stationary import Cosine as Cs
+        return Cs
+
+    def design_matrix(self):
+        f = 2 * np.pi / self.scale
+        return np.array([[0.0, -f], [f, 0.0]])
+
+    def _ssm(self):
+        return _leaf_ssm(QS_COS, [2 * np.pi / float(self.scale)], [float(self.sigma), 0.0], np.eye(2))
+
+    def _phi(self, dt):
+        a = 2 * np.pi / float(self.scale) * np.asarray(dt, dtype=np.float64)
+        c, s = np.cos(a), np.sin(a)
+        return _damped(np.zeros_like(a), [[c, -s], [s, c]])
+
+
+class Celerite(_Leaf):
+    """exp(-c tau) [a cos(d tau) + b sin(d tau)] (reference ``quasisep.py:343-401``); needs a c - b d > 0."""
+
+    def __init__(self, a, b, c, d):
+        self.a, self.b, self.c, self.d = a, b, c, d
+
+    def design_matrix(self):
+        return np.array([[-self.c, -self.d], [self.d, -self.c]])
+
+    def _ssm(self):
+        a, b, c, d = (float(v) for v in (self.a, self.b, self.c, self.d))
+        c2, d2 = c * c, d * d
+        s2 = c2 + d2
+        h2_2 = d2 * (a * c - b * d) / (2 * c * s2)
+        h2 = np.sqrt(h2_2)
+        h1 = (c * h2 - np.sqrt(a * d2 - s2 * h2_2)) / d
+        P = np.array([[1.0, -c / d], [-c / d, 1 + 2 * c2 / d2]])
+        return _leaf_ssm(QS_CELERITE, [c, d], [h1, h2], P)
+
+    def _phi(self, dt):
+        dt = np.asarray(dt, dtype=np.float64)
+        c, d = float(self.c), float(self.d)
+        co, si = np.cos(d * dt), np.sin(d * dt)
+        return _damped(c * dt, [[co, -si], [si, co]])
+
+
+class SHO(_Leaf):
+    """The damped, driven simple harmonic oscillator (reference ``quasisep.py:404-488``), J = 2, in its three
+    regimes: quality > 1/2, == 1/2 (``np.allclose``, as the reference decides it) and < 1/2."""
+
+    def __init__(self, omega, quality, sigma=1.0):
+        self.omega, self.quality, self.sigma = omega, quality, sigma
+
+    def design_matrix(self):
+        return np.array([[0.0, 1.0], [-self.omega ** 2, -self.omega / self.quality]])
+
+    def _regime(self):
+        q = float(self.quality)
+        if np.allclose(q, 0.5):
+            return QS_SHO_CRIT, 0.0
+        if q > 0.5:
+            return QS_SHO_UNDER, np.sqrt(max(4 * q * q - 1, 0.0))
+        return QS_SHO_OVER, np.sqrt(max(1 - 4 * q * q, 0.0))
+
+    def _ssm(self):
+        kind, f = self._regime()
+        w = float(self.omega)
+        return _leaf_ssm(kind, [w, float(self.quality), f], [float(self.sigma), 0.0], np.diag([1.0, w * w]))
+
+    def _phi(self, dt):
+        dt = np.asarray(dt, dtype=np.float64)
+        w, q = float(self.omega), float(self.quality)
+        kind, f = self._regime()
+        if kind == QS_SHO_CRIT:
+            wd = w * dt
+            return _damped(wd, [[1 + wd, dt], [-w * wd, 1 - wd]])
+        arg = 0.5 * f * w * dt / q
+        if kind == QS_SHO_UNDER:
+            s, c = np.sin(arg), np.cos(arg)
+        else:
+            s, c = np.sinh(arg), np.cosh(arg)
+        return _damped(0.5 * w * dt / q, [[c + s / f, 2 * q * s / (w * f)], [-2 * q * w * s / f, c - s / f]])

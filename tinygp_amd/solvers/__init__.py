@@ -1,11 +1,11 @@
-"""Solvers (mirror of ``tinygp.solvers``): the dense :class:`DirectSolver` on MI355X.
-
-``QuasisepSolver`` / ``KalmanSolver`` are a different algorithm family (O(N) state-space
-recurrences) and are outside the hot path this package replaces.
+"""Solvers (mirror of ``tinygp.solvers``): the dense :class:`DirectSolver` on MI355X, and
+:class:`QuasisepSolver`, the O(N J^2) state-space recurrences of ``kernels.quasisep`` on sorted
+1-D inputs, also on the device.  ``KalmanSolver`` is not provided.
 """
 
-__all__ = ["Solver", "DirectSolver", "DistributedDirectSolver"]
+__all__ = ["Solver", "DirectSolver", "DistributedDirectSolver", "QuasisepSolver"]
 
 from tinygp_amd.solvers.direct import DirectSolver
 from tinygp_amd.solvers.distributed import DistributedDirectSolver
 from tinygp_amd.solvers.solver import Solver
+from tinygp_amd.solvers.quasisep import QuasisepSolver

@@ -1,0 +1,218 @@
+"""``QuasisepSolver`` on MI355X (mirror of reference ``solvers/quasisep/solver.py``).
+
+For a :class:`tinygp_amd.kernels.quasisep.Quasisep` kernel on sorted 1-D inputs, ``K + diag(noise)`` has a Cholesky
+factor described by O(N J) numbers (``c_n``, ``w_n``; ``tests/_quasisep_np.py`` states the recursion).  A
+``tgp_qsep`` handle (C ABI, ``include/tgp_hip.h``) keeps t, the noise and that factor resident on the device; the
+factorisation, both triangular solves and ``L @ z`` are chunked reduce-then-scan recurrences in
+``csrc/qsep.hip``.  Nothing of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
+reference).
+
+dtypes: the device computes in fp64 whatever the inputs are; with fp32 inputs the results are returned as fp32
+(the Riccati recursion loses positivity quickly in fp32 arithmetic).
+
+Numerical failure never raises (as :class:`~tinygp_amd.solvers.DirectSolver`): a non-positive pivot sets
+``self.info`` to its 1-based step, ``log_probability`` returns ``-inf`` and the affected outputs are NaN.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any
+
+import numpy as np
+
+from tinygp_amd import _device, _ffi
+from tinygp_amd.noise import Diagonal, Noise
+from tinygp_amd.solvers.solver import Solver
+
+__all__ = ["QuasisepSolver"]
+
+
+def _check_sorted(t):
+    if np.any(np.diff(t) < 0):
+        raise ValueError(
+            "Input coordinates must be sorted in order to use the QuasisepSolver")
+
+
+def _f64(a, shape=None):
+    a = np.asarray(a, dtype=np.float64)
+    if shape is not None:
+        a = np.broadcast_to(a, shape)
+    return np.ascontiguousarray(a)
+
+
+class QuasisepSolver(Solver):
+    """O(N J^2) solver for quasiseparable kernels on sorted 1-D inputs.
+
+    Args:
+        kernel: a :class:`tinygp_amd.kernels.quasisep.Quasisep` kernel (state dimension J <= 8 on the device).
+        X: sorted coordinates, shape (N,) or (N, 1).
+        noise: a :class:`tinygp_amd.noise.Diagonal` noise model.
+        covariance: not supported (a dense matrix defeats the purpose; pass the kernel instead).
+        assume_sorted: skip the host check that X is sorted.
+        parallel: accepted for compatibility with the reference and ignored: the device always scans.
+        ctx: optional :class:`tinygp_amd._ffi.Ctx`.
+    """
+
+    def __init__(self, kernel, X, noise: Noise, *, covariance: Any | None = None, assume_sorted: bool = False,
+                 parallel: bool = False, ctx=None):
+        from tinygp_amd.kernels.quasisep import Quasisep, _coords
+
+        del parallel
+        if covariance is not None:
+            raise TypeError("QuasisepSolver takes no covariance=: it works from the quasiseparable kernel itself")
+        if not isinstance(noise, Diagonal):
+            raise TypeError(f"QuasisepSolver supports noise.Diagonal only (got {type(noise).__name__}); use "
+                            "DirectSolver for dense noise")
+        if not isinstance(kernel, Quasisep):
+            raise TypeError("QuasisepSolver needs a kernels.quasisep.Quasisep kernel")
+        self.kernel, self.X, self.noise = kernel, X, noise
+        t = _coords(X)
+        noise_diag = np.asarray(noise.diagonal())
+        self.dtype = _device.common_dtype(t, noise_diag)
+        self.n = t.shape[0]
+        if noise_diag.shape != (self.n,):
+            raise ValueError("the noise model must have one entry per data point")
+        if not assume_sorted:
+            _check_sorted(t)
+        self._t = _f64(t)
+        self._noise = _f64(noise_diag)
+        self._ssm = kernel._lower_ssm()
+        self._ctx = _ffi.default_ctx() if ctx is None else ctx
+        self._handle = None
+        h = C.c_void_p()
+        _ffi.check(_ffi.lib().tgp_qsep_create(self._ctx.handle, self.n, _ffi.ptr(self._t), C.byref(h)),
+                   "tgp_qsep_create")
+        self._handle = h
+        self._info = 0
+        self._factored = False
+
+    # -- factorisation -------------------------------------------------------------
+    def _model_args(self):
+        s = self._ssm
+        self._margs = (_f64(s.leaves), np.ascontiguousarray(s.state_map, dtype=np.int32), _f64(s.h), _f64(s.Pinf))
+        lv, sm, h, P = self._margs
+        return (_ffi.ptr(lv), len(lv), _ffi.ptr(sm), len(h), _ffi.ptr(h), _ffi.ptr(P), _ffi.ptr(self._noise))
+
+    def refactor(self, kernel=None) -> int:
+        """(Re-)factor in place, optionally with a new kernel of the same coordinates."""
+        if kernel is not None:
+            self._ssm, self.kernel = kernel._lower_ssm(), kernel
+        info = C.c_int32(0)
+        _ffi.check(_ffi.lib().tgp_qsep_factor(self._handle, *self._model_args(), C.byref(info)), "tgp_qsep_factor")
+        self._info, self._factored = int(info.value), True
+        return self._info
+
+    def _ensure_factor(self):
+        if not self._factored:
+            self.refactor()
+
+    @property
+    def info(self) -> int:
+        """0, or the 1-based step of the first non-positive pivot."""
+        self._ensure_factor()
+        return self._info
+
+    def factor_data(self):
+        """``(c, w)``: the factor's diagonal squares (N,) and its state vectors (N, J), as float64 host arrays."""
+        self._ensure_factor()
+        c = np.empty(self.n)
+        w = np.empty((self.n, self._ssm.J))
+        _ffi.check(_ffi.lib().tgp_qsep_factor_data(self._handle, _ffi.ptr(c), _ffi.ptr(w)), "tgp_qsep_factor_data")
+        return c, w
+
+    # -- Solver protocol -------------------------------------------------------------
+    def variance(self):
+        return (self.kernel(self.X) + self._noise).astype(self.dtype, copy=False)
+
+    def covariance(self):
+        """Dense, on the host, O(N^2) memory (reference ``solver.py`` makes the same caveat)."""
+        K = np.asarray(self.kernel(self.X, self.X), dtype=np.float64)
+        K[np.diag_indices(self.n)] += self._noise
+        return K.astype(self.dtype, copy=False)
+
+    def normalization(self):
+        self._ensure_factor()
+        out = C.c_double()
+        _ffi.check(_ffi.lib().tgp_qsep_normalization(self._handle, C.byref(out)), "tgp_qsep_normalization")
+        return self.dtype.type(np.nan if self._info else out.value)
+
+    def _affine(self, fn, y, *args):
+        self._ensure_factor()
+        y = np.asarray(y)
+        if y.ndim < 1 or y.shape[0] != self.n:
+            raise ValueError(f"y must have leading dimension {self.n}; got {y.shape}")
+        dt = np.result_type(self.dtype, y.dtype) if y.dtype.kind == "f" else self.dtype
+        yy = _f64(y.reshape(self.n, -1))
+        out = np.empty_like(yy)
+        if yy.shape[1]:
+            _ffi.check(fn(self._handle, *args, yy.shape[1], _ffi.ptr(yy), _ffi.ptr(out)), "tgp_qsep")
+        if self._info:
+            out[:] = np.nan
+        return out.reshape(y.shape).astype(dt, copy=False)
+
+    def solve_triangular(self, y, *, transpose: bool = False):
+        """``L x = y`` or ``L^T x = y``; y (N,) or (N, R)."""
+        return self._affine(_ffi.lib().tgp_qsep_solve_tri, y, int(bool(transpose)))
+
+    def dot_triangular(self, y):
+        """``L @ y``."""
+        return self._affine(_ffi.lib().tgp_qsep_dot_tri, y)
+
+    def _cond(self, kernel, X_test, var_only: bool):
+        """``Kss - A^T A`` with ``A = L^-1 Ks``: Ks and Kss on the host, the M-column solve on the device
+        (the reference's own fallback, ``solvers/quasisep/solver.py:130-139``)."""
+        Xt = self.X if X_test is None else X_test
+        A = self.solve_triangular(np.asarray(kernel(self.X, Xt), dtype=np.float64))
+        if var_only:
+            return np.asarray(kernel(Xt), dtype=np.float64) - np.sum(A * A, axis=0)
+        return np.asarray(kernel(Xt, Xt), dtype=np.float64) - A.T @ A
+
+    def condition(self, kernel, X_test, noise):
+        out = self._cond(kernel, X_test, False)
+        if isinstance(noise, Diagonal):
+            out[np.diag_indices(out.shape[0])] += np.asarray(noise.diagonal())
+        else:
+            out = out + noise
+        return out.astype(self.dtype, copy=False)
+
+    def condition_variance(self, kernel, X_test):
+        return self._cond(kernel, X_test, True).astype(self.dtype, copy=False)
+
+    # -- fused entry points used by GaussianProcess ------------------------------------
+    def log_probability(self, resid):
+        """Factor + forward solve + sums in one call; non-finite or a failed factor -> ``-inf``."""
+        r = _f64(resid, (self.n,))
+        info, out = C.c_int32(0), C.c_double()
+        _ffi.check(_ffi.lib().tgp_qsep_factor_logprob(self._handle, *self._model_args(), _ffi.ptr(r),
+                                                      C.byref(info), C.byref(out)), "tgp_qsep_factor_logprob")
+        self._info, self._factored = int(info.value), True
+        v = out.value
+        if self._info or not np.isfinite(v):
+            v = -np.inf
+        return self.dtype.type(v)
+
+    def alpha(self, resid):
+        """``(K^-1 r, log_probability)``."""
+        self._ensure_factor()
+        z = self.solve_triangular(_f64(resid, (self.n,)))
+        a = self.solve_triangular(z, transpose=True)
+        v = -0.5 * float(np.sum(np.square(z, dtype=np.float64))) - float(self.normalization())
+        if self._info or not np.isfinite(v):
+            v = -np.inf
+        return a.astype(self.dtype, copy=False), self.dtype.type(v)
+
+    def log_probability_and_grad(self, resid):
+        raise NotImplementedError("the gradient of the quasiseparable log-probability is not yet implemented")
+
+    # -- lifetime ----------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_handle", None):
+            _ffi.lib().tgp_qsep_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
