@@ -6,6 +6,7 @@ import scipy.linalg as sla
 
 import _cases
 import _lowlevel as ll
+from _schedules import PANEL_CHAIN_VARIANTS
 from conftest import ulp_diff
 from oracle import tinygp_np as o
 from tinygp_amd import kernels
@@ -217,32 +218,7 @@ def test_potrf_block_sizes_agree(nb_outer):
 
 
 @pytest.mark.parametrize("n", [1152, 2560, 5120])
-@pytest.mark.parametrize("opts", [dict(chain_kernel=0, fused_step=1, gate_split=0), dict(chain_kernel=0, fused_step=1, gate_split=1),
-                                  dict(chain_kernel=0, fused_step=1, gate_split=1, lookahead=0),
-                                  dict(chain_kernel=0, fused_step=0, chain_reserve=0), dict(chain_kernel=0, fused_step=1, chain_reserve=256),
-                                  dict(chain_kernel=0, sub_panel=512), dict(chain_kernel=0, sub_panel=256, first_split=4),
-                                  dict(chain_kernel=0, nb_first=256), dict(chain_kernel=0, nb_first=512, sub_panel=512, lookahead=0),
-                                  dict(chain_kernel=0, split_tail=1), dict(chain_kernel=0, split_tail=1, sub_panel=512, nb_first=768),
-                                  dict(chain_kernel=0),
-                                  # the persistent chain (the default): panel by panel only, without look-ahead, two
-                                  # chain workgroups per compute unit, narrow panels + early share, a narrow first panel
-                                  dict(chain_full_rows=0), dict(lookahead=0), dict(lookahead=0, chain_full_rows=0),
-                                  dict(chain_lds_pad=0), dict(nb_outer=512, first_split=3, chain_full_rows=2048),
-                                  dict(nb_first=256, chain_full_rows=1024), dict(first_split=0, chain_reserve=0),
-                                  # round 5: update tasks on the 4x4x4 MFMA form with LDS-direct operands (measured, not the default); the
-                                  # followers of a chain launch behind a stream wait-value / behind the whole launch
-                                  # (default: the wall-clock-bounded one-wave poll kernel)
-                                  dict(chain_fast_update=1), dict(chain_polls=3), dict(chain_polls=0),
-                                  dict(chain_fast_update=1, chain_polls=3, chain_full_rows=0),
-                                  # round 6 (measured, not the defaults): K-batched update tasks, everywhere and in the
-                                  # one-launch tail only; the next panel's first diagonal block beside the gate
-                                  dict(chain_batch=4, chain_batch_minrows=0), dict(chain_batch=4, chain_full_rows=8192),
-                                  dict(chain_batch=8, chain_batch_lag=2, chain_batch_rowlag=3, chain_batch_minrows=0),
-                                  dict(chain_gate_split=1), dict(chain_gate_split=1, chain_full_rows=0),
-                                  # the merged schedule's prefix poll as a kernel of its own (default: inside the panel's potf2)
-                                  dict(chain_polls=2), dict(chain_polls=2, chain_full_rows=0),
-                                  # the chain of a panel sub-panel by sub-panel (measured, not the default: profiles/r06_i)
-                                  dict(chain_sub_panel=512), dict(chain_sub_panel=256, chain_sub_role=0, chain_full_rows=0)])
+@pytest.mark.parametrize("opts", PANEL_CHAIN_VARIANTS)
 def test_panel_chain_variants_agree(n, opts):
     """The schedules of the panel chain -- the default persistent chain (chain_kernel: tile tasks behind a ticket
     counter, the whole rest of the matrix in one launch once few rows are left), one fused launch per 128-column

@@ -7,6 +7,11 @@ verifies with vector clocks that each pair of conflicting accesses (write-write,
 read-write) is ordered by stream order or by an event record / wait pair -- i.e. that the
 multi-stream schedule has no data race by construction.  (The GPU suite's determinism test is
 the empirical counterpart.)
+
+The fused evaluation's two sums are modelled too: the per-block partial sums ('S', j) that the
+chain's forward-substitution tasks leave and the evaluation's scalars ('Z',).  A read of a partial
+sum that no earlier record of the same trace wrote is a STALE read (a value left by an earlier
+evaluation), and exactly one record writes the scalars.
 """
 import ctypes as C
 
@@ -26,24 +31,29 @@ def trace(n_pad, nb=1024, lookahead=1, first_split=5, first_small=1100, fused=1,
     chain (potf2 | trsm | in-panel update per block -- the library's default) instead of one panel-step
     launch per block, bit 2 = the block-column update between two chains in one piece (no split gate).
     `more`: further context options by name (sub_panel=512, nb_first=256, ...)."""
-    lib = _ffi.load_library()
-    cap = 48 * (n_pad // 128) + 256
-    out = np.zeros(cap * 10, dtype=np.int64)
-    n = C.c_int64()
     opts = dict(nb_outer=nb, lookahead=lookahead, first_split=first_split, first_small_tiles=first_small,
                 nb_wide_rows=wide_rows, fused_step=0 if fused & 2 else 1, gate_split=0 if fused & 4 else 1)
     opts["chain_kernel"] = 0  # (the library's default is the persistent chain: its configurations say so)
     opts.update(more)
+    return trace_options(n_pad, opts, fused & 1)
+
+
+def trace_options(n_pad, opts, fused):
+    """The records of tgp_trace_factor with exactly these context options (library defaults for the others)."""
+    lib = _ffi.load_library()
+    cap = 48 * (n_pad // 128) + 256
+    out = np.zeros(cap * 10, dtype=np.int64)
+    n = C.c_int64()
     text = ",".join(f"{k}={v}" for k, v in opts.items())
-    st = lib.tgp_trace_factor(n_pad, text.encode(), fused & 1, out.ctypes.data_as(C.POINTER(C.c_int64)), cap,
-                              C.byref(n))
+    st = lib.tgp_trace_factor(n_pad, text.encode(), fused, out.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n))
     assert st == 0, lib.tgp_last_error()
     return out[: n.value * 10].reshape(-1, 10).tolist()
 
 
 def accesses(rec, T, part=None):
     """(reads, writes): sets of resources.  ('A', tr, tc) matrix tile, ('D', j) 16x16 inverses
-    of block j, ('Y', j) 128 entries of the solved vector."""
+    of block j, ('Y', j) 128 entries of the solved vector, ('S', j) the partial sums of block j
+    (chain_column_accesses), ('Z',) the evaluation's two scalars (sum z^2, sum log L_ii)."""
     kind, _, *v = rec
     R, W = set(), set()
 
@@ -56,8 +66,9 @@ def accesses(rec, T, part=None):
         W |= {("A", tr, tc) for tc in range(tc0, tc0 + ntc) for tr in range(tc, T)}
     elif kind == 8:
         W |= {("Y", j) for j in range(T)}
-    elif kind == 9:
+    elif kind == 9:  # the reduction kernels behind the factorisation (only when no chain launch left the sums)
         R |= {("A", j, j) for j in range(T)} | {("Y", j) for j in range(T)}
+        W.add(("Z",))
     elif kind == 1:
         tr, tc = tile(v[0], v[2])
         assert tr == tc
@@ -123,7 +134,9 @@ def chain_column_accesses(rec, c):
     """What the persistent chain launch `rec` (kind 11: block columns [cb, ce) of the panel at (t0, t0), `rows` row
     tiles, nblk block columns) reads and writes while it makes block column c final: the column's own tiles (potf2 --
     the panel's very first block is factored by the potf2 launch in front --, the solves of the rows below) and,
-    right-looking, every LATER block column of the panel (the update tasks behind column c)."""
+    right-looking, every LATER block column of the panel (the update tasks behind column c).  v[7], the evaluation's
+    sums: 0 none; 1 the forward task of column c writes the partial sums S(t0 + c); 2 also, at the launch's last column
+    (the matrix's last block), every partial sum S(0 .. t0 + rows) is read and the scalars Z are written."""
     _, _, *v = rec
     ld, rows, cb, ce, nblk = v[1], v[2], v[3], v[4], v[5]
     off = v[0]
@@ -147,10 +160,21 @@ def chain_column_accesses(rec, c):
             R.add(("A", t0 + c, t0 + c - 1)); R.add(("Y", t0 + c - 1))
         for i in range(c + 1, rows):
             R.add(("Y", t0 + i)); W.add(("Y", t0 + i))
+    red = v[7] if len(v) > 7 else 0
+    if red >= 1:
+        assert v[6], ("partial sums without forward tasks", rec)
+        W.add(("S", t0 + c))
+    if red == 2 and c == ce - 1:
+        assert ce == rows, ("the sums are added up by the launch with the matrix's last block", rec)
+        R |= {("S", j) for j in range(t0 + rows)}
+        W.add(("Z",))
     return R, W
 
 
 def find_races(recs, T, limit=5):
+    """Unordered pairs of conflicting accesses ("after write", "write after read") and STALE reads: a partial sum
+    ('S', j) read with no write of it earlier in the trace (the record that writes it and adds the sums up at once
+    counts as earlier)."""
     clock = [[0] * NSTREAMS for _ in range(NSTREAMS)]
     snap = {}
     last_w = {}   # resource -> (stream, counter, index)
@@ -162,6 +186,9 @@ def find_races(recs, T, limit=5):
         return now_clock[s] >= c
 
     def check_and_register(R, W, now, me, idx):
+        for r in R - W:
+            if r[0] == "S" and r not in last_w:
+                races.append((r, None, idx, "stale read"))
         for r in R | W:
             lw = last_w.get(r)
             if lw is not None and lw[2] != idx and not ordered(lw, now):
@@ -228,8 +255,16 @@ def find_races(recs, T, limit=5):
         check_and_register(R, W, now, me, idx)
         if len(races) >= limit:
             break
-    return [(r, f"#{i} {KIND[recs[i][0]]} s{recs[i][1]}", f"#{j} {KIND[recs[j][0]]} s{recs[j][1]}", why)
-            for r, i, j, why in races[:limit]]
+    def at(i):
+        return "-" if i is None else f"#{i} {KIND[recs[i][0]]} s{recs[i][1]}"
+
+    return [(r, at(i), at(j), why) for r, i, j, why in races[:limit]]
+
+
+def scalar_writers(recs):
+    """Records that write the evaluation's scalars: the reduction kernels (kind 9) or the chain launch that adds the
+    partial sums up (v[7] = 2)."""
+    return [i for i, r in enumerate(recs) if r[0] == 9 or (r[0] == 11 and r[9] == 2)]
 
 
 CONFIGS = [
@@ -308,7 +343,35 @@ CONFIGS = [
     (16384, 1024, 1, 5, 1100, 3, 0, dict(chain_kernel=1, chain_merged=1, chain_sub_panel=512)),
     (16384, 1024, 1, 5, 1100, 3, 0, dict(chain_kernel=1, chain_merged=1, chain_sub_panel=256, chain_sub_role=0)),
     (9216, 1024, 1, 5, 1100, 3, 0, dict(chain_kernel=1, chain_merged=1, chain_sub_panel=512, chain_sub_min_rows=6144)),
+    # panels on both sides of the chain launch's limit of 64 block columns: a wider panel runs block by block (MIXED below),
+    # and then the forward substitution of the whole evaluation stays on the followers and the reduction kernels run
+    (9216, 1024, 1, 5, 1100, 3, 0, dict(chain_kernel=1, nb_first=8320)),
+    (9216, 1024, 1, 5, 1100, 1, 0, dict(chain_kernel=1, nb_first=8320)),
+    (9216, 1024, 0, 5, 1100, 3, 0, dict(chain_kernel=1, nb_first=8320)),
+    (9216, 1024, 1, 5, 1100, 3, 0, dict(chain_kernel=1, nb_first=8320, chain_sub_panel=512)),
+    (9216, 1024, 1, 5, 1100, 3, 0, dict(chain_kernel=1, nb_first=8320, chain_fwd_tasks=0)),
+    (9216, 1024, 1, 5, 1100, 3, 0, dict(chain_kernel=1, nb_first=8192)),   # 64 blocks: every panel is a chain
+    (9216, 1024, 1, 5, 1100, 1, 0, dict(chain_kernel=1, nb_first=8192)),
+    (9216, 1024, 1, 5, 1100, 3, 0, dict(chain_kernel=1, nb_first=8064)),
+    (12288, 8448, 1, 5, 1100, 3, 0, dict(chain_kernel=1)),
+    (12288, 8448, 0, 5, 1100, 3, 0, dict(chain_kernel=1)),
+    (12288, 8448, 1, 5, 1100, 1, 0, dict(chain_kernel=1)),
+    (12288, 8448, 1, 5, 1100, 3, 0, dict(chain_kernel=1, chain_fwd_tasks=0)),
+    (12288, 8192, 1, 5, 1100, 3, 0, dict(chain_kernel=1)),
+    (12288, 8192, 0, 5, 1100, 3, 0, dict(chain_kernel=1)),
+    (16896, 4224, 1, 5, 1100, 3, 8000, dict(chain_kernel=1)),              # wide panel: chain 33, per block 66, chain 33
+    (16896, 4224, 0, 5, 1100, 3, 8000, dict(chain_kernel=1)),
+    (16384, 4096, 1, 5, 1100, 3, 8000, dict(chain_kernel=1)),              # wide panel of exactly 64 blocks
+    (24576, 16384, 1, 5, 1100, 3, 0, dict(chain_kernel=1)),
+    (12288, 1024, 1, 5, 1100, 3, 0, dict(chain_kernel=1)),                 # the default schedule above 8 192 rows
 ]
+
+# (n_pad, nb, wide_rows, nb_first) of the configurations above with a panel of more than 64 block columns
+MIXED = {(9216, 1024, 0, 8320), (12288, 8448, 0, 0), (16896, 4224, 8000, 0), (24576, 16384, 0, 0)}
+
+
+def _mixed(c):
+    return len(c) > 7 and bool(c[7].get("chain_kernel")) and (c[0], c[1], c[6], c[7].get("nb_first", 0)) in MIXED
 
 
 # round 6: the default schedule with the persistent chain is the MERGED trailing update (one launch per panel, the next
@@ -341,7 +404,10 @@ def test_schedule_has_no_data_race(cfg):
 
     order = [j for r in recs for j in factored(r)]
     assert order == list(range(T))
-    if len(cfg) > 7 and cfg[7].get("chain_kernel"):
+    mixed = _mixed(cfg)
+    if mixed:  # chain launches and panels block by block (trsm or panel-step launches) in one factorisation
+        assert any(r[0] == 11 for r in recs) and any(r[0] in (2, 10) for r in recs)
+    elif len(cfg) > 7 and cfg[7].get("chain_kernel"):
         assert not any(r[0] in (2, 10) for r in recs)            # no trsm / panel-step launches ...
         # ... and nothing on the update stream's GEMM queue but the next panel's first diagonal block (chain_gate_split)
         assert all(r[5] == 128 and r[6] == 128 and cfg[7].get("chain_gate_split") for r in recs if r[0] == 3 and r[1] == 3)
@@ -349,15 +415,19 @@ def test_schedule_has_no_data_race(cfg):
         assert not any(r[0] == 10 for r in recs)
     else:
         assert not any(r[0] == 2 for r in recs)  # every trsm of the chain rides in a panel step
-    in_chain = len(cfg) > 7 and cfg[7].get("chain_kernel") and cfg[7].get("chain_fwd_tasks", 1)
+    in_chain = len(cfg) > 7 and cfg[7].get("chain_kernel") and cfg[7].get("chain_fwd_tasks", 1) and not mixed
     if cfg[5] & 1 and in_chain:
         # round 6: the forward substitution rides in the chain launches as tasks -- no step launch, no poller for it
         assert not any(r[0] == 4 for r in recs)
         assert all(r[8] == 1 for r in recs if r[0] == 11)
         if cfg[7].get("chain_depth2", 1) and cfg[2]:
             assert not any(r[0] == 12 for r in recs)  # (the default schedule has no early shares either)
+        # ... and so do the two sums: every launch leaves its blocks' partial sums, the last one adds them up
+        assert all(r[9] >= 1 for r in recs if r[0] == 11) and not any(r[0] == 9 for r in recs)
     elif cfg[5] & 1:
         assert sum(1 for r in recs if r[0] == 4) == T  # one forward-substitution step per block
+        assert not any(r[0] == 11 and (r[8] or r[9]) for r in recs)  # no chain task touches y or the sums
+    assert len(scalar_writers(recs)) == 1  # the scalars are written exactly once: by the chain or by the reduction kernels
     assert find_races(recs, T) == []
 
 
@@ -383,6 +453,53 @@ def test_checker_sees_a_missing_dependency():
     no_chain_wait = [r for r in recs if not (r[0] == 6 and r[1] == 0 and r[2] == 1)]  # main waits ev_b
     assert len(no_chain_wait) < len(recs)
     assert find_races(no_chain_wait, T)
+
+
+def test_checker_sees_a_stale_partial_sum():
+    """The fused evaluation's sums: a chain launch that leaves no partial sums for its block columns (v[7] = 0, an edit of
+    a clean trace) in front of the launch that adds them all up must be reported as stale reads of exactly those blocks."""
+    recs = trace(16384, 1024, 1, 5, 1100, 3, 0, chain_kernel=1)
+    T = 16384 // 128
+    assert find_races(recs, T) == []
+    chains = [i for i, r in enumerate(recs) if r[0] == 11]
+    assert [recs[i][9] for i in chains] == [1] * (len(chains) - 1) + [2]
+    first = recs[chains[0]]
+    t0 = (first[2] % first[3]) // 128
+    dropped = [list(r) for r in recs]
+    dropped[chains[0]][9] = 0
+    found = find_races(dropped, T, limit=1000)
+    assert found and all(why == "stale read" and b == f"#{chains[-1]} chain s{recs[chains[-1]][1]}" for _, _, b, why in found)
+    assert sorted(r for r, *_ in found) == [("S", t0 + c) for c in range(first[5], first[6])]
+
+
+def test_checker_sees_a_forward_step_without_its_wait():
+    """Panels on both sides of the 64-block limit: the forward substitution runs on the followers and the reduction
+    kernels read y behind it.  Without the wait that puts the reductions behind the last forward step (the main stream
+    waits for ev_c), the checker must report the race on y."""
+    recs = trace(9216, 1024, 1, 5, 1100, 3, 0, chain_kernel=1, nb_first=8320)
+    T = 9216 // 128
+    assert find_races(recs, T) == [] and sum(1 for r in recs if r[0] == 4) == T and scalar_writers(recs) == [len(recs) - 1]
+    last_wait = max(i for i, r in enumerate(recs) if r[0] == 6 and r[1] == 0 and r[2] == 2)  # main waits ev_c
+    found = find_races(recs[:last_wait] + recs[last_wait + 1:], T)
+    assert found and all(r[0] == "Y" and why == "after write" for r, _, _, why in found)
+
+
+def test_default_schedule_trace_is_unchanged():
+    """Panels on both sides of the 64-block limit take one decision per evaluation; the default schedule is not affected:
+    its records at N = 16 384 -- the persistent chain's configuration above and the library's defaults with and without
+    the fused solve -- are the ones kept in tests/golden/schedule_traces.npz (tests/golden/make_golden_schedule.py)."""
+    import importlib.util
+    from pathlib import Path
+
+    here = Path(__file__).resolve().parent / "golden"
+    spec = importlib.util.spec_from_file_location("make_golden_schedule", here / "make_golden_schedule.py")
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want = np.load(here / "schedule_traces.npz")
+    got = gen.traces()
+    assert sorted(got) == sorted(want.files)
+    for name, recs in got.items():
+        assert np.array_equal(np.asarray(recs, dtype=np.int64), want[name]), name
 
 
 def test_checker_sees_a_missing_join_of_the_split_gate():

@@ -743,19 +743,17 @@ static int factor_body(tgp_solver* s, const tgp_kop* prog, int nops, const void*
     ctx->defer_join = ctx->late_join != 0;  // (one host round trip per evaluation: `info` comes back with the scalars below)
     ctx->join_deferred = false;
     // (the chain's fsolve tasks leave both sums when the forward substitution rides in the chain launches: chol.hip)
-    ctx->chain_red_total = fused && ctx->chain_reduce != 0 ? s->npad / 128 : 0;
-    ctx->reductions_done = false;
+    reductions_begin(ctx, s->npad, fused != 0);
     int st = potrf<T>(ctx, s->npad, A, s->npad, (T*)s->dinv, &inf, fused ? (T*)s->vec : (T*)nullptr);
     ctx->defer_join = false;
-    ctx->chain_red_total = 0;
+    const bool reduce = reductions_end(ctx);
     if (st < 0) return st;
     s->info = inf;
     if (prof) TGP_HIP_TRY(hipEventRecord(e2, ctx->stream));
-    if (!ctx->reductions_done) {
+    if (reduce) {
       TGP_TRY(launch_sum_log_diag<T>(ctx, s->n, A, s->npad, 1));
       if (fused) TGP_TRY(launch_sum_squares<T>(ctx, s->n, (const T*)s->vec, 0));
     }
-    ctx->reductions_done = false;
     return TGP_OK;
   });
   if (status < 0) return status;
@@ -1354,9 +1352,11 @@ int tgp_trace_factor(int64_t n_pad, const char* options, int32_t fused, int64_t*
   if (fused & 1) trace_push(&ctx, 8, ctx.stream);  // residual -> work vector (main stream, in front of the assembly)
   TGP_TRY(assemble_lower<double>(&ctx, kp, n_pad, 1, X, X, base, n_pad));
   int32_t info = 0;
+  reductions_begin(&ctx, n_pad, (fused & 1) != 0);  // (factor_body's decision: the chain launches may leave both sums)
   const int st = potrf<double>(&ctx, n_pad, base, n_pad, dinv, &info, (fused & 1) ? y : nullptr);
+  const bool reduce = reductions_end(&ctx);
   if (st < 0) return st;
-  trace_push(&ctx, 9, ctx.stream);  // reductions over diag(L) and the solved vector (main stream)
+  if (reduce) trace_push(&ctx, 9, ctx.stream);  // reductions over diag(L) and the solved vector (main stream)
   *n_records = (int64_t)recs.size();
   TGP_ARG_CHECK((int64_t)recs.size() <= cap_records, "trace: %lld records, room for %lld",
                 (long long)recs.size(), (long long)cap_records);

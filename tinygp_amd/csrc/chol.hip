@@ -2418,15 +2418,28 @@ int launch_chain(tgp_ctx* ctx, hipStream_t st, T* A0, int64_t ld, T* dinv0, int6
     TGP_TRY(st_wait(ctx, st, ctx->ev_f));
     ctx->chain_polls_pending = false;
   }
-  if (ctx->trace) {  // v: panel origin offset, ld, row tiles, first / end block column
+  const int fwd = y0 != nullptr ? 1 : 0;  // the forward substitution of these block columns as tasks of the launch
+  // the evaluation's two sums (ChainArgs::red): 0 the launch leaves none, 1 it leaves the partial sums of its block columns in
+  // d_chain_red, 2 it also adds slots [0, chain_red_total) up into d_scal (and the reduction kernels are not launched)
+  int red = 0;
+  if (fwd != 0 && ctx->chain_red_total > 0 && ctx->chain_red_total <= CHAIN_MAX_ROW_TILES && pivot_base % TILE == 0) {
+    red = 1;
+    ctx->chain_red_written += ce - cb;
+    // the launch with the matrix's last block adds the partial sums up -- only if THIS evaluation's launches wrote every
+    // slot (a slot that none of them wrote holds a value of an earlier evaluation)
+    if (pivot_base / TILE + ce == ctx->chain_red_total && ctx->chain_red_written == ctx->chain_red_total) {
+      red = 2;
+      ctx->reductions_done = true;
+    }
+  }
+  if (ctx->trace) {  // v: panel origin offset, ld, row tiles, first / end block column, blocks, forward tasks, sums
     if (counters_ready != nullptr) TGP_TRY(ev_record(ctx, counters_ready, st));
-    trace_push(ctx, 11, st, trace_off(ctx, A0), ld, R, cb, ce, nblk, y0 != nullptr ? 1 : 0);
+    trace_push(ctx, 11, st, trace_off(ctx, A0), ld, R, cb, ce, nblk, fwd, red);
     return TGP_OK;
   }
   // the launch's task list (chain_tasks.h: ticket order + K-batched updates), one table per shape and policy, kept on the
   // device for the life of the context (13 shapes per evaluation at c2, the same in every evaluation)
   const ChainPolicy pol = chain_policy<T>(ctx);
-  const int fwd = y0 != nullptr ? 1 : 0;  // the forward substitution of these block columns as tasks of the launch
   const std::array<int64_t, 9> key = {R, nblk, cb, ce, pol.batch, pol.lag, pol.rowlag, pol.minrows, fwd};
   auto found = ctx->chain_tables.find(key);
   if (found == ctx->chain_tables.end()) {
@@ -2462,15 +2475,9 @@ int launch_chain(tgp_ctx* ctx, hipStream_t st, T* A0, int64_t ld, T* dinv0, int6
   q.y = y0;
   q.fgs = CHAIN_FWD_GROUP;
   q.fprev = fprev ? 1 : 0;
-  q.red = nullptr; q.scal = nullptr; q.red_total = 0;
-  if (fwd != 0 && ctx->chain_red_total > 0 && ctx->chain_red_total <= CHAIN_MAX_ROW_TILES && pivot_base % TILE == 0) {
-    q.red = ctx->d_chain_red;
-    q.scal = ctx->d_scal;
-    if (pivot_base / TILE + ce == ctx->chain_red_total) {  // the launch with the matrix's last block adds the partial sums up
-      q.red_total = (int32_t)ctx->chain_red_total;
-      ctx->reductions_done = true;
-    }
-  }
+  q.red = red != 0 ? ctx->d_chain_red : nullptr;
+  q.scal = red != 0 ? ctx->d_scal : nullptr;
+  q.red_total = red == 2 ? (int32_t)ctx->chain_red_total : 0;
   if (ctx->chain_stamps != 0 && ctx->chain_stamp_base + tasks <= CHAIN_STAMP_TASKS) {
     if (ctx->d_chain_stamps == nullptr)
       TGP_HIP_TRY(hipMalloc((void**)&ctx->d_chain_stamps, size_t(CHAIN_STAMP_TASKS) * 16 * sizeof(long long)));
@@ -2619,8 +2626,9 @@ int panel_chain(tgp_ctx* ctx, hipStream_t st, int64_t n, T* A, int64_t ld, T* di
     // (as in the per-block path: the early share exists when rows AND columns are left behind block after_blocks-1)
     const bool mid_in = after_blocks > cb && after_blocks <= ce && after_blocks < nblk && R > after_blocks;
     // Round 6: the forward-substitution steps of these block columns are TASKS of the launch (chain_tasks.h, F(c)) -- no
-    // poller, no per-block launch pair on the solve stream (ctx option chain_fwd_tasks = 0: round 5's followers)
-    const bool fwd_in = y != nullptr && ctx->chain_fwd_tasks != 0;
+    // poller, no per-block launch pair on the solve stream (ctx option chain_fwd_tasks = 0: round 5's followers; potrf
+    // decides once per factorisation, chain_fwd_now)
+    const bool fwd_in = y != nullptr && ctx->chain_fwd_now;
     T* y_follow = fwd_in ? (T*)nullptr : y;
     const bool follow = y_follow != nullptr || mid_in;
     const bool polls = follow && ctx->chain_polls != 0;
@@ -2827,6 +2835,15 @@ int potrf(tgp_ctx* ctx, int64_t n, T* A, int64_t ld, T* dinv, int32_t* info_host
     if (ctx->chain_kernel != 0 && rem <= ctx->chain_full_rows && rem / TILE <= 64) w = rem;
     return rem < w ? rem : w;
   };
+  // ONE decision per factorisation: the forward substitution (and with it the fused evaluation's two sums) rides in the
+  // chain launches only if EVERY panel is one (panel_chain: at most CHAIN_FLAG_LD block columns and CHAIN_MAX_ROW_TILES row
+  // tiles).  A panel that runs block by block queues its forward steps on the solve stream, which nothing orders against
+  // the forward tasks of a chain launch, and leaves no partial sums: then every panel keeps y on the followers and the
+  // reduction kernels run (capi.hip).  (Sub-panels of chain_of_panel are narrower than their panel: never a chain less.)
+  bool all_chain = ctx->chain_kernel != 0;
+  for (int64_t k0 = 0; k0 < n && all_chain; k0 += width(k0))
+    all_chain = width(k0) / TILE <= CHAIN_FLAG_LD && (n - k0) / TILE <= CHAIN_MAX_ROW_TILES;
+  ctx->chain_fwd_now = y != nullptr && ctx->chain_fwd_tasks != 0 && all_chain;
   // TWO-LEVEL PANEL for the persistent chain (round 6, merged schedule; ctx option chain_sub_panel): the chain of a panel runs
   // sub-panel by sub-panel -- its in-panel rank-128 update tasks stay inside `chain_sub_panel` columns -- and every finished
   // sub-panel updates the panel's remaining columns with ONE K = chain_sub_panel product on the tiled MFMA kernel (the same
@@ -2979,7 +2996,7 @@ int potrf(tgp_ctx* ctx, int64_t n, T* A, int64_t ld, T* dinv, int32_t* info_host
         // chain_gate_split: the next panel's first diagonal block on the update stream (idle with the persistent chain once
         // the forward steps are chain tasks) beside the gate -- its own 128 x 128 x kb product, then potf2; the gate skips it
         const bool gsplit = ctx->chain_gate_split != 0 && grole == 4 && mt > TILE && ctx->update_stream != nullptr &&
-                            (y == nullptr || ctx->chain_fwd_tasks != 0 || ctx->solve_on_update == 0);
+                            (y == nullptr || ctx->chain_fwd_now || ctx->solve_on_update == 0);
         if (gsplit) {
           hipStream_t S3 = ctx->update_stream;
           TGP_TRY(ev_record(ctx, ctx->ev_i, S1));  // (everything the gate waits for)

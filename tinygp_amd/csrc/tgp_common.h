@@ -134,6 +134,7 @@ struct tgp_ctx {
   int64_t chain_reduce = 1;
   double* d_chain_red = nullptr;   // [2 * CHAIN_MAX_ROW_TILES] per-block partial sums
   int64_t chain_red_total = 0;     // set by the fused evaluation around its potrf call: blocks of the matrix (0: off)
+  int64_t chain_red_written = 0;   // ... blocks whose partial sums the chain launches of this evaluation wrote (launch_chain)
   bool reductions_done = false;    // ... and the answer: the launch with the matrix's last block left both sums in d_scal[0..1]
   bool defer_join = false;     // set by the fused evaluation around its potrf call: do not join, `info` is read with the scalars
   bool join_deferred = false;  // ... and potrf's answer: it did leave the join (and the check of d_info) to the caller
@@ -197,6 +198,7 @@ struct tgp_ctx {
   // Round 6: the fused forward substitution as TASKS of the chain launch (chain_tasks.h F(c), chol.hip chain_fsolve /
   // chain_fupdate): no poller, no forward-step launch at all.  0: round 5's followers on the solve stream (chain_polls)
   int64_t chain_fwd_tasks = 1;
+  bool chain_fwd_now = false;  // set by potrf: the forward substitution rides in THIS factorisation's chain launches
   bool wait_values_inflight = false;  // this factorisation enqueued stream wait-values: join with a deadline (join_bounded)
   // tile order of the MFMA products (tile_order.h): bands of this many tile rows, column by column inside a band; 0 = column
   // by column over all rows (rounds 1-4).  Round 5, measured at c2 (profiles/r05_j, r05_k): fabric traffic of a
@@ -310,6 +312,22 @@ inline int64_t first_panel_cols(const tgp_ctx* ctx, int64_t n) {
   if (ctx->nb_first >= TILE) w = ctx->nb_first / TILE * TILE;
   if (ctx->chain_kernel != 0 && n <= ctx->chain_full_rows && n / TILE <= 64) w = n;
   return n < w ? n : w;
+}
+
+// The evaluation's two sums (sum z^2, sum log L_ii) around its potrf call -- shared by factor_body and the schedule tracer
+// (tgp_trace_factor), so that the traced reductions are the library's: reductions_begin in front of potrf (fused: the chain
+// launches may leave both sums, chol.hip launch_chain), reductions_end behind it -- true: the reduction kernels must run.
+inline void reductions_begin(tgp_ctx* ctx, int64_t npad, bool fused) {
+  ctx->chain_red_total = fused && ctx->chain_reduce != 0 ? npad / TILE : 0;
+  ctx->chain_red_written = 0;
+  ctx->reductions_done = false;
+}
+inline bool reductions_end(tgp_ctx* ctx) {
+  const bool launch = !ctx->reductions_done;
+  ctx->chain_red_total = 0;
+  ctx->chain_red_written = 0;
+  ctx->reductions_done = false;
+  return launch;
 }
 
 int ensure_dinv(tgp_ctx* ctx, size_t bytes);
