@@ -610,6 +610,12 @@ int tgp_qsep_normalization(tgp_qsep* q, double* out); /* 1/2 sum log c_n + n/2 l
 int tgp_qsep_solve_tri(tgp_qsep* q, int transpose, int64_t nrhs, const double* y_host, double* out_host);
 int tgp_qsep_dot_tri(tgp_qsep* q, int64_t nrhs, const double* y_host, double* out_host); /* L y */
 int tgp_qsep_factor_data(tgp_qsep* q, double* c_host, double* w_host); /* c (n), w (n x J); either may be NULL */
+/* Conditional mean k(x, t) K^-1 r and variance k(x, x) - k(x, t) K^-1 k(t, x) at m test points (any order, any
+ * position relative to the data) in O((n + m) J^2 + m log n), on a factored handle.  v_host (n): the residual r, or
+ * with v_is_alpha != 0 alpha = K^-1 r itself; only read when mean_host is given.  mean_host, var_host: m doubles each,
+ * either may be NULL.  After a failed factor both are NaN. */
+int tgp_qsep_predict(tgp_qsep* q, const double* v_host, int32_t v_is_alpha, int64_t m, const double* xtest_host,
+                     double* mean_host, double* var_host);
 
 #ifdef __cplusplus
 }

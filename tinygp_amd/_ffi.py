@@ -161,6 +161,7 @@ SIGNATURES = {
     "tgp_qsep_solve_tri": [_vp, _int, _i64, _vp, _vp],
     "tgp_qsep_dot_tri": [_vp, _i64, _vp, _vp],
     "tgp_qsep_factor_data": [_vp, _vp, _vp],
+    "tgp_qsep_predict": [_vp, _vp, _i32, _i64, _vp, _vp, _vp],
 }
 
 

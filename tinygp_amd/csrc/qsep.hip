@@ -17,14 +17,18 @@
 // L^-1 y, L^-T y and L z are affine recurrences g <- M_n g + v_n over a J-vector per right-hand side (the M_n
 // shared by all columns); they run the same three phases with element (M, V) and combine M = M2 M1, V = M2 V1 + V2.
 // A_n is regenerated from dt_n = t_n - t_{n-1} (dt_0 = 0, A = I) in every kernel instead of being stored.
+// Prediction at test points (qs_pred_*) runs two more scans of the same shape, one per direction, whose elements pair
+// a congruence recurrence X <- M X M^T + V (J x J) with an affine one f <- Mf f + Vf (J-vector); see below.
 //
 // Layout: one wavefront holds a J x J matrix (or a J x 8 block of right-hand sides) as one entry per lane,
 // lane = 8 r + c; entries outside J x J are zero.  Products read operands through __shfl.  Every reduction runs in
 // a fixed order, so results are bit-identical from run to run.  Arithmetic is fp64 throughout.
 #include "tgp_common.h"
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
+#include <vector>
 
 namespace {
 
@@ -447,6 +451,251 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_emit(int op, const QModel* 
   }
 }
 
+// ---- prediction: conditional mean and variance at test points ---------------------------------------------------
+// With alpha = K^-1 r, i the last data index with t_i <= x, A_l = A(x - t_i), A_r = A(t_{i+1} - x):
+//   forward   D_n = A_n D_{n-1} A_n^T + w_n w_n^T,             F_n = A_n F_{n-1} + P h alpha_n
+//   backward  O_n = T_n^T O_{n+1} T_n + h h^T / c_n,           B_n = A_{n+1}^T B_{n+1} + h alpha_n
+//             T_n = A_{n+1} (I - w_n h^T / sqrt c_n)   (the closed-loop map of the forward solve)
+//   q = A_l^T h,  e = P h - A_l D_i q,  e^- = A_r e
+//   mean = q^T F_i + (A_r P h)^T B_{i+1},   var = h^T P h - q^T D_i q - e^-T O_{i+1} e^-
+// Both directions are scans over elements (M, V, Mf, Vf): X <- M X M^T + V and f <- Mf f + Vf, combined as
+// (M2 M1, M2 V1 M2^T + V2, Mf2 Mf1, Mf2 Vf1 + Vf2).  f lives in column 0 of a lane-layout block.  D_n and O_n are
+// never stored: the emit pass of each direction walks its chunk once and serves the test points whose interval ends
+// (forward) or starts (backward) there.  Test points are visited in the order of their interval index; the forward
+// pass leaves (q^T F, q^T D q, e) per test point in `pt` (PT doubles each), the backward pass finishes both outputs.
+constexpr int PT = 2 + QJ;
+
+// idx[m] = (number of t_n <= x_m) - 1: the interval of x_m, -1 before the first point (NaN lands there too)
+__global__ void qs_pred_locate(const double* __restrict__ t, int64_t n, const double* __restrict__ x, int64_t m,
+                               int64_t* __restrict__ idx) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const double xv = x[j];
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (t[mid] <= xv) lo = mid + 1; else hi = mid;
+  }
+  idx[j] = lo - 1;
+}
+
+// first position p in the sorted sidx[0..m) with sidx[p] >= v
+__device__ __forceinline__ int64_t lower_bound_idx(const int64_t* sidx, int64_t m, int64_t v) {
+  int64_t lo = 0, hi = m;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (sidx[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// one forward / backward step of the pair (X, f); dir 0: step i consumes A_i, dir 1: step i consumes A_{i+1}
+struct PredStep {
+  double Phi, T, V, Vf;  // T: the congruence map (dir 0: A_i, used as T X T^T; dir 1: T_i, used as T^T X T)
+};
+
+__device__ __forceinline__ PredStep pred_step(int dir, const QModel& m, const double* t, const double* cbuf,
+                                              const double* wbuf, const double* alpha, int64_t n, int64_t i, int r,
+                                              int c, double Ph_r) {
+  PredStep s;
+  const int J = m.J;
+  const double w_r = r < J ? wbuf[i * J + r] : 0.0;
+  const double a = alpha ? alpha[i] : 0.0;
+  if (dir == 0) {
+    s.Phi = phi_entry(m, dt_at(t, i), r, c);
+    s.T = s.Phi;
+    s.V = w_r * sh(w_r, c * 8);
+    s.Vf = c == 0 ? Ph_r * a : 0.0;
+  } else {
+    s.Phi = phi_entry(m, i + 1 < n ? t[i + 1] - t[i] : 0.0, r, c);
+    const double cv = cbuf[i];
+    const double h_r = r < J ? m.h[r] : 0.0, h_c = c < J ? m.h[c] : 0.0;
+    double Aw = 0.0;
+    for (int k = 0; k < J; ++k) Aw += at(s.Phi, r, k) * sh(w_r, k * 8);
+    s.T = s.Phi - Aw * h_c / sqrt(cv);
+    s.V = h_r * h_c / cv;
+    s.Vf = c == 0 ? h_r * a : 0.0;
+  }
+  return s;
+}
+
+__device__ __forceinline__ double cong(int dir, double T, double X, int J, int r, int c) {
+  return dir == 0 ? mm_nt(mm(T, X, J, r, c), T, J, r, c) : mm_tn(T, mm(X, T, J, r, c), J, r, c);
+}
+__device__ __forceinline__ double lin(int dir, double A, double X, int J, int r, int c) {
+  return dir == 0 ? mm(A, X, J, r, c) : mm_tn(A, X, J, r, c);
+}
+
+// scan position k -> chunk and its j-th step (the backward direction walks chunks and steps from the end)
+__device__ __forceinline__ int64_t pred_index(int dir, int64_t k, int64_t nchunks, int64_t lc, int64_t n, int64_t j,
+                                              int64_t* n0, int64_t* n1) {
+  const int64_t chunk = dir ? nchunks - 1 - k : k;
+  *n0 = chunk * lc, *n1 = min(n, *n0 + lc);
+  return dir ? *n1 - 1 - j : *n0 + j;
+}
+
+__global__ __launch_bounds__(WAVE * WPB) void qs_pred_fold(int dir, int want_mean, int want_var,
+                                                           const QModel* __restrict__ mp, const double* __restrict__ t,
+                                                           const double* __restrict__ cbuf,
+                                                           const double* __restrict__ wbuf,
+                                                           const double* __restrict__ alpha, int64_t n, int64_t lc,
+                                                           int64_t nchunks, double* __restrict__ elem) {
+  const Lane L;
+  if (L.wave >= nchunks) return;
+  const QModel& m = *mp;
+  const int J = m.J, r = L.r, c = L.c;
+  const double Ph_r = Xh(m, m.P[L.lane], r);
+  const double I = (r == c && r < J) ? 1.0 : 0.0;
+  double M = I, V = 0.0, Mf = I, Vf = 0.0;
+  int64_t n0, n1;
+  pred_index(dir, L.wave, nchunks, lc, n, 0, &n0, &n1);
+  for (int64_t j = 0; j < n1 - n0; ++j) {
+    const int64_t i = pred_index(dir, L.wave, nchunks, lc, n, j, &n0, &n1);
+    const PredStep s = pred_step(dir, m, t, cbuf, wbuf, want_mean ? alpha : nullptr, n, i, r, c, Ph_r);
+    if (want_var) {
+      M = lin(dir, s.T, M, J, r, c);
+      V = symm(cong(dir, s.T, V, J, r, c) + s.V, r, c);
+    }
+    if (want_mean) {
+      Mf = lin(dir, s.Phi, Mf, J, r, c);
+      Vf = lin(dir, s.Phi, Vf, J, r, c) + s.Vf;
+    }
+  }
+  double* e = elem + L.wave * 4 * WAVE;
+  e[L.lane] = M, e[WAVE + L.lane] = V, e[2 * WAVE + L.lane] = Mf, e[3 * WAVE + L.lane] = Vf;
+}
+
+__global__ __launch_bounds__(WAVE * WPB) void qs_pred_reduce(const QModel* __restrict__ mp,
+                                                             const double* __restrict__ in, int64_t count,
+                                                             double* __restrict__ out, int64_t ngroups) {
+  const Lane L;
+  if (L.wave >= ngroups) return;
+  const int J = mp->J, r = L.r, c = L.c;
+  const int64_t b = L.wave * GROUP, e = min(count, b + GROUP);
+  const double* x = in + b * 4 * WAVE;
+  double M = x[L.lane], V = x[WAVE + L.lane], Mf = x[2 * WAVE + L.lane], Vf = x[3 * WAVE + L.lane];
+  for (int64_t i = b + 1; i < e; ++i) {
+    x = in + i * 4 * WAVE;
+    const double M2 = x[L.lane], Mf2 = x[2 * WAVE + L.lane];
+    V = symm(mm_nt(mm(M2, V, J, r, c), M2, J, r, c) + x[WAVE + L.lane], r, c);
+    M = mm(M2, M, J, r, c);
+    Vf = mm(Mf2, Vf, J, r, c) + x[3 * WAVE + L.lane];
+    Mf = mm(Mf2, Mf, J, r, c);
+  }
+  double* o = out + L.wave * 4 * WAVE;
+  o[L.lane] = M, o[WAVE + L.lane] = V, o[2 * WAVE + L.lane] = Mf, o[3 * WAVE + L.lane] = Vf;
+}
+
+// prefixes: (X, f), 2 x WAVE doubles per element; the top level starts from X = 0, f = 0
+__global__ __launch_bounds__(WAVE * WPB) void qs_pred_down(const QModel* __restrict__ mp,
+                                                           const double* __restrict__ elem, int64_t count,
+                                                           const double* __restrict__ prefix_in,
+                                                           double* __restrict__ prefix_out, int64_t ngroups) {
+  const Lane L;
+  if (L.wave >= ngroups) return;
+  const int J = mp->J, r = L.r, c = L.c;
+  double X = prefix_in ? prefix_in[L.wave * 2 * WAVE + L.lane] : 0.0;
+  double f = prefix_in ? prefix_in[L.wave * 2 * WAVE + WAVE + L.lane] : 0.0;
+  const int64_t b = L.wave * GROUP, e = min(count, b + GROUP);
+  for (int64_t i = b; i < e; ++i) {
+    prefix_out[i * 2 * WAVE + L.lane] = X, prefix_out[i * 2 * WAVE + WAVE + L.lane] = f;
+    const double* x = elem + i * 4 * WAVE;
+    const double M2 = x[L.lane], Mf2 = x[2 * WAVE + L.lane];
+    X = symm(mm_nt(mm(M2, X, J, r, c), M2, J, r, c) + x[WAVE + L.lane], r, c);
+    f = mm(Mf2, f, J, r, c) + x[3 * WAVE + L.lane];
+  }
+}
+
+// forward: the left parts of sorted test point p, whose interval starts dt before it with state (D, F)
+__device__ __forceinline__ void pred_serve_fwd(const QModel& m, double D, double F, double dt, double Ph_r, int lane,
+                                               int r, int c, double* __restrict__ pt) {
+  const int J = m.J;
+  const double Al = phi_entry(m, dt, r, c);
+  const double q_c = hT(m, Al, c);  // q = A_l^T h, by column
+  double Dq = 0.0, qDq = 0.0, u = 0.0, qF = 0.0;
+  for (int k = 0; k < J; ++k) Dq += at(D, r, k) * sh(q_c, k);
+  for (int k = 0; k < J; ++k) qDq += sh(q_c, k) * sh(Dq, k * 8);
+  for (int k = 0; k < J; ++k) u += at(Al, r, k) * sh(Dq, k * 8);
+  for (int k = 0; k < J; ++k) qF += sh(q_c, k) * sh(F, k * 8);
+  if (lane == 0) pt[0] = qF, pt[1] = qDq;
+  if (c == 0) pt[2 + r] = Ph_r - u;
+}
+
+// backward: finish sorted test point p, whose interval ends dt after it with state (O, B)
+__device__ __forceinline__ void pred_serve_bwd(const QModel& m, double O, double B, double dt, double Ph_r, double hPh,
+                                               int lane, int r, int c, const double* __restrict__ pt,
+                                               double* __restrict__ mean, double* __restrict__ var) {
+  const int J = m.J;
+  const double Ar = phi_entry(m, dt, r, c);
+  const double e_r = pt[2 + r];
+  double em = 0.0, g = 0.0, Oe = 0.0, right = 0.0, gB = 0.0;
+  for (int k = 0; k < J; ++k) em += at(Ar, r, k) * sh(e_r, k * 8);
+  for (int k = 0; k < J; ++k) g += at(Ar, r, k) * sh(Ph_r, k * 8);
+  for (int k = 0; k < J; ++k) Oe += at(O, r, k) * sh(em, k * 8);
+  for (int k = 0; k < J; ++k) right += sh(em, k * 8) * sh(Oe, k * 8);
+  for (int k = 0; k < J; ++k) gB += sh(g, k * 8) * sh(B, k * 8);
+  if (lane == 0) {
+    if (mean) *mean = pt[0] + gB;
+    if (var) *var = hPh - pt[1] - right;
+  }
+}
+
+// sidx: the test points' interval indices, sorted; order: the test point at each sorted position
+__global__ __launch_bounds__(WAVE * WPB) void qs_pred_emit(int dir, int want_mean, int want_var,
+                                                           const QModel* __restrict__ mp, const double* __restrict__ t,
+                                                           const double* __restrict__ cbuf,
+                                                           const double* __restrict__ wbuf,
+                                                           const double* __restrict__ alpha, int64_t n, int64_t lc,
+                                                           int64_t nchunks, const double* __restrict__ prefix,
+                                                           const double* __restrict__ xt,
+                                                           const int64_t* __restrict__ sidx,
+                                                           const int64_t* __restrict__ order, int64_t mt,
+                                                           double* __restrict__ pt, double* __restrict__ mean,
+                                                           double* __restrict__ var) {
+  const Lane L;
+  if (L.wave >= nchunks) return;
+  const QModel& m = *mp;
+  const int J = m.J, r = L.r, c = L.c;
+  const double Ph_r = Xh(m, m.P[L.lane], r);
+  double hPh = 0.0;
+  for (int k = 0; k < J; ++k) hPh += m.h[k] * sh(Ph_r, k * 8);
+  double X = prefix[L.wave * 2 * WAVE + L.lane], f = prefix[L.wave * 2 * WAVE + WAVE + L.lane];
+  int64_t n0, n1;
+  pred_index(dir, L.wave, nchunks, lc, n, 0, &n0, &n1);
+  if (dir == 0) {
+    // data point i serves the test points of interval i; chunk 0 also those before the first point (state 0)
+    int64_t p = L.wave == 0 ? 0 : lower_bound_idx(sidx, mt, n0);
+    for (; p < mt && sidx[p] < n0; ++p) pred_serve_fwd(m, X, f, 0.0, Ph_r, L.lane, r, c, pt + p * PT);
+    for (int64_t i = n0; i < n1; ++i) {
+      const PredStep s = pred_step(0, m, t, cbuf, wbuf, want_mean ? alpha : nullptr, n, i, r, c, Ph_r);
+      if (want_var) X = symm(cong(0, s.T, X, J, r, c) + s.V, r, c);
+      if (want_mean) f = lin(0, s.Phi, f, J, r, c) + s.Vf;
+      for (; p < mt && sidx[p] == i; ++p)
+        pred_serve_fwd(m, X, f, xt[order[p]] - t[i], Ph_r, L.lane, r, c, pt + p * PT);
+    }
+  } else {
+    // data point i serves the test points of interval i - 1; the last chunk also those of interval n - 1 (state 0)
+    int64_t p = lower_bound_idx(sidx, mt, n1 - 1);  // first position past this chunk's points
+    if (L.wave == 0) {
+      for (int64_t e = mt; e-- > p;) {
+        const int64_t o = order[e];
+        pred_serve_bwd(m, X, f, 0.0, Ph_r, hPh, L.lane, r, c, pt + e * PT, want_mean ? mean + o : nullptr,
+                       want_var ? var + o : nullptr);
+      }
+    }
+    for (int64_t i = n1 - 1; i >= n0; --i) {
+      const PredStep s = pred_step(1, m, t, cbuf, wbuf, want_mean ? alpha : nullptr, n, i, r, c, Ph_r);
+      if (want_var) X = symm(cong(1, s.T, X, J, r, c) + s.V, r, c);
+      if (want_mean) f = lin(1, s.Phi, f, J, r, c) + s.Vf;
+      for (; p > 0 && sidx[p - 1] == i - 1; --p) {
+        const int64_t o = order[p - 1];
+        pred_serve_bwd(m, X, f, t[i] - xt[o], Ph_r, hPh, L.lane, r, c, pt + (p - 1) * PT,
+                       want_mean ? mean + o : nullptr, want_var ? var + o : nullptr);
+      }
+    }
+  }
+}
+
 // one wavefront: fixed-order sums of a[0..n) and b[0..nb), minimum of bad[0..n)
 __global__ __launch_bounds__(WAVE) void qs_finish(const double* __restrict__ a, int64_t na,
                                                   const double* __restrict__ b, int64_t nb,
@@ -492,6 +741,10 @@ struct tgp_qsep {
   double* red = nullptr;   // per-chunk partial sums (2 x nchunks x ncg) + finish output
   int64_t red_elems = 0;
   int64_t* bad = nullptr;  // per-chunk first bad pivot + finish output
+  double* pred = nullptr;  // prediction: test points, per-point partial results, mean, variance
+  int64_t pred_elems = 0;
+  int64_t* pidx = nullptr;  // prediction: interval index per test point, then sorted indices and their order
+  int64_t pidx_elems = 0;
 };
 
 namespace {
@@ -515,11 +768,16 @@ std::vector<int64_t> level_sizes(int64_t count) {
   return s;
 }
 
+enum ScanKind { SCAN_RIC, SCAN_AFF, SCAN_PRED };  // Riccati (width 1), affine (M, V), prediction (M, V, Mf, Vf; width 1)
+inline int64_t scan_esz(ScanKind k) { return (k == SCAN_RIC ? 3 : k == SCAN_AFF ? 2 : 4) * WAVE; }
+inline int64_t scan_psz(ScanKind k) { return (k == SCAN_PRED ? 2 : 1) * WAVE; }
+
 // Exclusive scan over the elements already in `elem0` (esz doubles each, `width` independent scans interleaved):
-// prefixes (WAVE doubles each) of level 0 land in the returned pointer.  Work layout: per level, elements then
-// prefixes.  `ric`: Riccati elements (width 1), else affine (M, V) elements.
-int run_scan(tgp_qsep* q, hipStream_t st, bool ric, int64_t count, int64_t width, double* elem0, double** prefix0) {
-  const int64_t esz = ric ? 3 * WAVE : 2 * WAVE;
+// prefixes (psz doubles each) of level 0 land in the returned pointer.  Work layout: per level, elements then
+// prefixes.
+int run_scan(tgp_qsep* q, hipStream_t st, ScanKind kind, int64_t count, int64_t width, double* elem0,
+             double** prefix0) {
+  const int64_t esz = scan_esz(kind), psz = scan_psz(kind);
   const std::vector<int64_t> sz = level_sizes(count);
   std::vector<double*> el(sz.size()), pre(sz.size());
   el[0] = elem0;
@@ -530,20 +788,24 @@ int run_scan(tgp_qsep* q, hipStream_t st, bool ric, int64_t count, int64_t width
       cur += sz[l] * width * esz;
     }
     pre[l] = cur;
-    cur += sz[l] * width * WAVE;
+    cur += sz[l] * width * psz;
   }
   for (size_t l = 0; l + 1 < sz.size(); ++l) {
     const int64_t g = sz[l + 1];
-    if (ric)
+    if (kind == SCAN_RIC)
       qs_reduce<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], el[l + 1], g);
+    else if (kind == SCAN_PRED)
+      qs_pred_reduce<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], el[l + 1], g);
     else
       qs_aff_reduce<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, el[l + 1], g);
   }
   for (size_t l = sz.size(); l-- > 0;) {
     const int64_t g = l + 1 < sz.size() ? sz[l + 1] : 1;
     const double* pin = l + 1 < sz.size() ? pre[l + 1] : nullptr;
-    if (ric)
+    if (kind == SCAN_RIC)
       qs_down<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], pin, pre[l], g);
+    else if (kind == SCAN_PRED)
+      qs_pred_down<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], pin, pre[l], g);
     else
       qs_aff_down<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, pin, pre[l], g);
   }
@@ -552,10 +814,9 @@ int run_scan(tgp_qsep* q, hipStream_t st, bool ric, int64_t count, int64_t width
   return TGP_OK;
 }
 
-int64_t scan_work(bool ric, int64_t count, int64_t width) {
-  const int64_t esz = ric ? 3 * WAVE : 2 * WAVE;
+int64_t scan_work(ScanKind kind, int64_t count, int64_t width) {
   int64_t total = 0;
-  for (int64_t s : level_sizes(count)) total += s * width * (esz + WAVE);
+  for (int64_t s : level_sizes(count)) total += s * width * (scan_esz(kind) + scan_psz(kind));
   return total;
 }
 
@@ -590,10 +851,10 @@ int factor(tgp_qsep* q, const double* noise_host) {
   const int64_t n = q->n, nc = q->nchunks;
   TGP_ARG_CHECK(noise_host != nullptr, "null noise array");
   TGP_HIP_TRY(hipMemcpyAsync(q->noise, noise_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
-  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(true, nc, 1)));
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_RIC, nc, 1)));
   qs_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, n, q->lc, nc, q->work);
   double* prefix = nullptr;
-  TGP_TRY(run_scan(q, st, true, nc, 1, q->work, &prefix));
+  TGP_TRY(run_scan(q, st, SCAN_RIC, nc, 1, q->work, &prefix));
   qs_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, n, q->lc, nc, prefix, q->c, q->w,
                                                  q->red, q->bad);
   qs_finish<<<1, WAVE, 0, st>>>(q->red, nc, nullptr, 0, q->bad, q->red + 2 * nc, q->bad + nc);
@@ -613,11 +874,11 @@ int factor(tgp_qsep* q, const double* noise_host) {
 int affine(tgp_qsep* q, int op, int64_t nrhs, const double* y, double* out, double* sumsq) {
   hipStream_t st = q->ctx->stream;
   const int64_t n = q->n, nc = q->nchunks, ncg = ceil_div(nrhs, 8);
-  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(false, nc, ncg)));
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_AFF, nc, ncg)));
   qs_aff_fold<<<blocks_for(nc * ncg), WAVE * WPB, 0, st>>>(op, q->model, q->t, q->c, q->w, n, q->lc, nc, nrhs, ncg,
                                                             y, q->work);
   double* prefix = nullptr;
-  TGP_TRY(run_scan(q, st, false, nc, ncg, q->work, &prefix));
+  TGP_TRY(run_scan(q, st, SCAN_AFF, nc, ncg, q->work, &prefix));
   qs_aff_emit<<<blocks_for(nc * ncg), WAVE * WPB, 0, st>>>(op, q->model, q->t, q->c, q->w, n, q->lc, nc, nrhs, ncg,
                                                             prefix, y, out, sumsq ? q->red : nullptr);
   if (sumsq) {
@@ -641,6 +902,63 @@ int host_affine(tgp_qsep* q, int op, int64_t nrhs, const void* y_host, void* out
   TGP_HIP_TRY(hipMemcpyAsync(q->io, y_host, size_t(elems) * sizeof(double), hipMemcpyHostToDevice, st));
   TGP_TRY(affine(q, op, nrhs, q->io, q->io2, sumsq));
   TGP_HIP_TRY(hipMemcpyAsync(out_host, q->io2, size_t(elems) * sizeof(double), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  return TGP_OK;
+}
+
+// Conditional mean and variance at m test points.  `v_host`: the residual (alpha = K^-1 r is then computed by the two
+// solves) or, with v_is_alpha, alpha itself; only read when the mean is wanted.
+int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const double* xtest_host, double* mean_host,
+            double* var_host) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks;
+  const int want_mean = mean_host != nullptr, want_var = var_host != nullptr;
+  // pred: xt (m) | pt (m x PT) | mean (m) | var (m);  pidx: idx (m) | sidx (m) | order (m)
+  TGP_TRY(grow(&q->pred, &q->pred_elems, m * (PT + 3)));
+  if (q->pidx_elems < 3 * m) {
+    if (q->pidx) hipFree(q->pidx);
+    q->pidx = nullptr, q->pidx_elems = 0;
+    TGP_HIP_TRY(hipMalloc(&q->pidx, size_t(3 * m) * sizeof(int64_t)));
+    q->pidx_elems = 3 * m;
+  }
+  double *xt = q->pred, *pt = xt + m, *mean = pt + m * PT, *var = mean + m;
+  int64_t *idx = q->pidx, *sidx = idx + m, *order = sidx + m;
+  TGP_HIP_TRY(hipMemcpyAsync(xt, xtest_host, size_t(m) * sizeof(double), hipMemcpyHostToDevice, st));
+  qs_pred_locate<<<unsigned((m + 255) / 256), 256, 0, st>>>(q->t, n, xt, m, idx);
+  TGP_HIP_TRY(hipGetLastError());
+  const size_t um = size_t(m);
+  std::vector<int64_t> h_idx(um), h_order(um), h_sidx(um);
+  TGP_HIP_TRY(hipMemcpyAsync(h_idx.data(), idx, size_t(m) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  const double* alpha = nullptr;
+  if (want_mean) {  // alpha stays on the device, in io
+    TGP_TRY(grow(&q->io, &q->io_elems, n));
+    TGP_TRY(grow(&q->io2, &q->io2_elems, n));
+    TGP_HIP_TRY(hipMemcpyAsync(q->io, v_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+    if (!v_is_alpha) {
+      TGP_TRY(affine(q, TGP_QS_FWD, 1, q->io, q->io2, nullptr));
+      TGP_TRY(affine(q, TGP_QS_BWD, 1, q->io2, q->io, nullptr));
+    }
+    alpha = q->io;
+  }
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t j = 0; j < m; ++j) h_order[size_t(j)] = j;
+  std::stable_sort(h_order.begin(), h_order.end(),
+                   [&](int64_t a, int64_t b) { return h_idx[size_t(a)] < h_idx[size_t(b)]; });
+  for (int64_t j = 0; j < m; ++j) h_sidx[size_t(j)] = h_idx[size_t(h_order[size_t(j)])];
+  TGP_HIP_TRY(hipMemcpyAsync(sidx, h_sidx.data(), size_t(m) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  TGP_HIP_TRY(hipMemcpyAsync(order, h_order.data(), size_t(m) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_PRED, nc, 1)));
+  for (int dir = 0; dir < 2; ++dir) {
+    qs_pred_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
+                                                        n, q->lc, nc, q->work);
+    double* prefix = nullptr;
+    TGP_TRY(run_scan(q, st, SCAN_PRED, nc, 1, q->work, &prefix));
+    qs_pred_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
+                                                        n, q->lc, nc, prefix, xt, sidx, order, m, pt, mean, var);
+  }
+  TGP_HIP_TRY(hipGetLastError());
+  if (want_mean) TGP_HIP_TRY(hipMemcpyAsync(mean_host, mean, size_t(m) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (want_var) TGP_HIP_TRY(hipMemcpyAsync(var_host, var, size_t(m) * sizeof(double), hipMemcpyDeviceToHost, st));
   TGP_HIP_TRY(hipStreamSynchronize(st));
   return TGP_OK;
 }
@@ -692,7 +1010,7 @@ int tgp_qsep_destroy(tgp_qsep* q) {
     hipSetDevice(q->ctx->device);
     hipStreamSynchronize(q->ctx->stream);
   }
-  void* bufs[] = {q->model, q->t, q->noise, q->c, q->w, q->io, q->io2, q->work, q->red, q->bad};
+  void* bufs[] = {q->model, q->t, q->noise, q->c, q->w, q->io, q->io2, q->work, q->red, q->bad, q->pred, q->pidx};
   for (void* b : bufs)
     if (b) hipFree(b);
   delete q;
@@ -754,6 +1072,24 @@ int tgp_qsep_factor_data(tgp_qsep* q, double* c_host, double* w_host) {
     TGP_HIP_TRY(hipMemcpyAsync(w_host, q->w, size_t(q->n) * q->J * sizeof(double), hipMemcpyDeviceToHost, st));
   TGP_HIP_TRY(hipStreamSynchronize(st));
   return TGP_OK;
+}
+
+int tgp_qsep_predict(tgp_qsep* q, const double* v_host, int32_t v_is_alpha, int64_t m, const double* xtest_host,
+                     double* mean_host, double* var_host) {
+  QS_GUARD(q);
+  TGP_ARG_CHECK(q->factored, "the quasiseparable factor has not been computed (call tgp_qsep_factor first)");
+  TGP_ARG_CHECK(m >= 0, "negative number of test points (%lld)", (long long)m);
+  if (m == 0 || (!mean_host && !var_host)) return TGP_OK;
+  TGP_ARG_CHECK(xtest_host != nullptr, "null test points");
+  TGP_ARG_CHECK(!mean_host || v_host, "the mean needs the residual or alpha");
+  if (q->info != 0) {  // failed factor: c and w are not a factor of anything
+    for (int64_t j = 0; j < m; ++j) {
+      if (mean_host) mean_host[j] = NAN;
+      if (var_host) var_host[j] = NAN;
+    }
+    return TGP_OK;
+  }
+  return predict(q, v_host, v_is_alpha, m, xtest_host, mean_host, var_host);
 }
 
 }  // extern "C"

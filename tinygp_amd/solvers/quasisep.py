@@ -4,8 +4,9 @@ For a :class:`tinygp_amd.kernels.quasisep.Quasisep` kernel on sorted 1-D inputs,
 factor described by O(N J) numbers (``c_n``, ``w_n``; ``tests/_quasisep_np.py`` states the recursion).  A
 ``tgp_qsep`` handle (C ABI, ``include/tgp_hip.h``) keeps t, the noise and that factor resident on the device; the
 factorisation, both triangular solves and ``L @ z`` are chunked reduce-then-scan recurrences in
-``csrc/qsep.hip``.  Nothing of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
-reference).
+``csrc/qsep.hip``, and so are the conditional mean and variance at M test points (``predict_mean_var``; O(N + M),
+nothing of size N x M).  Nothing of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
+reference); the full conditional covariance and conditioning on another kernel keep the reference's dense route.
 
 dtypes: the device computes in fp64 whatever the inputs are; with fp32 inputs the results are returned as fp32
 (the Riccati recursion loses positivity quickly in fp32 arithmetic).
@@ -177,7 +178,42 @@ class QuasisepSolver(Solver):
         return out.astype(self.dtype, copy=False)
 
     def condition_variance(self, kernel, X_test):
+        if kernel is self.kernel and X_test is not None and X_test is not self.X:  # O(N + M) on the device
+            return self._predict(None, False, X_test, False, True)[1]
         return self._cond(kernel, X_test, True).astype(self.dtype, copy=False)
+
+    def conditional_mean(self, kernel, X_out, alpha):
+        """``k(X_out, X) @ alpha`` (the hook of ``GaussianProcess._kernel_matvec``): on the device in O(N + M) for
+        the solver's own kernel at test points, on the host otherwise."""
+        if kernel is self.kernel and X_out is not self.X and np.ndim(alpha) == 1:
+            return self._predict(alpha, True, X_out, True, False)[0]
+        return kernel.matmul(X_out, self.X, alpha)
+
+    # -- prediction at test points -------------------------------------------------------
+    def _predict(self, v, is_alpha, X_test, want_mean, want_var):
+        from tinygp_amd.kernels.quasisep import _coords
+
+        self._ensure_factor()
+        x = _f64(_coords(X_test))
+        m = x.shape[0]
+        vv = _f64(v, (self.n,)) if want_mean else None
+        mean = np.empty(m) if want_mean else None
+        var = np.empty(m) if want_var else None
+        if m:
+            _ffi.check(_ffi.lib().tgp_qsep_predict(self._handle, _ffi.ptr(vv), int(bool(is_alpha)), m, _ffi.ptr(x),
+                                                   _ffi.ptr(mean), _ffi.ptr(var)), "tgp_qsep_predict")
+        cast = lambda a: None if a is None else a.astype(self.dtype, copy=False)  # noqa: E731
+        return cast(mean), cast(var)
+
+    def predict_mean_var(self, resid, X_test, *, return_var: bool = True):
+        """Conditional mean ``k(X_test, X) K^-1 resid`` and variance ``k(x, x) - k(x, X) K^-1 k(X, x)`` (no noise
+        added) at M test points, in O((N + M) J^2 + M log N) on the device (``csrc/qsep.hip``, ``qs_pred_*``).
+
+        ``X_test``: shape (M,) or (M, 1), in any order and anywhere relative to the data; M = 0 is allowed.
+        Returns ``(mean, var)``, or the mean alone with ``return_var=False``.  After a failed factor both are NaN.
+        """
+        mean, var = self._predict(resid, False, X_test, True, return_var)
+        return (mean, var) if return_var else mean
 
     # -- fused entry points used by GaussianProcess ------------------------------------
     def log_probability(self, resid):
