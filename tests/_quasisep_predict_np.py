@@ -29,48 +29,52 @@ def alpha(F, r):
     return o.solve_upper(F, o.solve_lower(F, r))
 
 
-def predict(kernel, t, noise, r, xt, F=None):
+def predict(kernel, t, noise, r, xt, F=None, dtype=np.float64):
     """``(mean, var)`` at the test points ``xt`` (any order) of the GP with covariance k(t, t) + diag(noise)
-    conditioned on the residual ``r``.  ``F``: ``_quasisep_np.factor(kernel, t, noise)`` if already at hand."""
+    conditioned on the residual ``r``.  ``F``: ``_quasisep_np.factor(kernel, t, noise, dtype)`` if already at hand.
+    ``dtype``: as in ``_quasisep_np`` (the lags x - t_i are formed in float64, as the device forms them)."""
     t = np.asarray(t, dtype=np.float64)
     xt = np.asarray(xt, dtype=np.float64)
     s = kernel._ssm()
-    h, P, J, n = s.h, s.Pinf, s.J, len(t)
-    A, _, c, w = o.factor(kernel, t, noise) if F is None else F
-    a = alpha((A, h, c, w), np.asarray(r, dtype=np.float64))
+    J, n = s.J, len(t)
+    h, P = o.cast(s.h, dtype), o.cast(s.Pinf, dtype)
+    phi = kernel._phi if dtype is np.float64 else (lambda lag: o.model_transitions(s, lag, dtype))
+    zeros = lambda *shape: o.cast(np.zeros(shape), dtype)  # noqa: E731
+    A, _, c, w = o.factor(kernel, t, noise, dtype) if F is None else F
+    a = alpha((A, h, c, w), o.cast(r, dtype))
     Ph = P @ h
     idx = intervals(t, xt)
     need_left = set(idx[idx >= 0].tolist())
     need_right = set((idx[idx + 1 < n] + 1).tolist())
 
     left = {}
-    D, Fv = np.zeros((J, J)), np.zeros(J)
+    D, Fv = zeros(J, J), zeros(J)
     for i in range(n):
-        D = A[i] @ D @ A[i].T + np.outer(w[i], w[i])
+        D = A[i] @ D @ A[i].T + np.multiply.outer(w[i], w[i])
         Fv = A[i] @ Fv + Ph * a[i]
         if i in need_left:
             left[i] = (D, Fv)
 
     right = {}
-    Om, B = np.zeros((J, J)), np.zeros(J)
-    eye = np.eye(J)
+    Om, B = zeros(J, J), zeros(J)
+    eye = o.cast(np.eye(J), dtype)
     for j in range(n - 1, -1, -1):
         if j + 1 < n:
-            T = A[j + 1] @ (eye - np.outer(w[j], h) / np.sqrt(c[j]))
+            T = A[j + 1] @ (eye - np.multiply.outer(w[j], h) / o._sqrt(c[j]))
             Om = T.T @ Om @ T
             B = A[j + 1].T @ B
-        Om = Om + np.outer(h, h) / c[j]
+        Om = Om + np.multiply.outer(h, h) / c[j]
         B = B + h * a[j]
         if j in need_right:
             right[j] = (Om, B)
 
-    mean = np.zeros(len(xt))
-    var = np.full(len(xt), h @ Ph)
+    mean = zeros(len(xt))
+    var = zeros(len(xt)) + h @ Ph
     for m, (x, i) in enumerate(zip(xt, idx)):
         e = Ph
         if i >= 0:
             D, Fv = left[i]
-            Al = kernel._phi(np.asarray(x - t[i]))
+            Al = phi(np.asarray(x - t[i]))
             q = Al.T @ h
             Dq = D @ q
             mean[m] += q @ Fv
@@ -78,7 +82,7 @@ def predict(kernel, t, noise, r, xt, F=None):
             e = Ph - Al @ Dq
         if i + 1 < n:
             Om, B = right[i + 1]
-            Ar = kernel._phi(np.asarray(t[i + 1] - x))
+            Ar = phi(np.asarray(t[i + 1] - x))
             em = Ar @ e
             mean[m] += (Ar @ Ph) @ B
             var[m] -= em @ Om @ em

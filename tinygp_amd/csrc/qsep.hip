@@ -112,9 +112,16 @@ __device__ __forceinline__ double leaf_phi(int kind, const double* p, double dt,
     default: {  // SHO under- / over-damped: p = (omega, quality, f)
       const double w = p[0], q = p[1], f = p[2];
       const double arg = 0.5 * f * w * dt / q;
-      const double s = kind == TGP_QS_SHO_UNDER ? sin(arg) : sinh(arg);
-      const double co = kind == TGP_QS_SHO_UNDER ? cos(arg) : cosh(arg);
-      return exp(-0.5 * w * dt / q) * pick2(i, j, co + s / f, 2 * q * s / (w * f), -2 * q * w * s / f, co - s / f);
+      if (kind == TGP_QS_SHO_UNDER) {
+        const double s = sin(arg), co = cos(arg);
+        return exp(-0.5 * w * dt / q) * pick2(i, j, co + s / f, 2 * q * s / (w * f), -2 * q * w * s / f, co - s / f);
+      }
+      // Over-damped: with a = w dt / 2q, s = e^-a sinh(arg) and co = e^-a cosh(arg) are formed from e^-(a - arg) and
+      // e^-2arg, both <= 1 (f < 1), never as e^-a cosh(arg) = 0 * inf beyond arg ~ 710.  a - arg = 2 w q dt / (1 + f)
+      // because 1 - f^2 = 4 q^2: no cancellation for small q; expm1 keeps s accurate for small arg.
+      const double ep = exp(-2 * w * q * dt / (1 + f)), em = expm1(-2 * arg);
+      const double s = -0.5 * ep * em, co = 0.5 * ep * (2 + em);
+      return pick2(i, j, co + s / f, 2 * q * s / (w * f), -2 * q * w * s / f, co - s / f);
     }
   }
 }

@@ -482,7 +482,11 @@ class SHO(_Leaf):
             return _damped(wd, [[1 + wd, dt], [-w * wd, 1 - wd]])
         arg = 0.5 * f * w * dt / q
         if kind == QS_SHO_UNDER:
-            s, c = np.sin(arg), np.cos(arg)
+            s, c, decay = np.sin(arg), np.cos(arg), 0.5 * w * dt / q
         else:
-            s, c = np.sinh(arg), np.cosh(arg)
-        return _damped(0.5 * w * dt / q, [[c + s / f, 2 * q * s / (w * f)], [-2 * q * w * s / f, c - s / f]])
+            # with a = w dt / 2q: s = e^-a sinh(arg), c = e^-a cosh(arg) from e^-(a - arg) and e^-2arg, both <= 1
+            # (f < 1), never as e^-a cosh(arg) = 0 * inf beyond arg ~ 710.  a - arg = 2 w q dt / (1 + f) because
+            # 1 - f^2 = 4 q^2 (no cancellation for small q); expm1 keeps s accurate for small arg.
+            ep, em = np.exp(-2 * w * q * dt / (1 + f)), np.expm1(-2 * arg)
+            s, c, decay = -0.5 * ep * em, 0.5 * ep * (2 + em), np.zeros_like(dt)
+        return _damped(decay, [[c + s / f, 2 * q * s / (w * f)], [-2 * q * w * s / f, c - s / f]])
