@@ -616,6 +616,17 @@ int tgp_qsep_factor_data(tgp_qsep* q, double* c_host, double* w_host); /* c (n),
  * either may be NULL.  After a failed factor both are NaN. */
 int tgp_qsep_predict(tgp_qsep* q, const double* v_host, int32_t v_is_alpha, int64_t m, const double* xtest_host,
                      double* mean_host, double* var_host);
+/* Factor, log-probability (as tgp_qsep_factor_logprob) and its gradient in O(n J^3) per direction.  A direction is the
+ * tangent of the model along one parameter: `dleaves` (ndir x nleaves x 4: one tangent per stored leaf parameter, the
+ * dependent third parameter of an SHO included), `dh` (ndir x J), `dPinf` (ndir x J x J).  dout (ndir): the directional
+ * derivatives of the log-probability.  gnoise_host (n): its derivative with respect to every noise variance,
+ * 1/2 (alpha_n^2 - (K^-1)_nn); alpha_host (n): alpha = K^-1 r, the derivative with respect to the mean vector.  Either
+ * may be NULL, and its scan is then skipped.  Directions run in batches whose device scratch stays under 1 GiB; n (1 + J)
+ * doubles must fit it.  After a failed factor (*info != 0) dout and both vectors are NaN. */
+int tgp_qsep_grad(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t* state_map, int32_t J,
+                  const double* hvec, const double* Pinf, const double* noise_host, const double* resid_host,
+                  int32_t ndir, const double* dleaves, const double* dh, const double* dPinf, int32_t* info,
+                  double* out, double* dout, double* gnoise_host, double* alpha_host);
 
 #ifdef __cplusplus
 }

@@ -138,6 +138,95 @@ __device__ __forceinline__ double phi_entry(const QModel& m, double dt, int r, i
   return v;
 }
 
+// Tangent of the model along one parameter direction: a tangent for every stored leaf parameter (SHO's dependent f
+// included), for h and for P (padded 8 x 8).  The host forms these (kernels/quasisep.py, _ssm_tangents).
+struct QDir {
+  double dpar[QL][4];
+  double dh[QJ];
+  double dP[QJ * QJ];
+};
+
+// directional derivative of leaf_phi along dp; every term carries a factor dt, so it is 0 at dt = 0
+__device__ __forceinline__ double leaf_dphi(int kind, const double* p, const double* dp, double dt, int i, int j) {
+  switch (kind) {
+    case TGP_QS_EXP:
+      return -dt * exp(-p[0] * dt) * dp[0];
+    case TGP_QS_M32:
+    case TGP_QS_SHO_CRIT: {
+      const double f = p[0], fd = f * dt;
+      return dp[0] * dt * exp(-fd) * pick2(i, j, -fd, -dt, f * (fd - 2), fd - 2);
+    }
+    case TGP_QS_M52: {
+      const double f = p[0], f2 = f * f, fd = f * dt, d2 = dt * dt;
+      double v, vf;  // the polynomial factor of leaf_phi and its derivative with respect to f
+      switch (i * 3 + j) {
+        case 0: v = 0.5 * f2 * d2 + fd + 1, vf = f * d2 + dt; break;
+        case 1: v = dt * (fd + 1), vf = d2; break;
+        case 2: v = 0.5 * d2, vf = 0.0; break;
+        case 3: v = -0.5 * f * f2 * d2, vf = -1.5 * f2 * d2; break;
+        case 4: v = -f2 * d2 + fd + 1, vf = -2 * f * d2 + dt; break;
+        case 5: v = 0.5 * dt * (2 - fd), vf = -0.5 * d2; break;
+        case 6: v = 0.5 * f2 * f * dt * (fd - 2), vf = 2 * f2 * f * d2 - 3 * f2 * dt; break;
+        case 7: v = f2 * dt * (fd - 3), vf = 3 * f2 * d2 - 6 * fd; break;
+        default: v = 0.5 * f2 * d2 - 2 * fd + 1, vf = f * d2 - 2 * dt; break;
+      }
+      return dp[0] * exp(-fd) * (vf - dt * v);
+    }
+    case TGP_QS_COS:
+    case TGP_QS_CELERITE: {
+      const bool cosk = kind == TGP_QS_COS;
+      const double decay = cosk ? 1.0 : exp(-p[0] * dt);
+      const double a = (cosk ? p[0] : p[1]) * dt;
+      const double dom = cosk ? dp[0] : dp[1], ddec = cosk ? 0.0 : dp[0];
+      const double co = cos(a), si = sin(a);
+      return decay * dt * (dom * pick2(i, j, -si, -co, co, -si) - ddec * pick2(i, j, co, -si, si, co));
+    }
+    default: {  // SHO under- / over-damped, entries built from S = e^-a sin(h)(arg), Cc = e^-a cos(h)(arg)
+      const double w = p[0], q = p[1], f = p[2], dw = dp[0], dq = dp[1], df = dp[2];
+      const double a = 0.5 * w * dt / q, arg = f * a;
+      const double da = a * (dw / w - dq / q), darg = df * a + f * da;
+      double S, dS, dC;
+      if (kind == TGP_QS_SHO_UNDER) {
+        const double e = exp(-a), Cc = e * cos(arg);
+        S = e * sin(arg);
+        dS = -da * S + Cc * darg, dC = -da * Cc - S * darg;
+      } else {
+        // as in leaf_phi: S and Cc from e^-(a - arg) and e^-2arg, both <= 1.  dS = -da S + Cc darg is regrouped
+        // around Cc - S = e^-(a + arg) so that the two nearly equal large terms never meet: nothing overflows
+        const double ep = exp(-2 * w * q * dt / (1 + f)), em = expm1(-2 * arg);
+        const double Cc = 0.5 * ep * (2 + em), diff = ep * (1 + em), dd = da - darg;
+        S = -0.5 * ep * em;
+        dS = -dd * S + diff * darg, dC = -dd * Cc - diff * darg;
+      }
+      const double rel = df / f;
+      switch (i * 2 + j) {
+        case 0: return dC + (dS - S * rel) / f;
+        case 1: return 2 * q / (w * f) * (dS + S * (dq / q - dw / w - rel));
+        case 2: return -2 * q * w / f * (dS + S * (dq / q + dw / w - rel));
+        default: return dC - (dS - S * rel) / f;
+      }
+    }
+  }
+}
+
+// phi_entry and its tangent along d: the product rule over the leaves
+__device__ __forceinline__ void phi_entry_d(const QModel& m, const QDir& d, double dt, int r, int c, double* phi,
+                                            double* dphi) {
+  *phi = 0.0, *dphi = 0.0;
+  if (r >= m.J || c >= m.J) return;
+  double v = 1.0, dv = 0.0;
+  for (int l = 0; l < m.nleaves; ++l) {
+    const int a = m.map[r][l], b = m.map[c][l];
+    if ((a < 0) != (b < 0)) return;
+    if (a >= 0) {
+      const double f = leaf_phi(m.kind[l], m.par[l], dt, a, b);
+      dv = dv * f + v * leaf_dphi(m.kind[l], m.par[l], d.dpar[l], dt, a, b);
+      v *= f;
+    }
+  }
+  *phi = v, *dphi = dv;
+}
+
 __device__ __forceinline__ double dt_at(const double* t, int64_t n) { return n == 0 ? 0.0 : t[n] - t[n - 1]; }
 
 // row-vector h^T X (one value per column c) and X h (one value per row r)
@@ -703,6 +792,218 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_emit(int dir, int want_mea
   }
 }
 
+// ---- gradient of the log-likelihood: forward-mode tangents, one parameter direction per blockIdx.y ---------------
+// With D_n = P - P_n (P the stationary, P_n the filtered covariance; D^-_n = A_n D_{n-1} A_n^T, D_{-1} = 0) and a dot
+// for the derivative along one direction:
+//   factor   dD_n = M_n dD_{n-1} M_n^T + G_n,   M_n = (I - w_n h^T / sqrt c_n) A_n   (the closed-loop map again)
+//   solve    ds_n = M_n ds_{n-1} + u_n          (s_n the state of L^-1 r)
+// G_n and u_n are what the plain tangent of one step gives from dD_{n-1} = 0 / ds_{n-1} = 0; they depend on the primal
+// D_{n-1} / s_{n-1}, which are not stored, so fold and emit re-run the primal step from the chunk's incoming filtered
+// covariance / state (kept from the primal scans).  The factor pass writes dc_n, dw_n (n (1 + J) doubles per
+// direction) and a per-chunk sum of dc_n / c_n; the solve pass, which needs them, a per-chunk sum of z_n dz_n:
+//   d log p = -1/2 sum dc_n / c_n - sum z_n dz_n.
+// Scan elements are (M, V), `ndir` independent scans interleaved as element * ndir + direction.
+struct GStep {
+  double Phi, cv, dc, w, dw;  // w, dw: by row
+};
+
+// one step of the Riccati recursion (as qs_emit) and of its tangent: P, dD in and out
+__device__ __forceinline__ GStep gfac_step(const QModel& m, const QDir& d, const double* t, const double* noise,
+                                           int64_t i, double Pinf, double dPinf, double& P, double& dD, int r, int c) {
+  const int J = m.J;
+  GStep s;
+  double dPhi;
+  phi_entry_d(m, d, dt_at(t, i), r, c, &s.Phi, &dPhi);
+  const double N = i > 0 ? P - Pinf : 0.0;  // -D_{n-1}
+  const double Pm = symm(mm_nt(mm(s.Phi, N, J, r, c), s.Phi, J, r, c) + Pinf, r, c);
+  const double X = mm_nt(mm(dPhi, N, J, r, c), s.Phi, J, r, c);  // -dA D A^T
+  const double dPm = dPinf + X + at(X, c, r) - mm_nt(mm(s.Phi, dD, J, r, c), s.Phi, J, r, c);  // dP - dD^-
+  const double g = Xh(m, Pm, r), g_c = sh(g, c * 8);
+  double cv = noise[i], dg = 0.0, dc = 0.0;
+  for (int k = 0; k < J; ++k) cv += m.h[k] * sh(g, k * 8);
+  for (int k = 0; k < J; ++k) dg += at(dPm, r, k) * m.h[k] + at(Pm, r, k) * d.dh[k];
+  for (int k = 0; k < J; ++k) dc += d.dh[k] * sh(g, k * 8) + m.h[k] * sh(dg, k * 8);
+  const double sq = sqrt(cv);
+  s.cv = cv, s.dc = dc, s.w = g / sq;
+  s.dw = dg / sq - s.w * dc / (2 * cv);
+  P = symm(Pm - g * g_c / cv, r, c);
+  dD = symm(dPinf - dPm + s.dw * sh(s.w, c * 8) + s.w * sh(s.dw, c * 8), r, c);
+  return s;
+}
+
+__global__ __launch_bounds__(WAVE * WPB) void qs_gfac_fold(const QModel* __restrict__ mp,
+                                                           const QDir* __restrict__ dirs, const double* __restrict__ t,
+                                                           const double* __restrict__ noise, int64_t n, int64_t lc,
+                                                           int64_t nchunks, const double* __restrict__ prefixP,
+                                                           double* __restrict__ elem) {
+  const Lane L;
+  if (L.wave >= nchunks) return;
+  const QModel& m = *mp;
+  const QDir& d = dirs[blockIdx.y];
+  const int J = m.J, r = L.r, c = L.c;
+  const double Pinf = m.P[L.lane], dPinf = d.dP[L.lane];
+  double P = prefixP[L.wave * WAVE + L.lane], V = 0.0, M = (r == c && r < J) ? 1.0 : 0.0;
+  const int64_t n0 = L.wave * lc, n1 = min(n, n0 + lc);
+  for (int64_t i = n0; i < n1; ++i) {
+    const GStep s = gfac_step(m, d, t, noise, i, Pinf, dPinf, P, V, r, c);
+    const double Ms = s.Phi - s.w * hT(m, s.Phi, c) / sqrt(s.cv);
+    M = mm(Ms, M, J, r, c);
+  }
+  double* e = elem + (L.wave * gridDim.y + blockIdx.y) * 2 * WAVE;
+  e[L.lane] = M, e[WAVE + L.lane] = V;
+}
+
+// congruence scans X <- M X M^T + V over (M, V) elements, `width` of them interleaved
+__global__ __launch_bounds__(WAVE * WPB) void qs_cong_reduce(const QModel* __restrict__ mp,
+                                                             const double* __restrict__ in, int64_t count,
+                                                             int64_t width, double* __restrict__ out, int64_t ngroups) {
+  const Lane L;
+  if (L.wave >= ngroups * width) return;
+  const int J = mp->J, r = L.r, c = L.c;
+  const int64_t g = L.wave / width, d = L.wave % width;
+  const int64_t b = g * GROUP, e = min(count, b + GROUP);
+  double M = in[(b * width + d) * 2 * WAVE + L.lane], V = in[(b * width + d) * 2 * WAVE + WAVE + L.lane];
+  for (int64_t i = b + 1; i < e; ++i) {
+    const double* x = in + (i * width + d) * 2 * WAVE;
+    const double M2 = x[L.lane];
+    V = symm(mm_nt(mm(M2, V, J, r, c), M2, J, r, c) + x[WAVE + L.lane], r, c);
+    M = mm(M2, M, J, r, c);
+  }
+  double* o = out + L.wave * 2 * WAVE;
+  o[L.lane] = M, o[WAVE + L.lane] = V;
+}
+
+__global__ __launch_bounds__(WAVE * WPB) void qs_cong_down(const QModel* __restrict__ mp,
+                                                           const double* __restrict__ elem, int64_t count,
+                                                           int64_t width, const double* __restrict__ prefix_in,
+                                                           double* __restrict__ prefix_out, int64_t ngroups) {
+  const Lane L;
+  if (L.wave >= ngroups * width) return;
+  const int J = mp->J, r = L.r, c = L.c;
+  const int64_t g = L.wave / width, d = L.wave % width;
+  double X = prefix_in ? prefix_in[L.wave * WAVE + L.lane] : 0.0;
+  const int64_t b = g * GROUP, e = min(count, b + GROUP);
+  for (int64_t i = b; i < e; ++i) {
+    prefix_out[(i * width + d) * WAVE + L.lane] = X;
+    const double* x = elem + (i * width + d) * 2 * WAVE;
+    const double M2 = x[L.lane];
+    X = symm(mm_nt(mm(M2, X, J, r, c), M2, J, r, c) + x[WAVE + L.lane], r, c);
+  }
+}
+
+// dcbuf: ndir x n, dwbuf: ndir x n x J, dsum: ndir x nchunks
+__global__ __launch_bounds__(WAVE * WPB) void qs_gfac_emit(const QModel* __restrict__ mp,
+                                                           const QDir* __restrict__ dirs, const double* __restrict__ t,
+                                                           const double* __restrict__ noise, int64_t n, int64_t lc,
+                                                           int64_t nchunks, const double* __restrict__ prefixP,
+                                                           const double* __restrict__ prefixD,
+                                                           double* __restrict__ dcbuf, double* __restrict__ dwbuf,
+                                                           double* __restrict__ dsum) {
+  const Lane L;
+  if (L.wave >= nchunks) return;
+  const QModel& m = *mp;
+  const int64_t dir = blockIdx.y;
+  const QDir& d = dirs[dir];
+  const int J = m.J, r = L.r, c = L.c;
+  const double Pinf = m.P[L.lane], dPinf = d.dP[L.lane];
+  double P = prefixP[L.wave * WAVE + L.lane], dD = prefixD[(L.wave * gridDim.y + dir) * WAVE + L.lane], acc = 0.0;
+  const int64_t n0 = L.wave * lc, n1 = min(n, n0 + lc);
+  for (int64_t i = n0; i < n1; ++i) {
+    const GStep s = gfac_step(m, d, t, noise, i, Pinf, dPinf, P, dD, r, c);
+    if (L.lane == 0) dcbuf[dir * n + i] = s.dc;
+    if (c == 0 && r < J) dwbuf[(dir * n + i) * J + r] = s.dw;
+    acc += s.dc / s.cv;
+  }
+  if (L.lane == 0) dsum[dir * nchunks + L.wave] = acc;
+}
+
+// one step of L^-1 y (one column) and of its tangent; s, ds: the state by row, in and out; returns z dz
+__device__ __forceinline__ double gsol_step(const QModel& m, const QDir& d, double Phi, double dPhi, double w,
+                                            double dw, double cv, double dc, double y, double& s, double& ds, int r) {
+  const int J = m.J;
+  double f = 0.0, df = 0.0, hf = 0.0, dhf = 0.0;
+  for (int k = 0; k < J; ++k) {
+    const double s_k = sh(s, k * 8);
+    f += at(Phi, r, k) * s_k;
+    df += at(dPhi, r, k) * s_k + at(Phi, r, k) * sh(ds, k * 8);
+  }
+  for (int k = 0; k < J; ++k) {
+    const double f_k = sh(f, k * 8);
+    hf += m.h[k] * f_k;
+    dhf += d.dh[k] * f_k + m.h[k] * sh(df, k * 8);
+  }
+  const double sq = sqrt(cv), z = (y - hf) / sq, dz = -dhf / sq - z * dc / (2 * cv);
+  s = f + w * z;
+  ds = df + dw * z + w * dz;
+  return z * dz;
+}
+
+// fold (prefixS only) or emit (prefixT too) of the solve's tangent; prefixS: the primal scan's chunk states (column 0)
+__global__ __launch_bounds__(WAVE * WPB) void qs_gsol(const QModel* __restrict__ mp, const QDir* __restrict__ dirs,
+                                                      const double* __restrict__ t, const double* __restrict__ cbuf,
+                                                      const double* __restrict__ wbuf, const double* __restrict__ dcbuf,
+                                                      const double* __restrict__ dwbuf, const double* __restrict__ y,
+                                                      int64_t n, int64_t lc, int64_t nchunks,
+                                                      const double* __restrict__ prefixS,
+                                                      const double* __restrict__ prefixT, double* __restrict__ elem,
+                                                      double* __restrict__ dsum) {
+  const Lane L;
+  if (L.wave >= nchunks) return;
+  const QModel& m = *mp;
+  const int64_t dir = blockIdx.y, slot = L.wave * gridDim.y + dir;
+  const QDir& d = dirs[dir];
+  const int J = m.J, r = L.r, c = L.c;
+  const double h_r = r < J ? m.h[r] : 0.0;
+  double s = prefixS[L.wave * WAVE + r * 8], ds = prefixT ? prefixT[slot * WAVE + L.lane] : 0.0;
+  double M = (r == c && r < J) ? 1.0 : 0.0, acc = 0.0, o;
+  const int64_t n0 = L.wave * lc, n1 = min(n, n0 + lc);
+  for (int64_t i = n0; i < n1; ++i) {
+    double Phi, dPhi;
+    phi_entry_d(m, d, dt_at(t, i), r, c, &Phi, &dPhi);
+    const double w = r < J ? wbuf[i * J + r] : 0.0, dw = r < J ? dwbuf[(dir * n + i) * J + r] : 0.0;
+    const double cv = cbuf[i];
+    acc += gsol_step(m, d, Phi, dPhi, w, dw, cv, dcbuf[dir * n + i], y[i], s, ds, r);
+    if (!prefixT) M = step_apply(TGP_QS_FWD, m, StepData{Phi, w, sqrt(cv), h_r}, M, 0.0, &o, r, c);
+  }
+  if (prefixT) {
+    if (L.lane == 0) dsum[dir * nchunks + L.wave] = acc;
+  } else {
+    elem[slot * 2 * WAVE + L.lane] = M, elem[slot * 2 * WAVE + WAVE + L.lane] = ds;
+  }
+}
+
+// ---- gradient with respect to the noise: 1/2 (alpha_n^2 - (K^-1)_nn) -------------------------------------------------
+// (K^-1)_nn = (1 + u^T O_{n+1} u) / c_n, u = A_{n+1} w_n, with O the backward recurrence of the prediction (qs_pred_*,
+// dir 1, variance part): this is its emit pass with N outputs instead of test points.
+__global__ __launch_bounds__(WAVE * WPB) void qs_invdiag_emit(const QModel* __restrict__ mp,
+                                                              const double* __restrict__ t,
+                                                              const double* __restrict__ cbuf,
+                                                              const double* __restrict__ wbuf,
+                                                              const double* __restrict__ alpha, int64_t n, int64_t lc,
+                                                              int64_t nchunks, const double* __restrict__ prefix,
+                                                              double* __restrict__ out) {
+  const Lane L;
+  if (L.wave >= nchunks) return;
+  const QModel& m = *mp;
+  const int J = m.J, r = L.r, c = L.c;
+  double X = prefix[L.wave * 2 * WAVE + L.lane];
+  int64_t n0, n1;
+  pred_index(1, L.wave, nchunks, lc, n, 0, &n0, &n1);
+  for (int64_t i = n1 - 1; i >= n0; --i) {
+    const PredStep s = pred_step(1, m, t, cbuf, wbuf, nullptr, n, i, r, c, 0.0);
+    const double w_r = r < J ? wbuf[i * J + r] : 0.0;
+    double u = 0.0, Ou = 0.0, q = 0.0;
+    for (int k = 0; k < J; ++k) u += at(s.Phi, r, k) * sh(w_r, k * 8);
+    for (int k = 0; k < J; ++k) Ou += at(X, r, k) * sh(u, k * 8);
+    for (int k = 0; k < J; ++k) q += sh(u, k * 8) * sh(Ou, k * 8);
+    if (L.lane == 0) {
+      const double a = alpha[i];
+      out[i] = 0.5 * (a * a - (1.0 + q) / cbuf[i]);
+    }
+    X = symm(cong(1, s.T, X, J, r, c) + s.V, r, c);
+  }
+}
+
 // one wavefront: fixed-order sums of a[0..n) and b[0..nb), minimum of bad[0..n)
 __global__ __launch_bounds__(WAVE) void qs_finish(const double* __restrict__ a, int64_t na,
                                                   const double* __restrict__ b, int64_t nb,
@@ -752,6 +1053,10 @@ struct tgp_qsep {
   int64_t pred_elems = 0;
   int64_t* pidx = nullptr;  // prediction: interval index per test point, then sorted indices and their order
   int64_t pidx_elems = 0;
+  // gradient: chunk prefixes kept from the primal scans (filtered covariance | solve state), the directions of one
+  // batch, their dc, dw (the capped scratch), per-chunk partial sums + results, the noise gradient
+  double *gkeep = nullptr, *gdir = nullptr, *gtan = nullptr, *gred = nullptr, *gout = nullptr;
+  int64_t gkeep_elems = 0, gdir_elems = 0, gtan_elems = 0, gred_elems = 0, gout_elems = 0;
 };
 
 namespace {
@@ -775,8 +1080,9 @@ std::vector<int64_t> level_sizes(int64_t count) {
   return s;
 }
 
-enum ScanKind { SCAN_RIC, SCAN_AFF, SCAN_PRED };  // Riccati (width 1), affine (M, V), prediction (M, V, Mf, Vf; width 1)
-inline int64_t scan_esz(ScanKind k) { return (k == SCAN_RIC ? 3 : k == SCAN_AFF ? 2 : 4) * WAVE; }
+// Riccati (width 1), affine (M, V), prediction (M, V, Mf, Vf; width 1), congruence (M, V)
+enum ScanKind { SCAN_RIC, SCAN_AFF, SCAN_PRED, SCAN_CONG };
+inline int64_t scan_esz(ScanKind k) { return (k == SCAN_RIC ? 3 : k == SCAN_PRED ? 4 : 2) * WAVE; }
 inline int64_t scan_psz(ScanKind k) { return (k == SCAN_PRED ? 2 : 1) * WAVE; }
 
 // Exclusive scan over the elements already in `elem0` (esz doubles each, `width` independent scans interleaved):
@@ -803,6 +1109,8 @@ int run_scan(tgp_qsep* q, hipStream_t st, ScanKind kind, int64_t count, int64_t 
       qs_reduce<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], el[l + 1], g);
     else if (kind == SCAN_PRED)
       qs_pred_reduce<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], el[l + 1], g);
+    else if (kind == SCAN_CONG)
+      qs_cong_reduce<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, el[l + 1], g);
     else
       qs_aff_reduce<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, el[l + 1], g);
   }
@@ -813,6 +1121,8 @@ int run_scan(tgp_qsep* q, hipStream_t st, ScanKind kind, int64_t count, int64_t 
       qs_down<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], pin, pre[l], g);
     else if (kind == SCAN_PRED)
       qs_pred_down<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], pin, pre[l], g);
+    else if (kind == SCAN_CONG)
+      qs_cong_down<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, pin, pre[l], g);
     else
       qs_aff_down<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, pin, pre[l], g);
   }
@@ -853,7 +1163,8 @@ int set_model(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t*
   return TGP_OK;
 }
 
-int factor(tgp_qsep* q, const double* noise_host) {
+// keep: optional device buffer (nchunks x WAVE) that receives the chunks' incoming filtered covariances
+int factor(tgp_qsep* q, const double* noise_host, double* keep = nullptr) {
   hipStream_t st = q->ctx->stream;
   const int64_t n = q->n, nc = q->nchunks;
   TGP_ARG_CHECK(noise_host != nullptr, "null noise array");
@@ -862,6 +1173,8 @@ int factor(tgp_qsep* q, const double* noise_host) {
   qs_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, n, q->lc, nc, q->work);
   double* prefix = nullptr;
   TGP_TRY(run_scan(q, st, SCAN_RIC, nc, 1, q->work, &prefix));
+  if (keep)
+    TGP_HIP_TRY(hipMemcpyAsync(keep, prefix, size_t(nc) * WAVE * sizeof(double), hipMemcpyDeviceToDevice, st));
   qs_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, n, q->lc, nc, prefix, q->c, q->w,
                                                  q->red, q->bad);
   qs_finish<<<1, WAVE, 0, st>>>(q->red, nc, nullptr, 0, q->bad, q->red + 2 * nc, q->bad + nc);
@@ -877,8 +1190,9 @@ int factor(tgp_qsep* q, const double* noise_host) {
   return TGP_OK;
 }
 
-// out = op(y) for nrhs columns, y / out device buffers (N x nrhs, row-major); sumsq: optional sum of out^2
-int affine(tgp_qsep* q, int op, int64_t nrhs, const double* y, double* out, double* sumsq) {
+// out = op(y) for nrhs columns, y / out device buffers (N x nrhs, row-major); sumsq: optional sum of out^2;
+// keep: optional device buffer (nchunks x ncg x WAVE) that receives the chunks' incoming states
+int affine(tgp_qsep* q, int op, int64_t nrhs, const double* y, double* out, double* sumsq, double* keep = nullptr) {
   hipStream_t st = q->ctx->stream;
   const int64_t n = q->n, nc = q->nchunks, ncg = ceil_div(nrhs, 8);
   TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_AFF, nc, ncg)));
@@ -886,6 +1200,8 @@ int affine(tgp_qsep* q, int op, int64_t nrhs, const double* y, double* out, doub
                                                             y, q->work);
   double* prefix = nullptr;
   TGP_TRY(run_scan(q, st, SCAN_AFF, nc, ncg, q->work, &prefix));
+  if (keep)
+    TGP_HIP_TRY(hipMemcpyAsync(keep, prefix, size_t(nc * ncg) * WAVE * sizeof(double), hipMemcpyDeviceToDevice, st));
   qs_aff_emit<<<blocks_for(nc * ncg), WAVE * WPB, 0, st>>>(op, q->model, q->t, q->c, q->w, n, q->lc, nc, nrhs, ncg,
                                                             prefix, y, out, sumsq ? q->red : nullptr);
   if (sumsq) {
@@ -970,6 +1286,93 @@ int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const 
   return TGP_OK;
 }
 
+// Directions are processed in batches of at most GRAD_MAX_BATCH (the grid's y extent) and of at most GRAD_SCRATCH_BYTES
+// of dc, dw scratch (n (1 + J) doubles per direction), whatever the number of parameters.
+constexpr int64_t GRAD_MAX_BATCH = 8;
+constexpr int64_t GRAD_SCRATCH_BYTES = int64_t(1) << 30;
+
+// After factor() and the forward solve of the residual (q->io: r, q->io2: z; gkeep: both scans' chunk prefixes):
+// the derivative of the log-likelihood along each of ndir directions, -1/2 sum dc/c - sum z dz.
+int grad_directions(tgp_qsep* q, int32_t ndir, const double* dleaves, const double* dh, const double* dPinf,
+                    double* dout) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks, J = q->J, nl = q->host_model.nleaves;
+  const int64_t per_dir = n * (1 + J);
+  TGP_ARG_CHECK(per_dir * int64_t(sizeof(double)) <= GRAD_SCRATCH_BYTES,
+                "the gradient's scratch for one direction (n (1 + J) doubles) exceeds its cap of %lld bytes",
+                (long long)GRAD_SCRATCH_BYTES);
+  const int64_t batch =
+      std::min<int64_t>({int64_t(ndir), GRAD_MAX_BATCH, GRAD_SCRATCH_BYTES / (per_dir * int64_t(sizeof(double)))});
+  constexpr int64_t DIR_DOUBLES = sizeof(QDir) / sizeof(double);
+  TGP_TRY(grow(&q->gdir, &q->gdir_elems, batch * DIR_DOUBLES));
+  TGP_TRY(grow(&q->gtan, &q->gtan_elems, batch * per_dir));
+  TGP_TRY(grow(&q->gred, &q->gred_elems, batch * (2 * nc + 2)));
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_CONG, nc, batch)));
+  const double *prefixP = q->gkeep, *prefixS = q->gkeep + nc * WAVE;
+  const QDir* dirs = reinterpret_cast<const QDir*>(q->gdir);
+  std::vector<QDir> hd(size_t(batch), QDir{});
+  std::vector<double> sums(size_t(2 * batch));
+  for (int64_t d0 = 0; d0 < ndir; d0 += batch) {
+    const int64_t nb = std::min<int64_t>(batch, ndir - d0);
+    for (int64_t b = 0; b < nb; ++b) {
+      QDir x{};
+      const int64_t d = d0 + b;
+      for (int64_t l = 0; l < nl; ++l)
+        for (int p = 0; p < 4; ++p) x.dpar[l][p] = dleaves[(d * nl + l) * 4 + p];
+      for (int64_t r = 0; r < J; ++r) {
+        x.dh[r] = dh[d * J + r];
+        for (int64_t c = 0; c < J; ++c) x.dP[r * QJ + c] = dPinf[(d * J + r) * J + c];
+      }
+      hd[size_t(b)] = x;
+    }
+    TGP_HIP_TRY(hipMemcpyAsync(q->gdir, hd.data(), size_t(nb) * sizeof(QDir), hipMemcpyHostToDevice, st));
+    const dim3 grid(unsigned(blocks_for(nc)), unsigned(nb));
+    double *dcb = q->gtan, *dwb = q->gtan + nb * n, *dsum = q->gred, *dsum2 = q->gred + nb * nc;
+    double* res = q->gred + 2 * nb * nc;
+    double* prefix = nullptr;
+    qs_gfac_fold<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->noise, n, q->lc, nc, prefixP, q->work);
+    TGP_TRY(run_scan(q, st, SCAN_CONG, nc, nb, q->work, &prefix));
+    qs_gfac_emit<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->noise, n, q->lc, nc, prefixP, prefix, dcb, dwb,
+                                              dsum);
+    qs_gsol<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->c, q->w, dcb, dwb, q->io, n, q->lc, nc, prefixS,
+                                         nullptr, q->work, nullptr);
+    TGP_TRY(run_scan(q, st, SCAN_AFF, nc, nb, q->work, &prefix));
+    qs_gsol<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->c, q->w, dcb, dwb, q->io, n, q->lc, nc, prefixS,
+                                         prefix, nullptr, dsum2);
+    for (int64_t b = 0; b < nb; ++b)
+      qs_finish<<<1, WAVE, 0, st>>>(dsum + b * nc, nc, dsum2 + b * nc, nc, nullptr, res + 2 * b, nullptr);
+    TGP_HIP_TRY(hipGetLastError());
+    // the host vectors are reused by the next batch: wait for this one
+    TGP_HIP_TRY(hipMemcpyAsync(sums.data(), res, size_t(2 * nb) * sizeof(double), hipMemcpyDeviceToHost, st));
+    TGP_HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t b = 0; b < nb; ++b) dout[d0 + b] = -0.5 * sums[size_t(2 * b)] - sums[size_t(2 * b + 1)];
+  }
+  return TGP_OK;
+}
+
+// alpha = K^-1 r (q->io2: z -> q->io) and, when wanted, 1/2 (alpha^2 - diag K^-1)
+int grad_vectors(tgp_qsep* q, double* gnoise_host, double* alpha_host) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks;
+  TGP_TRY(affine(q, TGP_QS_BWD, 1, q->io2, q->io, nullptr));
+  if (alpha_host)
+    TGP_HIP_TRY(hipMemcpyAsync(alpha_host, q->io, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (gnoise_host) {
+    TGP_TRY(grow(&q->gout, &q->gout_elems, n));
+    TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_PRED, nc, 1)));
+    qs_pred_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(1, 0, 1, q->model, q->t, q->c, q->w, nullptr, n, q->lc, nc,
+                                                        q->work);
+    double* prefix = nullptr;
+    TGP_TRY(run_scan(q, st, SCAN_PRED, nc, 1, q->work, &prefix));
+    qs_invdiag_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->c, q->w, q->io, n, q->lc, nc, prefix,
+                                                           q->gout);
+    TGP_HIP_TRY(hipGetLastError());
+    TGP_HIP_TRY(hipMemcpyAsync(gnoise_host, q->gout, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  return TGP_OK;
+}
+
 #define QS_GUARD(q)                                                                   \
   TGP_ARG_CHECK((q) != nullptr && (q)->ctx != nullptr, "null quasiseparable handle"); \
   std::unique_lock<std::recursive_mutex> _tgp_lock((q)->ctx->mu);                     \
@@ -1017,7 +1420,8 @@ int tgp_qsep_destroy(tgp_qsep* q) {
     hipSetDevice(q->ctx->device);
     hipStreamSynchronize(q->ctx->stream);
   }
-  void* bufs[] = {q->model, q->t, q->noise, q->c, q->w, q->io, q->io2, q->work, q->red, q->bad, q->pred, q->pidx};
+  void* bufs[] = {q->model, q->t,    q->noise, q->c,     q->w,    q->io,   q->io2,  q->work, q->red,
+                  q->bad,   q->pred, q->pidx,  q->gkeep, q->gdir, q->gtan, q->gred, q->gout};
   for (void* b : bufs)
     if (b) hipFree(b);
   delete q;
@@ -1049,6 +1453,40 @@ int tgp_qsep_factor_logprob(tgp_qsep* q, const double* leaves, int32_t nleaves, 
   TGP_TRY(affine(q, TGP_QS_FWD, 1, q->io, q->io2, &zz));
   TGP_HIP_TRY(hipStreamSynchronize(st));
   *out = -0.5 * zz - 0.5 * q->logdet - 0.5 * double(q->n) * kLog2Pi;
+  return TGP_OK;
+}
+
+int tgp_qsep_grad(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t* state_map, int32_t J,
+                  const double* hvec, const double* Pinf, const double* noise_host, const double* resid_host,
+                  int32_t ndir, const double* dleaves, const double* dh, const double* dPinf, int32_t* info,
+                  double* out, double* dout, double* gnoise_host, double* alpha_host) {
+  QS_GUARD(q);
+  TGP_ARG_CHECK(resid_host && out, "null argument");
+  TGP_ARG_CHECK(ndir >= 0, "negative number of directions (%d)", ndir);
+  TGP_ARG_CHECK(ndir == 0 || (dleaves && dh && dPinf && dout), "null direction array");
+  TGP_TRY(set_model(q, leaves, nleaves, state_map, J, hvec, Pinf));
+  const int64_t n = q->n, nc = q->nchunks;
+  TGP_TRY(grow(&q->gkeep, &q->gkeep_elems, 2 * nc * WAVE));
+  TGP_TRY(factor(q, noise_host, q->gkeep));
+  if (info) *info = q->info;
+  TGP_TRY(grow(&q->io, &q->io_elems, n));
+  TGP_TRY(grow(&q->io2, &q->io2_elems, n));
+  hipStream_t st = q->ctx->stream;
+  double zz = 0.0;
+  TGP_HIP_TRY(hipMemcpyAsync(q->io, resid_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+  TGP_TRY(affine(q, TGP_QS_FWD, 1, q->io, q->io2, &zz, q->gkeep + nc * WAVE));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  *out = -0.5 * zz - 0.5 * q->logdet - 0.5 * double(n) * kLog2Pi;
+  if (q->info != 0) {  // failed factor: c and w are not a factor of anything
+    for (int32_t d = 0; d < ndir; ++d) dout[d] = NAN;
+    for (int64_t i = 0; i < n; ++i) {
+      if (gnoise_host) gnoise_host[i] = NAN;
+      if (alpha_host) alpha_host[i] = NAN;
+    }
+    return TGP_OK;
+  }
+  if (ndir > 0) TGP_TRY(grad_directions(q, ndir, dleaves, dh, dPinf, dout));
+  if (gnoise_host || alpha_host) TGP_TRY(grad_vectors(q, gnoise_host, alpha_host));
   return TGP_OK;
 }
 

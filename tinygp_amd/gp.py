@@ -150,7 +150,11 @@ class GaussianProcess:
 
     def log_probability_and_grad(self, y):
         """``(log_probability, grads)``; see :meth:`solvers.DirectSolver.log_probability_and_grad`.
-        ``grads["kernel"]`` follows ``self.kernel.parameters()``."""
+        ``grads["kernel"]`` follows ``self.kernel.parameters()``.  A solver with a ``value_and_grad`` of its own
+        (:class:`solvers.QuasisepSolver`) is differentiated through that."""
+        fused = getattr(self.solver, "value_and_grad", None)
+        if fused is not None:
+            return fused(self._residual(y))
         return self.solver.log_probability_and_grad(self._residual(y))
 
     def _residual(self, y):

@@ -33,7 +33,7 @@ from tinygp_amd.kernels import base
 from tinygp_amd.kernels.distance import L1Distance
 
 __all__ = ["Quasisep", "Sum", "Product", "Scale", "Celerite", "SHO", "Exp", "Matern32", "Matern52", "Cosine",
-           "MAX_STATE", "MAX_LEAVES"]
+           "MAX_STATE", "MAX_LEAVES", "SSMTangent", "leaf_phi", "leaf_dphi", "model_dphi"]
 
 MAX_STATE = 8   # TGP_QSEP_MAX_J of include/tgp_hip.h
 MAX_LEAVES = 8  # TGP_QSEP_MAX_LEAVES
@@ -55,6 +55,15 @@ class SSM(NamedTuple):
     @property
     def J(self) -> int:
         return len(self.h)
+
+
+class SSMTangent(NamedTuple):
+    """The derivative of an :class:`SSM` with respect to one parameter: ``dleaves`` (L, 4), one tangent per stored
+    leaf parameter (the dependent third parameter of an ``SHO`` included), ``dh`` (J,), ``dPinf`` (J, J)."""
+
+    dleaves: np.ndarray
+    dh: np.ndarray
+    dPinf: np.ndarray
 
 
 def _coords(X) -> np.ndarray:
@@ -92,6 +101,16 @@ class Quasisep(base.Kernel):
 
     def coord_to_sortable(self, X):
         return X
+
+    # -- parameters and their tangents (the gradient of QuasisepSolver.value_and_grad) --
+    def parameters(self) -> list[tuple[Any, str]]:
+        """The scalar hyper-parameters as ``(object, attribute)`` pairs in constructor order, depth first: the order
+        of the ``"kernel"`` entry of :meth:`tinygp_amd.solvers.QuasisepSolver.value_and_grad`."""
+        raise NotImplementedError
+
+    def _ssm_tangents(self) -> list[SSMTangent]:
+        """Per entry of :meth:`parameters`, the analytic derivative of :meth:`_ssm` with respect to it."""
+        raise NotImplementedError
 
     def _lower_ssm(self) -> SSM:
         """The device description; raises :class:`tinygp_amd._device.DeviceLimit` beyond J = 8 or 8 leaves."""
@@ -216,6 +235,18 @@ class Sum(Quasisep):
         return SSM(np.concatenate([s1.leaves, s2.leaves]), m, np.concatenate([s1.h, s2.h]),
                    _block_diag(s1.Pinf, s2.Pinf))
 
+    def parameters(self):
+        return self.kernel1.parameters() + self.kernel2.parameters()
+
+    def _ssm_tangents(self):
+        s1, s2 = self.kernel1._ssm(), self.kernel2._ssm()
+        z1, z2 = SSMTangent(np.zeros((len(s1.leaves), 4)), np.zeros(s1.J), np.zeros((s1.J, s1.J))), \
+            SSMTangent(np.zeros((len(s2.leaves), 4)), np.zeros(s2.J), np.zeros((s2.J, s2.J)))
+        join = lambda a, b: SSMTangent(np.concatenate([a.dleaves, b.dleaves]), np.concatenate([a.dh, b.dh]),  # noqa: E731
+                                       _block_diag(a.dPinf, b.dPinf))
+        return ([join(d, z2) for d in self.kernel1._ssm_tangents()]
+                + [join(z1, d) for d in self.kernel2._ssm_tangents()])
+
     def _phi(self, dt):
         a1, a2 = self.kernel1._phi(dt), self.kernel2._phi(dt)
         j1, j2 = a1.shape[-1], a2.shape[-1]
@@ -248,6 +279,17 @@ class Product(Quasisep):
         return SSM(np.concatenate([s1.leaves, s2.leaves]), m.astype(np.int32), np.kron(s1.h, s2.h),
                    np.kron(s1.Pinf, s2.Pinf))
 
+    def parameters(self):
+        return self.kernel1.parameters() + self.kernel2.parameters()
+
+    def _ssm_tangents(self):
+        s1, s2 = self.kernel1._ssm(), self.kernel2._ssm()
+        z1, z2 = np.zeros((len(s1.leaves), 4)), np.zeros((len(s2.leaves), 4))
+        return ([SSMTangent(np.concatenate([d.dleaves, z2]), np.kron(d.dh, s2.h), np.kron(d.dPinf, s2.Pinf))
+                 for d in self.kernel1._ssm_tangents()]
+                + [SSMTangent(np.concatenate([z1, d.dleaves]), np.kron(s1.h, d.dh), np.kron(s1.Pinf, d.dPinf))
+                   for d in self.kernel2._ssm_tangents()])
+
     def _phi(self, dt):
         a1, a2 = self.kernel1._phi(dt), self.kernel2._phi(dt)
         j1, j2 = a1.shape[-1], a2.shape[-1]
@@ -275,6 +317,14 @@ class Scale(Quasisep):
         s = self.kernel._ssm()
         return SSM(s.leaves, s.state_map, s.h, float(self.scale) * s.Pinf)
 
+    def parameters(self):
+        return self.kernel.parameters() + [(self, "scale")]
+
+    def _ssm_tangents(self):
+        s = self.kernel._ssm()
+        inner = [SSMTangent(d.dleaves, d.dh, float(self.scale) * d.dPinf) for d in self.kernel._ssm_tangents()]
+        return inner + [SSMTangent(np.zeros((len(s.leaves), 4)), np.zeros(s.J), s.Pinf.copy())]
+
     def _phi(self, dt):
         return self.kernel._phi(dt)
 
@@ -297,8 +347,18 @@ def _damped(decay, m):
     return np.exp(-decay)[..., None, None] * np.moveaxis(np.asarray(m, dtype=np.float64), (0, 1), (-2, -1))
 
 
+def _leaf_tangent(dparams, dh, dP) -> SSMTangent:
+    p = np.zeros((1, 4))
+    p[0, :len(dparams)] = dparams
+    return SSMTangent(p, np.asarray(dh, dtype=np.float64), np.asarray(dP, dtype=np.float64))
+
+
 class _Leaf(Quasisep):
     _stationary: type | None = None  # the dense leaf this kernel equals sigma^2 times, if any
+    _params: tuple = ("scale", "sigma")
+
+    def parameters(self):
+        return [(self, name) for name in self._params]
 
     def _emit(self, ops):
         if self._stationary is None:
@@ -334,6 +394,10 @@ class Exp(_Leaf):
     def _ssm(self):
         return _leaf_ssm(QS_EXP, [1.0 / float(self.scale)], [float(self.sigma)], [[1.0]])
 
+    def _ssm_tangents(self):
+        return [_leaf_tangent([-1.0 / float(self.scale) ** 2], [0.0], [[0.0]]),
+                _leaf_tangent([0.0], [1.0], [[0.0]])]
+
     def _phi(self, dt):
         return np.exp(-np.asarray(dt, dtype=np.float64) / float(self.scale))[..., None, None]
 
@@ -360,6 +424,11 @@ class Matern32(_Leaf):
     def _ssm(self):
         f = np.sqrt(3) / float(self.scale)
         return _leaf_ssm(QS_M32, [f], [float(self.sigma), 0.0], np.diag([1.0, 3.0 / float(self.scale) ** 2]))
+
+    def _ssm_tangents(self):
+        sc = float(self.scale)
+        return [_leaf_tangent([-np.sqrt(3) / sc ** 2], [0.0, 0.0], np.diag([0.0, -6.0 / sc ** 3])),
+                _leaf_tangent([0.0], [1.0, 0.0], np.zeros((2, 2)))]
 
     def _phi(self, dt):
         dt = np.asarray(dt, dtype=np.float64)
@@ -388,6 +457,12 @@ class Matern52(_Leaf):
         f2 = f * f
         P = np.array([[1.0, 0.0, -f2 / 3], [0.0, f2 / 3, 0.0], [-f2 / 3, 0.0, f2 * f2]])
         return _leaf_ssm(QS_M52, [f], [float(self.sigma), 0.0, 0.0], P)
+
+    def _ssm_tangents(self):
+        f = np.sqrt(5) / float(self.scale)
+        df = -f / float(self.scale)
+        dP = df * np.array([[0.0, 0.0, -2 * f / 3], [0.0, 2 * f / 3, 0.0], [-2 * f / 3, 0.0, 4 * f ** 3]])
+        return [_leaf_tangent([df], np.zeros(3), dP), _leaf_tangent([0.0], [1.0, 0.0, 0.0], np.zeros((3, 3)))]
 
     def _phi(self, dt):
         d = np.asarray(dt, dtype=np.float64)
@@ -418,6 +493,10 @@ class Cosine(_Leaf):
     def _ssm(self):
         return _leaf_ssm(QS_COS, [2 * np.pi / float(self.scale)], [float(self.sigma), 0.0], np.eye(2))
 
+    def _ssm_tangents(self):
+        return [_leaf_tangent([-2 * np.pi / float(self.scale) ** 2], [0.0, 0.0], np.zeros((2, 2))),
+                _leaf_tangent([0.0], [1.0, 0.0], np.zeros((2, 2)))]
+
     def _phi(self, dt):
         a = 2 * np.pi / float(self.scale) * np.asarray(dt, dtype=np.float64)
         c, s = np.cos(a), np.sin(a)
@@ -426,6 +505,8 @@ class Cosine(_Leaf):
 
 class Celerite(_Leaf):
     """exp(-c tau) [a cos(d tau) + b sin(d tau)] (reference ``quasisep.py:343-401``); needs a c - b d > 0."""
+
+    _params = ("a", "b", "c", "d")
 
     def __init__(self, a, b, c, d):
         self.a, self.b, self.c, self.d = a, b, c, d
@@ -443,6 +524,27 @@ class Celerite(_Leaf):
         P = np.array([[1.0, -c / d], [-c / d, 1 + 2 * c2 / d2]])
         return _leaf_ssm(QS_CELERITE, [c, d], [h1, h2], P)
 
+    def _ssm_tangents(self):
+        a, b, c, d = (float(v) for v in (self.a, self.b, self.c, self.d))
+        s2 = c * c + d * d
+        num, den = d * d * (a * c - b * d), 2 * c * s2  # h2^2 = num / den
+        H = num / den
+        h2 = np.sqrt(H)
+        root = np.sqrt(a * d * d - s2 * H)
+        h1 = (c * h2 - root) / d
+        # rows: d/da, d/db, d/dc, d/dd
+        dnum = np.array([d * d * c, -d ** 3, d * d * a, 2 * a * c * d - 3 * b * d * d])
+        dden = np.array([0.0, 0.0, 6 * c * c + 2 * d * d, 4 * c * d])
+        dH = dnum / den - num * dden / den ** 2
+        dh2 = dH / (2 * h2)
+        dR = np.array([d * d, 0.0, -2 * c * H, 2 * a * d - 2 * d * H]) - s2 * dH
+        dc, dd = np.array([0.0, 0.0, 1.0, 0.0]), np.array([0.0, 0.0, 0.0, 1.0])
+        dh1 = (dc * h2 + c * dh2 - dR / (2 * root)) / d - h1 * dd / d
+        dP = [np.zeros((2, 2)), np.zeros((2, 2)),
+              np.array([[0.0, -1 / d], [-1 / d, 4 * c / d ** 2]]),
+              np.array([[0.0, c / d ** 2], [c / d ** 2, -4 * c * c / d ** 3]])]
+        return [_leaf_tangent([dc[i], dd[i]], [dh1[i], dh2[i]], dP[i]) for i in range(4)]
+
     def _phi(self, dt):
         dt = np.asarray(dt, dtype=np.float64)
         c, d = float(self.c), float(self.d)
@@ -453,6 +555,8 @@ class Celerite(_Leaf):
 class SHO(_Leaf):
     """The damped, driven simple harmonic oscillator (reference ``quasisep.py:404-488``), J = 2, in its three
     regimes: quality > 1/2, == 1/2 (``np.allclose``, as the reference decides it) and < 1/2."""
+
+    _params = ("omega", "quality", "sigma")
 
     def __init__(self, omega, quality, sigma=1.0):
         self.omega, self.quality, self.sigma = omega, quality, sigma
@@ -473,6 +577,20 @@ class SHO(_Leaf):
         w = float(self.omega)
         return _leaf_ssm(kind, [w, float(self.quality), f], [float(self.sigma), 0.0], np.diag([1.0, w * w]))
 
+    def _ssm_tangents(self):
+        """A critically damped oscillator (quality 0.5) sits on the boundary between two regimes with different
+        transition formulas: it has no derivative with respect to ``quality`` there, and that entry is NaN (the
+        gradient reports NaN for it); ``omega`` and ``sigma`` are exact."""
+        kind, f = self._regime()
+        w, q = float(self.omega), float(self.quality)
+        if kind == QS_SHO_CRIT:
+            dq = [np.nan, np.nan, np.nan]
+        else:
+            dq = [0.0, 1.0, (4 * q if kind == QS_SHO_UNDER else -4 * q) / f]
+        z = np.zeros((2, 2))
+        return [_leaf_tangent([1.0, 0.0, 0.0], [0.0, 0.0], np.diag([0.0, 2 * w])),
+                _leaf_tangent(dq, [0.0, 0.0], z), _leaf_tangent([0.0], [1.0, 0.0], z)]
+
     def _phi(self, dt):
         dt = np.asarray(dt, dtype=np.float64)
         w, q = float(self.omega), float(self.quality)
@@ -490,3 +608,109 @@ class SHO(_Leaf):
             ep, em = np.exp(-2 * w * q * dt / (1 + f)), np.expm1(-2 * arg)
             s, c, decay = -0.5 * ep * em, 0.5 * ep * (2 + em), np.zeros_like(dt)
         return _damped(decay, [[c + s / f, 2 * q * s / (w * f)], [-2 * q * w * s / f, c - s / f]])
+
+
+# -- the leaf table's transitions and their tangents on the host (twins of leaf_phi / leaf_dphi in csrc/qsep.hip) --------
+def _rows(m):
+    return np.moveaxis(np.asarray(m, dtype=np.float64), (0, 1), (-2, -1))
+
+
+def _sho_modes(kind, p, dt):
+    """S = e^-a sin(h)(arg), C = e^-a cos(h)(arg) and C - S (over-damped only), a = w dt / 2Q, arg = f a."""
+    w, q, f = p[0], p[1], p[2]
+    a = 0.5 * w * dt / q
+    arg = f * a
+    if kind == QS_SHO_UNDER:
+        e = np.exp(-a)
+        return a, arg, e * np.sin(arg), e * np.cos(arg), None
+    ep, em = np.exp(-2 * w * q * dt / (1 + f)), np.expm1(-2 * arg)
+    return a, arg, -0.5 * ep * em, 0.5 * ep * (2 + em), ep * (1 + em)
+
+
+def leaf_phi(kind, p, dt):
+    """A(dt) of one row ``(kind, p)`` of the leaf table: shape ``dt.shape + (j, j)``."""
+    dt = np.asarray(dt, dtype=np.float64)
+    kind = int(kind)
+    if kind == QS_EXP:
+        return np.exp(-p[0] * dt)[..., None, None]
+    if kind in (QS_M32, QS_SHO_CRIT):
+        f, fd = p[0], p[0] * dt
+        return _damped(fd, [[1 + fd, dt], [-f * fd, 1 - fd]])
+    if kind == QS_M52:
+        f = p[0]
+        f2, fd, d2 = f * f, f * dt, dt * dt
+        return _damped(fd, [
+            [0.5 * f2 * d2 + fd + 1, dt * (fd + 1), 0.5 * d2],
+            [-0.5 * f * f2 * d2, -f2 * d2 + fd + 1, 0.5 * dt * (2 - fd)],
+            [0.5 * f2 * f * dt * (fd - 2), f2 * dt * (fd - 3), 0.5 * f2 * d2 - 2 * fd + 1]])
+    if kind in (QS_COS, QS_CELERITE):
+        decay, om = (np.zeros_like(dt), p[0]) if kind == QS_COS else (p[0] * dt, p[1])
+        co, si = np.cos(om * dt), np.sin(om * dt)
+        return _damped(decay, [[co, -si], [si, co]])
+    w, q, f = p[0], p[1], p[2]
+    _, _, S, Cc, _ = _sho_modes(kind, p, dt)
+    return _rows([[Cc + S / f, 2 * q * S / (w * f)], [-2 * q * w * S / f, Cc - S / f]])
+
+
+def leaf_dphi(kind, p, dp, dt):
+    """The derivative of :func:`leaf_phi` along the tangent ``dp`` of the row's parameters.  Every term carries a
+    factor ``dt``.  Over-damped SHO: the same ``exp(-(a - b))`` / ``expm1(-2b)`` construction as the transition, the
+    two nearly equal terms of d(e^-a sinh b) regrouped around e^-(a + b), so nothing overflows past b = 710."""
+    dt = np.asarray(dt, dtype=np.float64)
+    kind = int(kind)
+    if kind == QS_EXP:
+        return (-dt * np.exp(-p[0] * dt) * dp[0])[..., None, None]
+    if kind in (QS_M32, QS_SHO_CRIT):
+        f, fd = p[0], p[0] * dt
+        return dp[0] * _damped(fd, [[-fd * dt, -dt * dt], [f * (fd - 2) * dt, (fd - 2) * dt]])
+    if kind == QS_M52:
+        f = p[0]
+        f2, fd, d2 = f * f, f * dt, dt * dt
+        v = [[0.5 * f2 * d2 + fd + 1, dt * (fd + 1), 0.5 * d2],
+             [-0.5 * f * f2 * d2, -f2 * d2 + fd + 1, 0.5 * dt * (2 - fd)],
+             [0.5 * f2 * f * dt * (fd - 2), f2 * dt * (fd - 3), 0.5 * f2 * d2 - 2 * fd + 1]]
+        vf = [[f * d2 + dt, d2, np.zeros_like(dt)],
+              [-1.5 * f2 * d2, -2 * f * d2 + dt, -0.5 * d2],
+              [2 * f2 * f * d2 - 3 * f2 * dt, 3 * f2 * d2 - 6 * fd, f * d2 - 2 * dt]]
+        return dp[0] * _damped(fd, [[vf[i][j] - dt * v[i][j] for j in range(3)] for i in range(3)])
+    if kind in (QS_COS, QS_CELERITE):
+        decay, om, dom, ddec = (np.zeros_like(dt), p[0], dp[0], 0.0) if kind == QS_COS else (p[0] * dt, p[1], dp[1],
+                                                                                          dp[0])
+        co, si = np.cos(om * dt), np.sin(om * dt)
+        return _damped(decay, [[dt * (-dom * si - ddec * co), dt * (-dom * co + ddec * si)],
+                               [dt * (dom * co - ddec * si), dt * (-dom * si - ddec * co)]])
+    w, q, f = p[0], p[1], p[2]
+    dw, dq, df = dp[0], dp[1], dp[2]
+    a, arg, S, Cc, diff = _sho_modes(kind, p, dt)
+    da = a * (dw / w - dq / q)
+    darg = df * a + f * da
+    if kind == QS_SHO_UNDER:
+        dS, dC = -da * S + Cc * darg, -da * Cc - S * darg
+    else:
+        dd = da - darg
+        dS, dC = -dd * S + diff * darg, -dd * Cc - diff * darg
+    rel = df / f
+    return _rows([[dC + (dS - S * rel) / f, 2 * q / (w * f) * (dS + S * (dq / q - dw / w - rel))],
+                  [-2 * q * w / f * (dS + S * (dq / q + dw / w - rel)), dC - (dS - S * rel) / f]])
+
+
+def model_dphi(ssm: SSM, dleaves, dt) -> np.ndarray:
+    """The derivative of the whole model's A(dt) along ``dleaves`` (L, 4): the product rule over the leaves of the
+    term that both states belong to.  Shape ``dt.shape + (J, J)``."""
+    dt = np.asarray(dt, dtype=np.float64)
+    J = ssm.J
+    phi = [leaf_phi(row[0], row[1:], dt) for row in ssm.leaves]
+    dphi = [leaf_dphi(row[0], row[1:], d, dt) if np.any(d != 0) else None for row, d in zip(ssm.leaves, dleaves)]
+    out = np.zeros(dt.shape + (J, J))
+    for r in range(J):
+        for c in range(J):
+            a, b = ssm.state_map[r], ssm.state_map[c]
+            if np.any((a < 0) != (b < 0)):
+                continue
+            v, dv = np.ones(dt.shape), np.zeros(dt.shape)
+            for l in np.nonzero(a >= 0)[0]:
+                f = phi[l][..., a[l], b[l]]
+                dv = dv * f + (v * dphi[l][..., a[l], b[l]] if dphi[l] is not None else 0.0)
+                v = v * f
+            out[..., r, c] = dv
+    return out

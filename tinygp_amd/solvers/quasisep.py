@@ -5,7 +5,8 @@ factor described by O(N J) numbers (``c_n``, ``w_n``; ``tests/_quasisep_np.py`` 
 ``tgp_qsep`` handle (C ABI, ``include/tgp_hip.h``) keeps t, the noise and that factor resident on the device; the
 factorisation, both triangular solves and ``L @ z`` are chunked reduce-then-scan recurrences in
 ``csrc/qsep.hip``, and so are the conditional mean and variance at M test points (``predict_mean_var``; O(N + M),
-nothing of size N x M).  Nothing of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
+nothing of size N x M) and the gradient of the log-probability (``value_and_grad``; O(N) per parameter).  Nothing
+of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
 reference); the full conditional covariance and conditioning on another kernel keep the reference's dense route.
 
 dtypes: the device computes in fp64 whatever the inputs are; with fp32 inputs the results are returned as fp32
@@ -237,6 +238,52 @@ class QuasisepSolver(Solver):
         if self._info or not np.isfinite(v):
             v = -np.inf
         return a.astype(self.dtype, copy=False), self.dtype.type(v)
+
+    def value_and_grad(self, resid):
+        """``(log_probability, grads)`` with ``grads = {"kernel": [...], "noise_diag": (N,), "mean": (N,),
+        "transform": None}``, the dictionary of :meth:`DirectSolver.log_probability_and_grad`: derivatives with
+        respect to ``kernel.parameters()`` (same order), to every noise variance and to every entry of the mean
+        vector (``K^-1 r``).  Exact, forward mode, O(N J^3) per parameter on the device (``csrc/qsep.hip``,
+        ``tgp_qsep_grad``): the tangents of the factor and of the forward solve are two more scans per parameter,
+        the noise gradient one backward scan; nothing of size N x N or N x P x N is formed.
+
+        A failed factor gives ``-inf`` and NaN gradients; fp32 inputs are computed in fp64 and returned as fp32.  A
+        critically damped ``SHO`` has no derivative with respect to ``quality``: that entry is NaN."""
+        tangents = self.kernel._ssm_tangents()
+        s = self._ssm
+        ndir, L, J = len(tangents), len(s.leaves), s.J
+        dleaves, dh, dP = np.zeros((ndir, L, 4)), np.zeros((ndir, J)), np.zeros((ndir, J, J))
+        undefined = []
+        for i, t in enumerate(tangents):
+            if np.all(np.isfinite(t.dleaves)) and np.all(np.isfinite(t.dh)) and np.all(np.isfinite(t.dPinf)):
+                dleaves[i], dh[i], dP[i] = t.dleaves, t.dh, t.dPinf
+            else:
+                undefined.append(i)
+        v, kgrad, gnoise, alpha = self._grad_call(resid, dleaves, dh, dP)
+        kgrad[undefined] = np.nan
+        if self._info or not np.isfinite(v):
+            v = -np.inf
+            kgrad[:] = np.nan
+            gnoise[:] = np.nan
+            alpha[:] = np.nan
+        return self.dtype.type(v), {"kernel": [float(g) for g in kgrad],
+                                    "noise_diag": gnoise.astype(self.dtype, copy=False),
+                                    "mean": alpha.astype(self.dtype, copy=False), "transform": None}
+
+    def _grad_call(self, resid, dleaves, dh, dP, vectors: bool = True):
+        """One ``tgp_qsep_grad``: the value, the derivatives along the given directions (``dleaves`` (P, L, 4), ``dh``
+        (P, J), ``dP`` (P, J, J)) and, with ``vectors``, the noise gradient and alpha (else ``None``)."""
+        r = _f64(resid, (self.n,))
+        dleaves, dh, dP = _f64(dleaves), _f64(dh), _f64(dP)
+        ndir = dh.shape[0]
+        info, out = C.c_int32(0), C.c_double()
+        kgrad = np.zeros(ndir)
+        gnoise, alpha = (np.empty(self.n), np.empty(self.n)) if vectors else (None, None)
+        _ffi.check(_ffi.lib().tgp_qsep_grad(self._handle, *self._model_args(), _ffi.ptr(r), ndir, _ffi.ptr(dleaves),
+                                            _ffi.ptr(dh), _ffi.ptr(dP), C.byref(info), C.byref(out),
+                                            _ffi.ptr(kgrad), _ffi.ptr(gnoise), _ffi.ptr(alpha)), "tgp_qsep_grad")
+        self._info, self._factored = int(info.value), True
+        return out.value, kgrad, gnoise, alpha
 
     def log_probability_and_grad(self, resid):
         raise NotImplementedError("the gradient of the quasiseparable log-probability is not yet implemented")
