@@ -237,8 +237,9 @@ int tgp_trsv(tgp_ctx* ctx, int dtype, int64_t n, const void* L, int64_t ld, int 
              void* y);
 
 /* K5 with R right-hand sides in transposed form: B (m x n, column-major, rows = RHS
- * index) <- B L^-T, i.e. row r of B becomes (L^-1 b_r)^T.  m % 64 == 0, n % TGP_TILE == 0.
- * Replaces solve_triangular(L, Ks) at solvers/direct.py:94. */
+ * index) <- B L^-T, i.e. row r of B becomes (L^-1 b_r)^T.  m % TGP_TILE == 0, n % TGP_TILE == 0 (the
+ * updates between the 128-column solves run on the 128 x 128-tile MFMA kernel); any other m is
+ * TGP_E_ARG and B is left untouched.  Replaces solve_triangular(L, Ks) at solvers/direct.py:94. */
 int tgp_trsm_right_lt(tgp_ctx* ctx, int dtype, int64_t m, int64_t n, const void* L, int64_t ldl,
                       void* B, int64_t ldb);
 

@@ -3384,31 +3384,45 @@ __global__ __launch_bounds__(256) void tri_mirror_kernel(T* __restrict__ Zb, T* 
   for (int c = c4; c < 64; c += 4) m[int64_t(c) * ld + r] = t[r][c];
 }
 
-// upper triangle <- transpose of the lower one (n a multiple of 64), 64 x 64 per workgroup, strictly-lower blocks only
+// upper triangle <- transpose of the lower one (n a multiple of 64), 64 x 64 per workgroup: the nt (nt - 1) / 2 strictly-lower
+// blocks first, then the nt diagonal blocks (their entries above the diagonal <- the ones below it)
 template <typename T>
 __global__ __launch_bounds__(256) void symmetrize_kernel(T* __restrict__ A, int64_t ld, int nt) {
   __shared__ T t[64][65];
-  // block (bi, bj), bi > bj, from the linear index over the strict lower triangle
-  const int b = blockIdx.x;
-  int bi = int((1.0f + sqrtf(1.0f + 8.0f * float(b))) * 0.5f);
-  while ((bi * (bi - 1)) / 2 > b) --bi;
-  while (((bi + 1) * bi) / 2 <= b) ++bi;
-  const int bj = b - (bi * (bi - 1)) / 2;
+  const int b = blockIdx.x, strict = (nt * (nt - 1)) / 2;
+  int bi, bj;
+  if (b >= strict) {
+    // a diagonal block: the SYRK-shaped producer writes it in full, but folds C into entry (i, j) and into entry (j, i) at
+    // different k-steps (gemm.hip, the chunked read of C), so the two halves agree only to rounding OF THE OPERANDS --
+    // under the cancellation of Kss - A^T A that is far more than an ulp of the result
+    bi = bj = b - strict;
+  } else {
+    // block (bi, bj), bi > bj, from the linear index over the strict lower triangle
+    bi = int((1.0f + sqrtf(1.0f + 8.0f * float(b))) * 0.5f);
+    while ((bi * (bi - 1)) / 2 > b) --bi;
+    while (((bi + 1) * bi) / 2 <= b) ++bi;
+    bj = b - (bi * (bi - 1)) / 2;
+  }
   const int r = threadIdx.x & 63, c4 = threadIdx.x >> 6;
   const T* z = A + int64_t(bj) * 64 * ld + int64_t(bi) * 64;
 #pragma unroll 4
   for (int c = c4; c < 64; c += 4) t[c][r] = z[int64_t(c) * ld + r];
   __syncthreads();
   T* m = A + int64_t(bi) * 64 * ld + int64_t(bj) * 64;
+  if (bi == bj) {
 #pragma unroll 4
-  for (int c = c4; c < 64; c += 4) m[int64_t(c) * ld + r] = t[r][c];
-  // (diagonal 64 x 64 blocks: the caller's producers write them in full)
+    for (int c = c4; c < 64; c += 4)
+      if (r < c) m[int64_t(c) * ld + r] = t[r][c];
+  } else {
+#pragma unroll 4
+    for (int c = c4; c < 64; c += 4) m[int64_t(c) * ld + r] = t[r][c];
+  }
 }
 
 template <typename T>
 int symmetrize_lower(tgp_ctx* ctx, int64_t n, T* A, int64_t ld) {
   TGP_ARG_CHECK(n % 64 == 0, "symmetrize_lower: n must be a multiple of 64");
-  const int64_t nt = n / 64, blocks = nt * (nt - 1) / 2;
+  const int64_t nt = n / 64, blocks = nt * (nt - 1) / 2 + nt;
   if (blocks == 0) return TGP_OK;
   TGP_ARG_CHECK(blocks < (int64_t(1) << 31), "symmetrize_lower: too many blocks");
   hipLaunchKernelGGL((symmetrize_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, A, ld, (int)nt);
