@@ -617,6 +617,13 @@ int tgp_qsep_factor_data(tgp_qsep* q, double* c_host, double* w_host); /* c (n),
  * either may be NULL.  After a failed factor both are NaN. */
 int tgp_qsep_predict(tgp_qsep* q, const double* v_host, int32_t v_is_alpha, int64_t m, const double* xtest_host,
                      double* mean_host, double* var_host);
+/* The same for each of nterms (1..8) terms of a sum at once: g_host (nterms x J, row-major) holds per term the test-side
+ * observation vector, h masked to the states of the addends that make the term up (g = h: the whole kernel, as
+ * tgp_qsep_predict).  Row k of mean_host / var_host (nterms x m each, either may be NULL) is k_g(x, t) K^-1 r and
+ * k_g(x, x) - k_g(x, t) K^-1 k_g(t, x) with K the whole model's.  The scans are shared: K terms cost one pair, not K.
+ * xtest_host == NULL: the test points are the data points themselves (m must equal n); nothing is uploaded or sorted. */
+int tgp_qsep_predict_terms(tgp_qsep* q, const double* v_host, int32_t v_is_alpha, int64_t m, const double* xtest_host,
+                           int32_t nterms, const double* g_host, double* mean_host, double* var_host);
 /* Factor, log-probability (as tgp_qsep_factor_logprob) and its gradient in O(n J^3) per direction.  A direction is the
  * tangent of the model along one parameter: `dleaves` (ndir x nleaves x 4: one tangent per stored leaf parameter, the
  * dependent third parameter of an SHO included), `dh` (ndir x J), `dPinf` (ndir x J x J).  dout (ndir): the directional

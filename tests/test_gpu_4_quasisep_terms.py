@@ -1,0 +1,263 @@
+"""Conditional mean and variance of each term of a quasiseparable sum in O(N + K M) on the device
+(``QuasisepSolver.predict_terms``, ``GaussianProcess.predict_terms``) against dense LAPACK, the sequential oracle with
+the test-side vector g, and ``predict_mean_var``.
+
+The bar is the project's posterior bar, rtol = atol = 5e-7 (README "Parity"), for kernels of amplitude O(1)."""
+import numpy as np
+import pytest
+
+from tinygp_amd import GaussianProcess
+from tinygp_amd.kernels import quasisep as q
+from tinygp_amd.noise import Diagonal
+from tinygp_amd.solvers import DirectSolver, QuasisepSolver
+
+import _quasisep_terms_np as tn
+from _quasisep_cases import CASES
+
+pytestmark = pytest.mark.gpu
+
+BAR = dict(rtol=5e-7, atol=5e-7)
+LC = 16  # chunk length below 65 536 points
+
+
+def _series(n, seed=0):
+    rng = np.random.default_rng(seed)
+    t = np.sort(rng.uniform(0, 0.05 * n + 1, n))
+    return t, rng.uniform(0.05, 0.2, n), rng.standard_normal(n)
+
+
+def _test_points(t, m, seed, lc=LC):
+    """Unsorted; outside the range on both sides, on data points (tied ones too), in the first and the last chunk
+    and exactly on the data points either side of chunk boundaries."""
+    rng = np.random.default_rng(seed)
+    n = len(t)
+    edges = np.unique(np.clip(np.concatenate([np.arange(lc - 1, n, lc), np.arange(lc, n, lc), [0, n - 1]]), 0, n - 1))
+    edges = edges[rng.permutation(len(edges))[:60]]
+    special = np.concatenate([
+        t[edges], t[[0, n - 1]], t[:3], t[-3:],
+        rng.uniform(t[0], t[min(lc, n) - 1], 8),            # inside the first chunk
+        rng.uniform(t[max(0, n - lc // 2)], t[-1], 8),      # inside the last chunk
+        t[0] - rng.uniform(0, 3, 6), t[-1] + rng.uniform(0, 3, 6), [t[0] - 40.0, t[-1] + 40.0],
+    ])
+    xt = np.concatenate([rng.uniform(t[0] - 1, t[-1] + 1, max(0, m - len(special))), special])
+    return xt[rng.permutation(len(xt))]
+
+
+def _tied(n, seed):
+    t, noise, r = _series(n, seed)
+    t[7] = t[6]
+    t[LC] = t[LC - 1]  # a tie across a chunk boundary
+    return t, noise, r
+
+
+MODELS = {
+    "m32cos_plus_sho": lambda: CASES["m32cos_plus_sho"](q),
+    "celerite4": lambda: CASES["celerite4"](q),
+    # (Matern32 + 0.8 SHO) + Matern52 x Cosine has J = 2 + 2 + 6 = 10, beyond the device's J <= 8.  Two models of J = 8
+    # keep each of its parts: the nested sum with a Scale beside a Product, and the 3 x 2 Kronecker product.
+    "m32_scaled_sho_plus_m32cos": lambda: ((q.Matern32(scale=1.5) + 0.8 * q.SHO(omega=2.0, quality=3.0))
+                                           + q.Matern32(scale=2.0) * q.Cosine(scale=3.0)),
+    "exp_scaled_exp_plus_m52cos": lambda: ((q.Exp(scale=1.3, sigma=0.7) + 0.8 * q.Exp(scale=0.4))
+                                           + q.Matern52(scale=2.0) * q.Cosine(scale=3.0)),
+}
+
+
+def _selectors(k):
+    """Every top-level term, one union of two terms, the whole kernel."""
+    terms = k._addends()
+    return terms + [terms[0] + terms[-1], k]
+
+
+def _check_rows(tag, model, selectors, t, noise, r, xt, means, vars_):
+    assert means.shape == vars_.shape == (len(selectors), len(xt))
+    for j, k in enumerate(selectors):
+        wmean, wvar = tn.dense_term(model, k, t, noise, r, xt)
+        print(f"{tag} row {j}: max |mean - ref| = {np.abs(means[j] - wmean).max():.3e}, max |var - ref| = "
+              f"{np.abs(vars_[j] - wvar).max():.3e}, min var = {wvar.min():.3e}")
+        np.testing.assert_allclose(means[j], wmean, **BAR)
+        np.testing.assert_allclose(vars_[j], wvar, **BAR)
+
+
+@pytest.mark.parametrize("n", [515, 1999])
+@pytest.mark.parametrize("name", sorted(MODELS))
+def test_vs_dense(name, n):
+    k = MODELS[name]()
+    t, noise, r = _tied(n, seed=n + len(name))
+    xt = np.concatenate([_test_points(t, 300, seed=n), t[[6, 7, LC - 1, LC]]])
+    sel = _selectors(k)
+    means, vars_ = QuasisepSolver(k, t, Diagonal(noise)).predict_terms(r, xt, sel)
+    assert means.dtype == vars_.dtype == np.float64
+    _check_rows(f"{name} n={n}", k, sel, t, noise, r, xt, means, vars_)
+
+
+@pytest.mark.parametrize("name", sorted(MODELS))
+def test_whole_kernel_equals_predict_mean_var_and_means_add_up(name):
+    k = MODELS[name]()
+    t, noise, r = _tied(1999, seed=3)
+    xt = _test_points(t, 300, seed=4)
+    s = QuasisepSolver(k, t, Diagonal(noise))
+    mean, var = s.predict_mean_var(r, xt)
+    wmeans, wvars = s.predict_terms(r, xt, [k])
+    assert wmeans.shape == wvars.shape == (1, len(xt))
+    assert np.array_equal(wmeans[0], mean) and np.array_equal(wvars[0], var)  # bit for bit
+    means, _ = s.predict_terms(r, xt)  # kernels=None: the top-level addends
+    assert means.shape == (len(k._addends()), len(xt))
+    err = np.abs(means.sum(axis=0) - mean).max()
+    print(f"{name}: |sum of term means - mean| = {err:.3e}")
+    assert err <= 1e-12 * (1 + np.abs(mean).max())
+
+
+def test_non_sum_kernel_is_its_own_term():
+    k = CASES["matern32"](q)
+    t, noise, r = _tied(515, seed=5)
+    xt = _test_points(t, 100, seed=6)
+    s = QuasisepSolver(k, t, Diagonal(noise))
+    means, vars_ = s.predict_terms(r, xt)
+    mean, var = s.predict_mean_var(r, xt)
+    assert means.shape == (1, len(xt))
+    assert np.array_equal(means[0], mean) and np.array_equal(vars_[0], var)
+
+
+def test_no_test_points_is_the_data():
+    k = MODELS["m32_scaled_sho_plus_m32cos"]()
+    t, noise, r = _tied(1999, seed=7)
+    sel = _selectors(k)
+    s = QuasisepSolver(k, t, Diagonal(noise))
+    means, vars_ = s.predict_terms(r, None, sel)
+    emeans, evars = s.predict_terms(r, t.copy(), sel)
+    assert np.array_equal(means, emeans) and np.array_equal(vars_, evars)  # bit for bit, ties included
+    _check_rows("X_test=None n=1999", k, sel, t, noise, r, t, means, vars_)
+    gmeans = GaussianProcess(k, t, noise=Diagonal(noise)).predict_terms(r, kernels=sel)
+    assert np.array_equal(gmeans, means)
+
+
+def test_batching_does_not_matter():
+    """J = 8 and eight terms, the cap of one device call; eleven selectors take two."""
+    terms = [q.Exp(scale=0.3 * 1.7 ** j, sigma=0.5 + 0.1 * j) for j in range(8)]
+    k = terms[0]
+    for term in terms[1:]:
+        k = k + term
+    assert k._ssm().J == 8 and k._addends() == terms
+    t, noise, r = _tied(515, seed=8)
+    xt = _test_points(t, 200, seed=9)
+    s = QuasisepSolver(k, t, Diagonal(noise))
+    means, vars_ = s.predict_terms(r, xt)
+    assert means.shape == vars_.shape == (8, len(xt))
+    for j, term in enumerate(terms):
+        m1, v1 = s.predict_terms(r, xt, [term])
+        assert np.array_equal(m1[0], means[j]) and np.array_equal(v1[0], vars_[j])
+    sel = terms + [terms[0] + terms[7], terms[2] + terms[3], (terms[1] + terms[4]) + terms[6]]
+    means11, vars11 = s.predict_terms(r, xt, sel)
+    assert means11.shape == vars11.shape == (11, len(xt))
+    assert np.array_equal(means11[:8], means) and np.array_equal(vars11[:8], vars_)
+    _check_rows("8 x Exp", k, sel, t, noise, r, xt, means11, vars11)
+
+
+@pytest.mark.parametrize("n", [1, 2, 16, 17])
+def test_tiny_series(n):
+    k = MODELS["m32cos_plus_sho"]()
+    t, noise, r = _series(n, seed=n)
+    xt = np.concatenate([t, [t[0] - 0.5, t[-1] + 0.5, 0.5 * (t[0] + t[-1])]])
+    sel = _selectors(k)
+    s = QuasisepSolver(k, t, Diagonal(noise))
+    means, vars_ = s.predict_terms(r, xt, sel)
+    _check_rows(f"tiny n={n}", k, sel, t, noise, r, xt, means, vars_)
+    dmeans, dvars = s.predict_terms(r, None, sel)
+    _check_rows(f"tiny n={n}, at the data", k, sel, t, noise, r, t, dmeans, dvars)
+
+
+def test_skipped_phases_and_repeats():
+    k = MODELS["celerite4"]()
+    t, noise, r = _tied(1999, seed=10)
+    xt = _test_points(t, 300, seed=11)
+    s = QuasisepSolver(k, t, Diagonal(noise))
+    a = s.predict_terms(r, xt)
+    b = s.predict_terms(r, xt)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    only = s.predict_terms(r, xt, return_var=False)
+    assert isinstance(only, np.ndarray) and np.array_equal(only, a[0])
+    assert np.array_equal(s.predict_terms(r, xt[:, None], return_var=False), a[0])  # (M, 1) input
+    gp = GaussianProcess(k, t, noise=Diagonal(noise))
+    assert np.array_equal(gp.predict_terms(r, xt), a[0])  # the means alone by default
+    gm, gv = gp.predict_terms(r, xt, return_var=True)
+    assert np.array_equal(gm, a[0]) and np.array_equal(gv, a[1])  # no jitter, no mean function
+    assert s.predict_terms(r, np.zeros(0))[0].shape == (4, 0)
+
+
+def test_mean_function_enters_through_the_residual_only():
+    k = MODELS["m32cos_plus_sho"]()
+    t, noise, y = _tied(515, seed=12)
+    xt = _test_points(t, 100, seed=13)
+    gp = GaussianProcess(k, t, noise=Diagonal(noise), mean=1.5)
+    want = QuasisepSolver(k, t, Diagonal(noise)).predict_terms(y - 1.5, xt, return_var=False)
+    assert np.array_equal(gp.predict_terms(y, xt), want)
+
+
+def test_fp32():
+    k = MODELS["m32cos_plus_sho"]()
+    t, noise, r = _series(3000, seed=4)
+    t32, n32, r32 = t.astype(np.float32), noise.astype(np.float32), r.astype(np.float32)
+    xt32 = _test_points(t32.astype(np.float64), 300, seed=5).astype(np.float32)
+    means, vars_ = QuasisepSolver(k, t32, Diagonal(n32)).predict_terms(r32, xt32)
+    assert means.dtype == vars_.dtype == np.float32 and means.shape == (2, len(xt32))
+    f64 = lambda a: a.astype(np.float64)  # noqa: E731
+    wmeans, wvars = QuasisepSolver(k, f64(t32), Diagonal(f64(n32))).predict_terms(f64(r32), f64(xt32))
+    assert wmeans.dtype == np.float64
+    np.testing.assert_allclose(means, wmeans, rtol=5e-4, atol=5e-4)
+    np.testing.assert_allclose(vars_, wvars, rtol=5e-4, atol=5e-4)
+
+
+def test_failed_factor_gives_nan():
+    k = MODELS["m32cos_plus_sho"]()
+    t, noise, r = _series(300, seed=6)
+    noise[100:] = -5.0
+    s = QuasisepSolver(k, t, Diagonal(noise))
+    means, vars_ = s.predict_terms(r, np.linspace(-1, 20, 50))
+    assert s.info == 101
+    assert means.shape == vars_.shape == (2, 50)
+    assert np.all(np.isnan(means)) and np.all(np.isnan(vars_))
+    dmeans, dvars = s.predict_terms(r)
+    assert dmeans.shape == (2, 300) and np.all(np.isnan(dmeans)) and np.all(np.isnan(dvars))
+
+
+def test_errors():
+    m32, cos, sho = q.Matern32(scale=1.5), q.Cosine(scale=3.0), q.SHO(omega=2.0, quality=3.0)
+    k = m32 * cos + 0.8 * sho
+    t, noise, r = _series(100, seed=14)
+    s = QuasisepSolver(k, t, Diagonal(noise))
+    for bad in (m32, sho, q.Matern32(scale=1.5) * q.Cosine(scale=3.0)):  # Product factor, inside a Scale, a copy
+        with pytest.raises(ValueError, match="not a term"):
+            s.predict_terms(r, t, [k.kernel1, bad])
+    dense = q.Matern32(scale=1.5) + q.Exp(scale=0.7)
+    gd = GaussianProcess(dense, t, noise=Diagonal(noise), solver=DirectSolver)
+    with pytest.raises(TypeError, match="predict_terms"):
+        gd.predict_terms(r)
+
+
+def test_at_the_data_forms_no_dense_host_matrix(monkeypatch):
+    """N = 2^17 at the data, both terms, mean and variance, with the dense host kernel forbidden."""
+    n = 1 << 17
+    k = MODELS["m32cos_plus_sho"]()
+    t, _, y = _series(n, seed=15)
+    t[7] = t[6]
+    noise = np.full(n, 1e-2)
+
+    def forbidden(self, X1, X2):
+        raise AssertionError(f"dense host kernel matrix {np.shape(X1)} x {np.shape(X2)} requested")
+
+    monkeypatch.setattr(q.Quasisep, "_host_matrix", forbidden)
+    gp = GaussianProcess(k, t, diag=1e-2, assume_sorted=True)
+    means, vars_ = gp.predict_terms(y, return_var=True)
+    assert means.shape == vars_.shape == (2, n)
+    assert np.all(np.isfinite(means)) and np.all(np.isfinite(vars_))
+    # the terms add up to the model's own mean at the data, y - noise * alpha: O(N)
+    alpha, _ = gp.solver.alpha(y)
+    np.testing.assert_allclose(means.sum(axis=0), y - noise * alpha, **BAR)
+    # 64 sampled points against the sequential oracle (one pass over the data for both terms)
+    sample = np.sort(np.concatenate([[0, 6, 7, n - 1], np.random.default_rng(16).choice(n, 60, replace=False)]))
+    g = np.stack([k._term_vector(term) for term in k._addends()])
+    wmeans, wvars = tn.predict_g(k, t, noise, y, t[sample], g)
+    print(f"n=2^17 at the data: max |mean - oracle| = {np.abs(means[:, sample] - wmeans).max():.3e}, "
+          f"max |var - oracle| = {np.abs(vars_[:, sample] - wvars).max():.3e}")
+    np.testing.assert_allclose(means[:, sample], wmeans, **BAR)
+    np.testing.assert_allclose(vars_[:, sample], wvars, **BAR)

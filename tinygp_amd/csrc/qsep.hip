@@ -558,7 +558,7 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_emit(int op, const QModel* 
 // (M2 M1, M2 V1 M2^T + V2, Mf2 Mf1, Mf2 Vf1 + Vf2).  f lives in column 0 of a lane-layout block.  D_n and O_n are
 // never stored: the emit pass of each direction walks its chunk once and serves the test points whose interval ends
 // (forward) or starts (backward) there.  Test points are visited in the order of their interval index; the forward
-// pass leaves (q^T F, q^T D q, e) per test point in `pt` (PT doubles each), the backward pass finishes both outputs.
+// pass leaves (q^T F, q^T D q, e) per test point and term in `pt` (PT doubles each), the backward pass finishes both outputs.
 constexpr int PT = 2 + QJ;
 
 // idx[m] = (number of t_n <= x_m) - 1: the interval of x_m, -1 before the first point (NaN lands there too)
@@ -573,6 +573,15 @@ __global__ void qs_pred_locate(const double* __restrict__ t, int64_t n, const do
     if (t[mid] <= xv) lo = mid + 1; else hi = mid;
   }
   idx[j] = lo - 1;
+}
+
+// the test points are the sorted data themselves: their intervals are already non-decreasing, the order is the identity
+__global__ void qs_pred_identity(const int64_t* __restrict__ idx, int64_t m, int64_t* __restrict__ sidx,
+                                 int64_t* __restrict__ order) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  sidx[j] = idx[j];
+  order[j] = j;
 }
 
 // first position p in the sorted sidx[0..m) with sidx[p] >= v
@@ -702,41 +711,58 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_down(const QModel* __restr
   }
 }
 
-// forward: the left parts of sorted test point p, whose interval starts dt before it with state (D, F)
-__device__ __forceinline__ void pred_serve_fwd(const QModel& m, double D, double F, double dt, double Ph_r, int lane,
-                                               int r, int c, double* __restrict__ pt) {
+// The test side of both serves is a J-vector g per term (gv: nterms x 8 doubles, rows zero-padded, wave-uniform
+// loads): g = h is the model's own kernel, h masked to the states of some addends of a sum is those addends' kernel.
+// Only the gathers below depend on g; D, F, O and B are driven by the data-side h whatever the term.
+// forward: the left parts of sorted test point p, whose interval starts dt before it with state (D, F); Pl: this
+// lane's entry of P; pt: nterms x PT
+__device__ __forceinline__ void pred_serve_fwd(const QModel& m, const double* __restrict__ gv, int nterms, double D,
+                                               double F, double dt, double Pl, int lane, int r, int c,
+                                               double* __restrict__ pt) {
   const int J = m.J;
   const double Al = phi_entry(m, dt, r, c);
-  const double q_c = hT(m, Al, c);  // q = A_l^T h, by column
-  double Dq = 0.0, qDq = 0.0, u = 0.0, qF = 0.0;
-  for (int k = 0; k < J; ++k) Dq += at(D, r, k) * sh(q_c, k);
-  for (int k = 0; k < J; ++k) qDq += sh(q_c, k) * sh(Dq, k * 8);
-  for (int k = 0; k < J; ++k) u += at(Al, r, k) * sh(Dq, k * 8);
-  for (int k = 0; k < J; ++k) qF += sh(q_c, k) * sh(F, k * 8);
-  if (lane == 0) pt[0] = qF, pt[1] = qDq;
-  if (c == 0) pt[2 + r] = Ph_r - u;
-}
-
-// backward: finish sorted test point p, whose interval ends dt after it with state (O, B)
-__device__ __forceinline__ void pred_serve_bwd(const QModel& m, double O, double B, double dt, double Ph_r, double hPh,
-                                               int lane, int r, int c, const double* __restrict__ pt,
-                                               double* __restrict__ mean, double* __restrict__ var) {
-  const int J = m.J;
-  const double Ar = phi_entry(m, dt, r, c);
-  const double e_r = pt[2 + r];
-  double em = 0.0, g = 0.0, Oe = 0.0, right = 0.0, gB = 0.0;
-  for (int k = 0; k < J; ++k) em += at(Ar, r, k) * sh(e_r, k * 8);
-  for (int k = 0; k < J; ++k) g += at(Ar, r, k) * sh(Ph_r, k * 8);
-  for (int k = 0; k < J; ++k) Oe += at(O, r, k) * sh(em, k * 8);
-  for (int k = 0; k < J; ++k) right += sh(em, k * 8) * sh(Oe, k * 8);
-  for (int k = 0; k < J; ++k) gB += sh(g, k * 8) * sh(B, k * 8);
-  if (lane == 0) {
-    if (mean) *mean = pt[0] + gB;
-    if (var) *var = hPh - pt[1] - right;
+  for (int term = 0; term < nterms; ++term, gv += QJ, pt += PT) {
+    double Pg_r = 0.0, q_c = 0.0;  // P g by row; q = A_l^T g, by column
+    for (int k = 0; k < J; ++k) Pg_r += at(Pl, r, k) * gv[k];
+    for (int k = 0; k < J; ++k) q_c += gv[k] * at(Al, k, c);
+    double Dq = 0.0, qDq = 0.0, u = 0.0, qF = 0.0;
+    for (int k = 0; k < J; ++k) Dq += at(D, r, k) * sh(q_c, k);
+    for (int k = 0; k < J; ++k) qDq += sh(q_c, k) * sh(Dq, k * 8);
+    for (int k = 0; k < J; ++k) u += at(Al, r, k) * sh(Dq, k * 8);
+    for (int k = 0; k < J; ++k) qF += sh(q_c, k) * sh(F, k * 8);
+    if (lane == 0) pt[0] = qF, pt[1] = qDq;
+    if (c == 0) pt[2 + r] = Pg_r - u;
   }
 }
 
-// sidx: the test points' interval indices, sorted; order: the test point at each sorted position
+// backward: finish sorted test point p, whose interval ends dt after it with state (O, B); term k's outputs land
+// `stride` after term k - 1's
+__device__ __forceinline__ void pred_serve_bwd(const QModel& m, const double* __restrict__ gv, int nterms, double O,
+                                               double B, double dt, double Pl, int lane, int r, int c,
+                                               const double* __restrict__ pt, double* __restrict__ mean,
+                                               double* __restrict__ var, int64_t stride) {
+  const int J = m.J;
+  const double Ar = phi_entry(m, dt, r, c);
+  for (int term = 0; term < nterms; ++term, gv += QJ, pt += PT) {
+    double Pg_r = 0.0, gPg = 0.0;
+    for (int k = 0; k < J; ++k) Pg_r += at(Pl, r, k) * gv[k];
+    for (int k = 0; k < J; ++k) gPg += gv[k] * sh(Pg_r, k * 8);
+    const double e_r = pt[2 + r];
+    double em = 0.0, g = 0.0, Oe = 0.0, right = 0.0, gB = 0.0;
+    for (int k = 0; k < J; ++k) em += at(Ar, r, k) * sh(e_r, k * 8);
+    for (int k = 0; k < J; ++k) g += at(Ar, r, k) * sh(Pg_r, k * 8);
+    for (int k = 0; k < J; ++k) Oe += at(O, r, k) * sh(em, k * 8);
+    for (int k = 0; k < J; ++k) right += sh(em, k * 8) * sh(Oe, k * 8);
+    for (int k = 0; k < J; ++k) gB += sh(g, k * 8) * sh(B, k * 8);
+    if (lane == 0) {
+      if (mean) mean[term * stride] = pt[0] + gB;
+      if (var) var[term * stride] = gPg - pt[1] - right;
+    }
+  }
+}
+
+// sidx: the test points' interval indices, sorted; order: the test point at each sorted position; gv: the nterms
+// test-side vectors; pt: mt x nterms x PT; mean, var: nterms x mt
 __global__ __launch_bounds__(WAVE * WPB) void qs_pred_emit(int dir, int want_mean, int want_var,
                                                            const QModel* __restrict__ mp, const double* __restrict__ t,
                                                            const double* __restrict__ cbuf,
@@ -746,28 +772,29 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_emit(int dir, int want_mea
                                                            const double* __restrict__ xt,
                                                            const int64_t* __restrict__ sidx,
                                                            const int64_t* __restrict__ order, int64_t mt,
+                                                           const double* __restrict__ gv, int nterms,
                                                            double* __restrict__ pt, double* __restrict__ mean,
                                                            double* __restrict__ var) {
   const Lane L;
   if (L.wave >= nchunks) return;
   const QModel& m = *mp;
   const int J = m.J, r = L.r, c = L.c;
-  const double Ph_r = Xh(m, m.P[L.lane], r);
-  double hPh = 0.0;
-  for (int k = 0; k < J; ++k) hPh += m.h[k] * sh(Ph_r, k * 8);
+  const double Pl = m.P[L.lane];
+  const double Ph_r = Xh(m, Pl, r);
+  const int64_t ptsz = int64_t(nterms) * PT;
   double X = prefix[L.wave * 2 * WAVE + L.lane], f = prefix[L.wave * 2 * WAVE + WAVE + L.lane];
   int64_t n0, n1;
   pred_index(dir, L.wave, nchunks, lc, n, 0, &n0, &n1);
   if (dir == 0) {
     // data point i serves the test points of interval i; chunk 0 also those before the first point (state 0)
     int64_t p = L.wave == 0 ? 0 : lower_bound_idx(sidx, mt, n0);
-    for (; p < mt && sidx[p] < n0; ++p) pred_serve_fwd(m, X, f, 0.0, Ph_r, L.lane, r, c, pt + p * PT);
+    for (; p < mt && sidx[p] < n0; ++p) pred_serve_fwd(m, gv, nterms, X, f, 0.0, Pl, L.lane, r, c, pt + p * ptsz);
     for (int64_t i = n0; i < n1; ++i) {
       const PredStep s = pred_step(0, m, t, cbuf, wbuf, want_mean ? alpha : nullptr, n, i, r, c, Ph_r);
       if (want_var) X = symm(cong(0, s.T, X, J, r, c) + s.V, r, c);
       if (want_mean) f = lin(0, s.Phi, f, J, r, c) + s.Vf;
       for (; p < mt && sidx[p] == i; ++p)
-        pred_serve_fwd(m, X, f, xt[order[p]] - t[i], Ph_r, L.lane, r, c, pt + p * PT);
+        pred_serve_fwd(m, gv, nterms, X, f, xt[order[p]] - t[i], Pl, L.lane, r, c, pt + p * ptsz);
     }
   } else {
     // data point i serves the test points of interval i - 1; the last chunk also those of interval n - 1 (state 0)
@@ -775,8 +802,8 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_emit(int dir, int want_mea
     if (L.wave == 0) {
       for (int64_t e = mt; e-- > p;) {
         const int64_t o = order[e];
-        pred_serve_bwd(m, X, f, 0.0, Ph_r, hPh, L.lane, r, c, pt + e * PT, want_mean ? mean + o : nullptr,
-                       want_var ? var + o : nullptr);
+        pred_serve_bwd(m, gv, nterms, X, f, 0.0, Pl, L.lane, r, c, pt + e * ptsz, want_mean ? mean + o : nullptr,
+                       want_var ? var + o : nullptr, mt);
       }
     }
     for (int64_t i = n1 - 1; i >= n0; --i) {
@@ -785,8 +812,8 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_emit(int dir, int want_mea
       if (want_mean) f = lin(1, s.Phi, f, J, r, c) + s.Vf;
       for (; p > 0 && sidx[p - 1] == i - 1; --p) {
         const int64_t o = order[p - 1];
-        pred_serve_bwd(m, X, f, t[i] - xt[o], Ph_r, hPh, L.lane, r, c, pt + (p - 1) * PT,
-                       want_mean ? mean + o : nullptr, want_var ? var + o : nullptr);
+        pred_serve_bwd(m, gv, nterms, X, f, t[i] - xt[o], Pl, L.lane, r, c, pt + (p - 1) * ptsz,
+                       want_mean ? mean + o : nullptr, want_var ? var + o : nullptr, mt);
       }
     }
   }
@@ -1053,6 +1080,8 @@ struct tgp_qsep {
   int64_t pred_elems = 0;
   int64_t* pidx = nullptr;  // prediction: interval index per test point, then sorted indices and their order
   int64_t pidx_elems = 0;
+  double host_g[QJ * QJ] = {};  // prediction of terms: the test-side vectors (8 x 8, rows zero-padded) and their
+  double* gvec = nullptr;       // device copy
   // gradient: chunk prefixes kept from the primal scans (filtered covariance | solve state), the directions of one
   // batch, their dc, dw (the capped scratch), per-chunk partial sums + results, the noise gradient
   double *gkeep = nullptr, *gdir = nullptr, *gtan = nullptr, *gred = nullptr, *gout = nullptr;
@@ -1229,29 +1258,37 @@ int host_affine(tgp_qsep* q, int op, int64_t nrhs, const void* y_host, void* out
   return TGP_OK;
 }
 
-// Conditional mean and variance at m test points.  `v_host`: the residual (alpha = K^-1 r is then computed by the two
-// solves) or, with v_is_alpha, alpha itself; only read when the mean is wanted.
-int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const double* xtest_host, double* mean_host,
-            double* var_host) {
+// Conditional mean and variance at m test points for each of nterms test-side vectors (gv, device, nterms x 8).
+// `v_host`: the residual (alpha = K^-1 r is then computed by the two solves) or, with v_is_alpha, alpha itself; only
+// read when the mean is wanted.  xtest_host == nullptr: the test points are the resident t (m == n); they are sorted,
+// so their intervals need no sort and nothing goes through the host.
+int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const double* xtest_host, int nterms,
+            const double* gv, double* mean_host, double* var_host) {
   hipStream_t st = q->ctx->stream;
   const int64_t n = q->n, nc = q->nchunks;
   const int want_mean = mean_host != nullptr, want_var = var_host != nullptr;
-  // pred: xt (m) | pt (m x PT) | mean (m) | var (m);  pidx: idx (m) | sidx (m) | order (m)
-  TGP_TRY(grow(&q->pred, &q->pred_elems, m * (PT + 3)));
+  // pred: xt (m) | pt (m x nterms x PT) | mean (nterms x m) | var (nterms x m);  pidx: idx (m) | sidx (m) | order (m)
+  TGP_TRY(grow(&q->pred, &q->pred_elems, m * (1 + int64_t(nterms) * (PT + 2))));
   if (q->pidx_elems < 3 * m) {
     if (q->pidx) hipFree(q->pidx);
     q->pidx = nullptr, q->pidx_elems = 0;
     TGP_HIP_TRY(hipMalloc(&q->pidx, size_t(3 * m) * sizeof(int64_t)));
     q->pidx_elems = 3 * m;
   }
-  double *xt = q->pred, *pt = xt + m, *mean = pt + m * PT, *var = mean + m;
+  double *pt = q->pred + m, *mean = pt + m * nterms * PT, *var = mean + m * nterms;
+  const double* xt = xtest_host ? q->pred : q->t;
   int64_t *idx = q->pidx, *sidx = idx + m, *order = sidx + m;
-  TGP_HIP_TRY(hipMemcpyAsync(xt, xtest_host, size_t(m) * sizeof(double), hipMemcpyHostToDevice, st));
-  qs_pred_locate<<<unsigned((m + 255) / 256), 256, 0, st>>>(q->t, n, xt, m, idx);
+  const unsigned mblocks = unsigned((m + 255) / 256);
+  if (xtest_host)
+    TGP_HIP_TRY(hipMemcpyAsync(q->pred, xtest_host, size_t(m) * sizeof(double), hipMemcpyHostToDevice, st));
+  qs_pred_locate<<<mblocks, 256, 0, st>>>(q->t, n, xt, m, idx);
   TGP_HIP_TRY(hipGetLastError());
-  const size_t um = size_t(m);
+  const size_t um = xtest_host ? size_t(m) : 0;
   std::vector<int64_t> h_idx(um), h_order(um), h_sidx(um);
-  TGP_HIP_TRY(hipMemcpyAsync(h_idx.data(), idx, size_t(m) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  if (xtest_host)
+    TGP_HIP_TRY(hipMemcpyAsync(h_idx.data(), idx, size_t(m) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  else
+    qs_pred_identity<<<mblocks, 256, 0, st>>>(idx, m, sidx, order);
   const double* alpha = nullptr;
   if (want_mean) {  // alpha stays on the device, in io
     TGP_TRY(grow(&q->io, &q->io_elems, n));
@@ -1263,13 +1300,15 @@ int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const 
     }
     alpha = q->io;
   }
-  TGP_HIP_TRY(hipStreamSynchronize(st));
-  for (int64_t j = 0; j < m; ++j) h_order[size_t(j)] = j;
-  std::stable_sort(h_order.begin(), h_order.end(),
-                   [&](int64_t a, int64_t b) { return h_idx[size_t(a)] < h_idx[size_t(b)]; });
-  for (int64_t j = 0; j < m; ++j) h_sidx[size_t(j)] = h_idx[size_t(h_order[size_t(j)])];
-  TGP_HIP_TRY(hipMemcpyAsync(sidx, h_sidx.data(), size_t(m) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  TGP_HIP_TRY(hipMemcpyAsync(order, h_order.data(), size_t(m) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  if (xtest_host) {
+    TGP_HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t j = 0; j < m; ++j) h_order[size_t(j)] = j;
+    std::stable_sort(h_order.begin(), h_order.end(),
+                     [&](int64_t a, int64_t b) { return h_idx[size_t(a)] < h_idx[size_t(b)]; });
+    for (int64_t j = 0; j < m; ++j) h_sidx[size_t(j)] = h_idx[size_t(h_order[size_t(j)])];
+    TGP_HIP_TRY(hipMemcpyAsync(sidx, h_sidx.data(), size_t(m) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    TGP_HIP_TRY(hipMemcpyAsync(order, h_order.data(), size_t(m) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  }
   TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_PRED, nc, 1)));
   for (int dir = 0; dir < 2; ++dir) {
     qs_pred_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
@@ -1277,11 +1316,13 @@ int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const 
     double* prefix = nullptr;
     TGP_TRY(run_scan(q, st, SCAN_PRED, nc, 1, q->work, &prefix));
     qs_pred_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
-                                                        n, q->lc, nc, prefix, xt, sidx, order, m, pt, mean, var);
+                                                        n, q->lc, nc, prefix, xt, sidx, order, m, gv, nterms, pt,
+                                                        mean, var);
   }
   TGP_HIP_TRY(hipGetLastError());
-  if (want_mean) TGP_HIP_TRY(hipMemcpyAsync(mean_host, mean, size_t(m) * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (want_var) TGP_HIP_TRY(hipMemcpyAsync(var_host, var, size_t(m) * sizeof(double), hipMemcpyDeviceToHost, st));
+  const size_t out_bytes = size_t(m) * size_t(nterms) * sizeof(double);
+  if (want_mean) TGP_HIP_TRY(hipMemcpyAsync(mean_host, mean, out_bytes, hipMemcpyDeviceToHost, st));
+  if (want_var) TGP_HIP_TRY(hipMemcpyAsync(var_host, var, out_bytes, hipMemcpyDeviceToHost, st));
   TGP_HIP_TRY(hipStreamSynchronize(st));
   return TGP_OK;
 }
@@ -1373,6 +1414,26 @@ int grad_vectors(tgp_qsep* q, double* gnoise_host, double* alpha_host) {
   return TGP_OK;
 }
 
+// checks and the failed-factor answer shared by both prediction entry points; *done: nothing is left to compute
+int predict_guard(tgp_qsep* q, const double* v_host, int64_t m, bool xtest_ok, int32_t nterms, double* mean_host,
+                  double* var_host, bool* done) {
+  *done = true;
+  TGP_ARG_CHECK(q->factored, "the quasiseparable factor has not been computed (call tgp_qsep_factor first)");
+  TGP_ARG_CHECK(m >= 0, "negative number of test points (%lld)", (long long)m);
+  if (m == 0 || (!mean_host && !var_host)) return TGP_OK;
+  TGP_ARG_CHECK(xtest_ok, "null test points");
+  TGP_ARG_CHECK(!mean_host || v_host, "the mean needs the residual or alpha");
+  if (q->info != 0) {  // failed factor: c and w are not a factor of anything
+    for (int64_t j = 0; j < m * nterms; ++j) {
+      if (mean_host) mean_host[j] = NAN;
+      if (var_host) var_host[j] = NAN;
+    }
+    return TGP_OK;
+  }
+  *done = false;
+  return TGP_OK;
+}
+
 #define QS_GUARD(q)                                                                   \
   TGP_ARG_CHECK((q) != nullptr && (q)->ctx != nullptr, "null quasiseparable handle"); \
   std::unique_lock<std::recursive_mutex> _tgp_lock((q)->ctx->mu);                     \
@@ -1406,6 +1467,7 @@ int tgp_qsep_create(tgp_ctx* ctx, int64_t n, const double* t_host, tgp_qsep** ou
   Q_TRY(hipMalloc(&q->c, size_t(n) * sizeof(double)));
   Q_TRY(hipMalloc(&q->w, size_t(n) * QJ * sizeof(double)));
   Q_TRY(hipMalloc(&q->bad, size_t(q->nchunks + 1) * sizeof(int64_t)));
+  Q_TRY(hipMalloc(&q->gvec, sizeof(q->host_g)));
   Q_TRY(hipMemcpyAsync(q->t, t_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   Q_TRY(hipStreamSynchronize(ctx->stream));
 #undef Q_TRY
@@ -1421,7 +1483,7 @@ int tgp_qsep_destroy(tgp_qsep* q) {
     hipStreamSynchronize(q->ctx->stream);
   }
   void* bufs[] = {q->model, q->t,    q->noise, q->c,     q->w,    q->io,   q->io2,  q->work, q->red,
-                  q->bad,   q->pred, q->pidx,  q->gkeep, q->gdir, q->gtan, q->gred, q->gout};
+                  q->bad,   q->pred, q->pidx,  q->gkeep, q->gdir, q->gtan, q->gred, q->gout, q->gvec};
   for (void* b : bufs)
     if (b) hipFree(b);
   delete q;
@@ -1522,19 +1584,30 @@ int tgp_qsep_factor_data(tgp_qsep* q, double* c_host, double* w_host) {
 int tgp_qsep_predict(tgp_qsep* q, const double* v_host, int32_t v_is_alpha, int64_t m, const double* xtest_host,
                      double* mean_host, double* var_host) {
   QS_GUARD(q);
-  TGP_ARG_CHECK(q->factored, "the quasiseparable factor has not been computed (call tgp_qsep_factor first)");
-  TGP_ARG_CHECK(m >= 0, "negative number of test points (%lld)", (long long)m);
-  if (m == 0 || (!mean_host && !var_host)) return TGP_OK;
-  TGP_ARG_CHECK(xtest_host != nullptr, "null test points");
-  TGP_ARG_CHECK(!mean_host || v_host, "the mean needs the residual or alpha");
-  if (q->info != 0) {  // failed factor: c and w are not a factor of anything
-    for (int64_t j = 0; j < m; ++j) {
-      if (mean_host) mean_host[j] = NAN;
-      if (var_host) var_host[j] = NAN;
-    }
-    return TGP_OK;
-  }
-  return predict(q, v_host, v_is_alpha, m, xtest_host, mean_host, var_host);
+  bool done;
+  TGP_TRY(predict_guard(q, v_host, m, xtest_host != nullptr, 1, mean_host, var_host, &done));
+  if (done) return TGP_OK;
+  // one term, g = h: the model's own (zero-padded) h on the device
+  return predict(q, v_host, v_is_alpha, m, xtest_host, 1, q->model->h, mean_host, var_host);
+}
+
+int tgp_qsep_predict_terms(tgp_qsep* q, const double* v_host, int32_t v_is_alpha, int64_t m,
+                           const double* xtest_host, int32_t nterms, const double* g_host, double* mean_host,
+                           double* var_host) {
+  QS_GUARD(q);
+  TGP_ARG_CHECK(nterms >= 1 && nterms <= QJ, "one call predicts 1..%d terms (got %d)", QJ, nterms);
+  TGP_ARG_CHECK(g_host != nullptr, "null term vectors");
+  TGP_ARG_CHECK(xtest_host || m == q->n, "without test points the prediction is at the %lld data points (m = %lld)",
+                (long long)q->n, (long long)m);
+  bool done;
+  TGP_TRY(predict_guard(q, v_host, m, true, nterms, mean_host, var_host, &done));
+  if (done) return TGP_OK;
+  const int J = q->J;
+  std::fill(q->host_g, q->host_g + QJ * QJ, 0.0);
+  for (int k = 0; k < nterms; ++k)
+    for (int j = 0; j < J; ++j) q->host_g[k * QJ + j] = g_host[k * J + j];
+  TGP_HIP_TRY(hipMemcpyAsync(q->gvec, q->host_g, sizeof(q->host_g), hipMemcpyHostToDevice, q->ctx->stream));
+  return predict(q, v_host, v_is_alpha, m, xtest_host, nterms, q->gvec, mean_host, var_host);
 }
 
 }  // extern "C"

@@ -253,6 +253,18 @@ class GaussianProcess:
             return cond.loc, cond.covariance
         return cond.loc
 
+    def predict_terms(self, y, X_test=None, *, kernels=None, return_var: bool = False):
+        """The contribution of each term of a sum kernel to the prediction (the reference's
+        ``condition(y, X_test, kernel=k1)`` for every ``k1`` at once): ``means`` of shape (K, M), or ``(means, vars)``
+        with ``return_var``.  ``kernels=None`` means the top-level addends of the kernel; ``X_test=None`` the data.
+        The mean function enters through the residual only and is added to no term; no jitter is added to the
+        variances.  Needs a solver with ``predict_terms`` (:class:`tinygp_amd.solvers.QuasisepSolver`)."""
+        fused = getattr(self.solver, "predict_terms", None)
+        if fused is None:
+            raise TypeError(f"{type(self.solver).__name__} has no predict_terms: the terms of a sum are predicted by "
+                            "QuasisepSolver (a kernels.quasisep kernel on sorted 1-D inputs)")
+        return fused(self._residual(y), X_test, kernels, return_var=return_var)
+
 
 class ConditionResult(NamedTuple):
     """``(log_probability, gp)`` (reference ``gp.py:364-385``)."""

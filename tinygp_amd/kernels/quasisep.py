@@ -126,6 +126,49 @@ class Quasisep(base.Kernel):
             raise ValueError("non-finite quasiseparable kernel parameters")
         return s
 
+    # -- terms of a sum (QuasisepSolver.predict_terms) ------------------------------
+    def _addends(self) -> list:
+        """The flattened addends: the leaves of the tree of ``Sum`` nodes rooted here, in state order."""
+        if isinstance(self, Sum):
+            return self.kernel1._addends() + self.kernel2._addends()
+        return [self]
+
+    def _term_vector(self, term):
+        """The test-side observation vector ``g`` of ``term``, or ``None`` when ``term`` is not a term of this kernel.
+
+        A sum's state is block-diagonal, so the covariance between one addend at x and the whole model at the data is
+        the model's own with ``h`` masked to that addend's states.  Terms are found by object identity, walking from
+        this kernel through ``Sum`` nodes only: this kernel itself (``g = h``), any addend or partial ``Sum`` of the
+        tree, and a ``Sum`` built elsewhere whose flattened addends are all found that way (their union).  A factor
+        of a ``Product``, the kernel inside a ``Scale`` and an equal-valued copy are not terms."""
+        nodes = []  # (node, first state, one past its last), every node reachable through Sum nodes
+
+        def walk(k, lo):
+            nodes.append((k, lo, lo + k._ssm().J))
+            if isinstance(k, Sum):
+                walk(k.kernel1, lo)
+                walk(k.kernel2, lo + k.kernel1._ssm().J)
+
+        def find(k):
+            for node, lo, hi in nodes:
+                if node is k:
+                    return [(lo, hi)]
+            if isinstance(k, Sum):
+                a, b = find(k.kernel1), find(k.kernel2)
+                if a is not None and b is not None:
+                    return a + b
+            return None
+
+        walk(self, 0)
+        ranges = find(term)
+        if ranges is None:
+            return None
+        h = self._ssm().h
+        g = np.zeros_like(h)
+        for lo, hi in ranges:
+            g[lo:hi] = h[lo:hi]
+        return g
+
     # -- dense value on the host ---------------------------------------------------
     def _k_of_lag(self, tau) -> np.ndarray:
         """k as a function of the lag ``tau >= 0`` (any shape)."""

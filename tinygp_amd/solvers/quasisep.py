@@ -5,7 +5,8 @@ factor described by O(N J) numbers (``c_n``, ``w_n``; ``tests/_quasisep_np.py`` 
 ``tgp_qsep`` handle (C ABI, ``include/tgp_hip.h``) keeps t, the noise and that factor resident on the device; the
 factorisation, both triangular solves and ``L @ z`` are chunked reduce-then-scan recurrences in
 ``csrc/qsep.hip``, and so are the conditional mean and variance at M test points (``predict_mean_var``; O(N + M),
-nothing of size N x M) and the gradient of the log-probability (``value_and_grad``; O(N) per parameter).  Nothing
+nothing of size N x M), the same for every term of a sum at once (``predict_terms``; also at the data themselves)
+and the gradient of the log-probability (``value_and_grad``; O(N) per parameter).  Nothing
 of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
 reference); the full conditional covariance and conditioning on another kernel keep the reference's dense route.
 
@@ -215,6 +216,47 @@ class QuasisepSolver(Solver):
         """
         mean, var = self._predict(resid, False, X_test, True, return_var)
         return (mean, var) if return_var else mean
+
+    def predict_terms(self, resid, X_test=None, kernels=None, *, return_var: bool = True):
+        """What each term of a sum contributes: for every kernel ``k_j`` of ``kernels`` the conditional mean
+        ``k_j(X_test, X) K^-1 resid`` and variance ``k_j(x, x) - k_j(x, X) K^-1 k_j(X, x)`` (no noise added), with
+        ``K`` the whole model's.  All terms share one pair of device scans (``tgp_qsep_predict_terms``): O(N + K M).
+
+        ``kernels``: terms of the solver's kernel in the sense of :meth:`Quasisep._term_vector`; ``None`` means its
+        flattened top-level addends, in order (a kernel that is no sum gives one row).  More than 8 are served in
+        batches of 8.  ``X_test``: as in :meth:`predict_mean_var`; ``None`` predicts at the data without uploading or
+        sorting anything.  Returns ``(means, vars)`` of shape (K, M), or the means alone with ``return_var=False``;
+        after a failed factor both are NaN."""
+        from tinygp_amd.kernels.quasisep import MAX_STATE, _coords
+
+        terms = self.kernel._addends() if kernels is None else list(kernels)
+        gs = []
+        for k in terms:
+            g = self.kernel._term_vector(k)
+            if g is None:
+                raise ValueError(
+                    f"{k!r} is not a term of the solver's kernel: a term is that kernel itself, one of the addends or "
+                    "partial sums reached from it through Sum nodes (the same object, not an equal copy), or a Sum of "
+                    "such addends; a factor of a Product and the kernel inside a Scale are not terms")
+            gs.append(g)
+        self._ensure_factor()
+        x = None if X_test is None else _f64(_coords(X_test))
+        m = self.n if x is None else x.shape[0]
+        vv = _f64(resid, (self.n,))
+        means = np.empty((len(gs), m))
+        vars_ = np.empty((len(gs), m)) if return_var else None
+        for b in range(0, len(gs) if m else 0, MAX_STATE):
+            g = _f64(np.stack(gs[b:b + MAX_STATE]))
+            mean = np.empty((len(g), m))
+            var = np.empty((len(g), m)) if return_var else None
+            _ffi.check(_ffi.lib().tgp_qsep_predict_terms(self._handle, _ffi.ptr(vv), 0, m, _ffi.ptr(x), len(g),
+                                                         _ffi.ptr(g), _ffi.ptr(mean), _ffi.ptr(var)),
+                       "tgp_qsep_predict_terms")
+            means[b:b + len(g)] = mean
+            if return_var:
+                vars_[b:b + len(g)] = var
+        means = means.astype(self.dtype, copy=False)
+        return (means, vars_.astype(self.dtype, copy=False)) if return_var else means
 
     # -- fused entry points used by GaussianProcess ------------------------------------
     def log_probability(self, resid):
