@@ -635,6 +635,22 @@ int tgp_qsep_grad(tgp_qsep* q, const double* leaves, int32_t nleaves, const int3
                   const double* hvec, const double* Pinf, const double* noise_host, const double* resid_host,
                   int32_t ndir, const double* dleaves, const double* dh, const double* dPinf, int32_t* info,
                   double* out, double* dout, double* gnoise_host, double* alpha_host);
+/* The log-probability (as tgp_qsep_factor_logprob) of nb models over the handle's series, evaluated together: one model
+ * per grid row of every kernel, so that small series fill the device.  The models share nleaves, state_map and J;
+ * member b's `leaves` (nb x nleaves x 5; leaf kinds may differ between members, e.g. the damping regime of an SHO),
+ * `hvec` (nb x J) and `Pinf` (nb x J x J) follow member b - 1's.  noise_host and resid_host hold one vector for all
+ * (stride 0) or one per member (stride n).  info (nb), out (nb): per member; a non-positive pivot sets that member's
+ * info to its 1-based step and its out to NaN and touches no other member.  A member's result has the bits of
+ * tgp_qsep_factor_logprob with its model, noise and residual, whatever nb and its position.  A launch chain (one
+ * upload per distinct array, one download, one stream synchronisation) holds at most 64 members and at most 1 GiB of
+ * device scratch (DESIGN section 11 states the layout); larger batches run as several chains inside the call, and
+ * *nchains (may be NULL) reports how many.  A series whose single member exceeds the cap is an argument error.  The
+ * handle's resident model, noise and factor are neither read nor changed; it need not be factored.  nb = 0 returns at
+ * once. */
+int tgp_qsep_logprob_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                           int32_t J, const double* hvec, const double* Pinf, const double* noise_host,
+                           int64_t noise_stride, const double* resid_host, int64_t resid_stride, int32_t* info,
+                           double* out, int32_t* nchains);
 
 #ifdef __cplusplus
 }

@@ -23,11 +23,18 @@
 // Layout: one wavefront holds a J x J matrix (or a J x 8 block of right-hand sides) as one entry per lane,
 // lane = 8 r + c; entries outside J x J are zero.  Products read operands through __shfl.  Every reduction runs in
 // a fixed order, so results are bit-identical from run to run.  Arithmetic is fp64 throughout.
+//
+// Batches of models: the kernels of the fused log-probability (qs_fold, qs_reduce / qs_down, qs_emit, qs_aff_fold,
+// qs_aff_reduce / qs_aff_down, qs_aff_emit, qs_finish) serve one model per blockIdx.y (qs_finish: per block) over the
+// shared t: model mp[blockIdx.y], every array of that member `stride` doubles after its neighbour's.  A single
+// evaluation is the batch of one (grid y = 1, where no stride matters), so both run the same code and a member's
+// result has the bits of its single call.
 #include "tgp_common.h"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 namespace {
@@ -276,11 +283,14 @@ struct Lane {
 
 // ---- factor, phase 1: fold each chunk into one filtering element (A, C, J) ----------------------------------
 __global__ __launch_bounds__(WAVE * WPB) void qs_fold(const QModel* __restrict__ mp, const double* __restrict__ t,
-                                                      const double* __restrict__ noise, int64_t n, int64_t lc,
-                                                      int64_t nchunks, double* __restrict__ elem) {
+                                                      const double* __restrict__ noise, int64_t noise_stride,
+                                                      int64_t n, int64_t lc, int64_t nchunks,
+                                                      double* __restrict__ elem, int64_t work_stride) {
   const Lane L;
   if (L.wave >= nchunks) return;
-  const QModel& m = *mp;
+  const int64_t mem = blockIdx.y;
+  const QModel& m = mp[mem];
+  noise += mem * noise_stride, elem += mem * work_stride;
   const int J = m.J, r = L.r, c = L.c;
   const double P = m.P[L.lane];
   double A = (r == c && r < J) ? 1.0 : 0.0, C = 0.0, Jm = 0.0;
@@ -334,11 +344,15 @@ __device__ void ric_combine(double& A, double& C, double& Jm, double A2, double 
   A = An, C = Cn, Jm = Jn;
 }
 
+// in, out (and the prefixes of qs_down): member blockIdx.y's lie work_stride doubles after its neighbour's
 __global__ __launch_bounds__(WAVE * WPB) void qs_reduce(const QModel* __restrict__ mp, const double* __restrict__ in,
-                                                        int64_t count, double* __restrict__ out, int64_t ngroups) {
+                                                        int64_t count, double* __restrict__ out, int64_t ngroups,
+                                                        int64_t work_stride) {
   const Lane L;
   if (L.wave >= ngroups) return;
-  const int J = mp->J;
+  const int64_t mem = blockIdx.y;
+  const int J = mp[mem].J;
+  in += mem * work_stride, out += mem * work_stride;
   const int64_t b = L.wave * GROUP, e = min(count, b + GROUP);
   double A = in[b * 3 * WAVE + L.lane], C = in[b * 3 * WAVE + WAVE + L.lane], Jm = in[b * 3 * WAVE + 2 * WAVE + L.lane];
   for (int64_t i = b + 1; i < e; ++i) {
@@ -352,11 +366,14 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_reduce(const QModel* __restrict
 // prefix_in: one state per group (nullptr: the top level, start from P = 0); prefix_out: one per element
 __global__ __launch_bounds__(WAVE * WPB) void qs_down(const QModel* __restrict__ mp, const double* __restrict__ elem,
                                                       int64_t count, const double* __restrict__ prefix_in,
-                                                      double* __restrict__ prefix_out, int64_t ngroups) {
+                                                      double* __restrict__ prefix_out, int64_t ngroups,
+                                                      int64_t work_stride) {
   const Lane L;
   if (L.wave >= ngroups) return;
-  const int J = mp->J, r = L.r, c = L.c;
-  double P = prefix_in ? prefix_in[L.wave * WAVE + L.lane] : 0.0;
+  const int64_t mem = blockIdx.y;
+  const int J = mp[mem].J, r = L.r, c = L.c;
+  elem += mem * work_stride, prefix_out += mem * work_stride;
+  double P = prefix_in ? prefix_in[mem * work_stride + L.wave * WAVE + L.lane] : 0.0;
   const int64_t b = L.wave * GROUP, e = min(count, b + GROUP);
   for (int64_t i = b; i < e; ++i) {
     prefix_out[i * WAVE + L.lane] = P;
@@ -370,15 +387,21 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_down(const QModel* __restrict__
 }
 
 // ---- factor, phase 3: the sequential recursion from each chunk's incoming filtered covariance ------------------
+// member blockIdx.y: c at cbuf + y n, w at wbuf + y n J, its bad-pivot slots at bad + y nchunks
 __global__ __launch_bounds__(WAVE * WPB) void qs_emit(const QModel* __restrict__ mp, const double* __restrict__ t,
-                                                      const double* __restrict__ noise, int64_t n, int64_t lc,
-                                                      int64_t nchunks, const double* __restrict__ prefix,
+                                                      const double* __restrict__ noise, int64_t noise_stride,
+                                                      int64_t n, int64_t lc, int64_t nchunks,
+                                                      const double* __restrict__ prefix, int64_t work_stride,
                                                       double* __restrict__ cbuf, double* __restrict__ wbuf,
-                                                      double* __restrict__ logsum, int64_t* __restrict__ bad) {
+                                                      double* __restrict__ logsum, int64_t red_stride,
+                                                      int64_t* __restrict__ bad) {
   const Lane L;
   if (L.wave >= nchunks) return;
-  const QModel& m = *mp;
+  const int64_t mem = blockIdx.y;
+  const QModel& m = mp[mem];
   const int J = m.J, r = L.r, c = L.c;
+  noise += mem * noise_stride, prefix += mem * work_stride, cbuf += mem * n, wbuf += mem * n * J;
+  logsum += mem * red_stride, bad += mem * nchunks;
   const double Pinf = m.P[L.lane];
   double P = prefix[L.wave * WAVE + L.lane];
   double acc = 0.0;
@@ -458,10 +481,13 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_fold(int op, const QModel* 
                                                           const double* __restrict__ t, const double* __restrict__ cbuf,
                                                           const double* __restrict__ wbuf, int64_t n, int64_t lc,
                                                           int64_t nchunks, int64_t nrhs, int64_t ncg,
-                                                          const double* __restrict__ y, double* __restrict__ elem) {
+                                                          const double* __restrict__ y, int64_t y_stride,
+                                                          double* __restrict__ elem, int64_t work_stride) {
   const Lane L;
   if (L.wave >= nchunks * ncg) return;
-  const QModel& m = *mp;
+  const int64_t mem = blockIdx.y;
+  const QModel& m = mp[mem];
+  cbuf += mem * n, wbuf += mem * n * m.J, y += mem * y_stride, elem += mem * work_stride;
   const int r = L.r, c = L.c;
   const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
   double M = (r == c && r < m.J) ? 1.0 : 0.0, V = 0.0, o;
@@ -480,10 +506,13 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_fold(int op, const QModel* 
 
 __global__ __launch_bounds__(WAVE * WPB) void qs_aff_reduce(const QModel* __restrict__ mp,
                                                             const double* __restrict__ in, int64_t count, int64_t ncg,
-                                                            double* __restrict__ out, int64_t ngroups) {
+                                                            double* __restrict__ out, int64_t ngroups,
+                                                            int64_t work_stride) {
   const Lane L;
   if (L.wave >= ngroups * ncg) return;
-  const int J = mp->J;
+  const int64_t mem = blockIdx.y;
+  const int J = mp[mem].J;
+  in += mem * work_stride, out += mem * work_stride;
   const int64_t g = L.wave / ncg, cg = L.wave % ncg;
   const int64_t b = g * GROUP, e = min(count, b + GROUP);
   double M = in[(b * ncg + cg) * 2 * WAVE + L.lane], V = in[(b * ncg + cg) * 2 * WAVE + WAVE + L.lane];
@@ -501,12 +530,15 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_reduce(const QModel* __rest
 __global__ __launch_bounds__(WAVE * WPB) void qs_aff_down(const QModel* __restrict__ mp,
                                                           const double* __restrict__ elem, int64_t count, int64_t ncg,
                                                           const double* __restrict__ prefix_in,
-                                                          double* __restrict__ prefix_out, int64_t ngroups) {
+                                                          double* __restrict__ prefix_out, int64_t ngroups,
+                                                          int64_t work_stride) {
   const Lane L;
   if (L.wave >= ngroups * ncg) return;
-  const int J = mp->J;
+  const int64_t mem = blockIdx.y;
+  const int J = mp[mem].J;
+  elem += mem * work_stride, prefix_out += mem * work_stride;
   const int64_t g = L.wave / ncg, cg = L.wave % ncg;
-  double X = prefix_in ? prefix_in[L.wave * WAVE + L.lane] : 0.0;
+  double X = prefix_in ? prefix_in[mem * work_stride + L.wave * WAVE + L.lane] : 0.0;
   const int64_t b = g * GROUP, e = min(count, b + GROUP);
   for (int64_t i = b; i < e; ++i) {
     prefix_out[(i * ncg + cg) * WAVE + L.lane] = X;
@@ -519,12 +551,15 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_emit(int op, const QModel* 
                                                           const double* __restrict__ t, const double* __restrict__ cbuf,
                                                           const double* __restrict__ wbuf, int64_t n, int64_t lc,
                                                           int64_t nchunks, int64_t nrhs, int64_t ncg,
-                                                          const double* __restrict__ prefix,
-                                                          const double* __restrict__ y, double* __restrict__ out,
-                                                          double* __restrict__ sumsq) {
+                                                          const double* __restrict__ prefix, int64_t work_stride,
+                                                          const double* __restrict__ y, int64_t y_stride,
+                                                          double* __restrict__ out, double* __restrict__ sumsq,
+                                                          int64_t red_stride) {
   const Lane L;
   if (L.wave >= nchunks * ncg) return;
-  const QModel& m = *mp;
+  const int64_t mem = blockIdx.y;
+  const QModel& m = mp[mem];
+  cbuf += mem * n, wbuf += mem * n * m.J, prefix += mem * work_stride, y += mem * y_stride, out += mem * n * nrhs;
   const int r = L.r, c = L.c;
   const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
   double X = prefix[L.wave * WAVE + L.lane], o = 0.0, acc = 0.0;
@@ -543,7 +578,7 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_emit(int op, const QModel* 
   if (sumsq) {  // fixed-order sum over the 8 columns of row 0
     double s = 0.0;
     for (int q = 0; q < 8; ++q) s += sh(acc, q);
-    if (L.lane == 0) sumsq[L.wave] = s;
+    if (L.lane == 0) sumsq[mem * red_stride + L.wave] = s;
   }
 }
 
@@ -1031,12 +1066,19 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_invdiag_emit(const QModel* __re
   }
 }
 
-// one wavefront: fixed-order sums of a[0..n) and b[0..nb), minimum of bad[0..n)
+// one wavefront per block: fixed-order sums of a[0..na) and b[0..nb), minimum of bad[0..na).  Block x reads a and b
+// x in_stride doubles, bad x bad_stride slots further on and writes out and first_bad x out_stride slots further on.
 __global__ __launch_bounds__(WAVE) void qs_finish(const double* __restrict__ a, int64_t na,
                                                   const double* __restrict__ b, int64_t nb,
                                                   const int64_t* __restrict__ bad, double* __restrict__ out,
-                                                  int64_t* __restrict__ first_bad) {
+                                                  int64_t* __restrict__ first_bad, int64_t in_stride,
+                                                  int64_t bad_stride, int64_t out_stride) {
   const int lane = threadIdx.x;
+  const int64_t mem = blockIdx.x;
+  a += mem * in_stride, out += mem * out_stride;
+  if (b) b += mem * in_stride;
+  if (bad) bad += mem * bad_stride;
+  if (first_bad) first_bad += mem * out_stride;
   double sa = 0.0, sb = 0.0;
   int64_t mb = INT64_MAX;
   for (int64_t i = lane; i < na; i += WAVE) sa += a[i];
@@ -1086,6 +1128,9 @@ struct tgp_qsep {
   // batch, their dc, dw (the capped scratch), per-chunk partial sums + results, the noise gradient
   double *gkeep = nullptr, *gdir = nullptr, *gtan = nullptr, *gred = nullptr, *gout = nullptr;
   int64_t gkeep_elems = 0, gdir_elems = 0, gtan_elems = 0, gred_elems = 0, gout_elems = 0;
+  // batches of models: the models and every array of one launch chain (the capped scratch; batch_layout)
+  double* bat = nullptr;
+  int64_t bat_elems = 0;
 };
 
 namespace {
@@ -1116,9 +1161,11 @@ inline int64_t scan_psz(ScanKind k) { return (k == SCAN_PRED ? 2 : 1) * WAVE; }
 
 // Exclusive scan over the elements already in `elem0` (esz doubles each, `width` independent scans interleaved):
 // prefixes (psz doubles each) of level 0 land in the returned pointer.  Work layout: per level, elements then
-// prefixes.
-int run_scan(tgp_qsep* q, hipStream_t st, ScanKind kind, int64_t count, int64_t width, double* elem0,
-             double** prefix0) {
+// prefixes.  Riccati and affine scans run `members` models at once (grid y): member b uses models[b] and the same
+// layout `work_stride` doubles after member b - 1's; the other kinds serve the handle's own model only.
+int run_scan(const QModel* models, hipStream_t st, ScanKind kind, int64_t count, int64_t width, double* elem0,
+             double** prefix0, int64_t members = 1, int64_t work_stride = 0) {
+  TGP_ARG_CHECK(members == 1 || kind == SCAN_RIC || kind == SCAN_AFF, "this scan serves one model at a time");
   const int64_t esz = scan_esz(kind), psz = scan_psz(kind);
   const std::vector<int64_t> sz = level_sizes(count);
   std::vector<double*> el(sz.size()), pre(sz.size());
@@ -1135,25 +1182,29 @@ int run_scan(tgp_qsep* q, hipStream_t st, ScanKind kind, int64_t count, int64_t 
   for (size_t l = 0; l + 1 < sz.size(); ++l) {
     const int64_t g = sz[l + 1];
     if (kind == SCAN_RIC)
-      qs_reduce<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], el[l + 1], g);
+      qs_reduce<<<dim3(unsigned(blocks_for(g)), unsigned(members)), WAVE * WPB, 0, st>>>(models, el[l], sz[l],
+                                                                                         el[l + 1], g, work_stride);
     else if (kind == SCAN_PRED)
-      qs_pred_reduce<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], el[l + 1], g);
+      qs_pred_reduce<<<blocks_for(g), WAVE * WPB, 0, st>>>(models, el[l], sz[l], el[l + 1], g);
     else if (kind == SCAN_CONG)
-      qs_cong_reduce<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, el[l + 1], g);
+      qs_cong_reduce<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(models, el[l], sz[l], width, el[l + 1], g);
     else
-      qs_aff_reduce<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, el[l + 1], g);
+      qs_aff_reduce<<<dim3(unsigned(blocks_for(g * width)), unsigned(members)), WAVE * WPB, 0, st>>>(
+          models, el[l], sz[l], width, el[l + 1], g, work_stride);
   }
   for (size_t l = sz.size(); l-- > 0;) {
     const int64_t g = l + 1 < sz.size() ? sz[l + 1] : 1;
     const double* pin = l + 1 < sz.size() ? pre[l + 1] : nullptr;
     if (kind == SCAN_RIC)
-      qs_down<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], pin, pre[l], g);
+      qs_down<<<dim3(unsigned(blocks_for(g)), unsigned(members)), WAVE * WPB, 0, st>>>(models, el[l], sz[l], pin,
+                                                                                       pre[l], g, work_stride);
     else if (kind == SCAN_PRED)
-      qs_pred_down<<<blocks_for(g), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], pin, pre[l], g);
+      qs_pred_down<<<blocks_for(g), WAVE * WPB, 0, st>>>(models, el[l], sz[l], pin, pre[l], g);
     else if (kind == SCAN_CONG)
-      qs_cong_down<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, pin, pre[l], g);
+      qs_cong_down<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(models, el[l], sz[l], width, pin, pre[l], g);
     else
-      qs_aff_down<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(q->model, el[l], sz[l], width, pin, pre[l], g);
+      qs_aff_down<<<dim3(unsigned(blocks_for(g * width)), unsigned(members)), WAVE * WPB, 0, st>>>(
+          models, el[l], sz[l], width, pin, pre[l], g, work_stride);
   }
   TGP_HIP_TRY(hipGetLastError());
   *prefix0 = pre[0];
@@ -1166,8 +1217,9 @@ int64_t scan_work(ScanKind kind, int64_t count, int64_t width) {
   return total;
 }
 
-int set_model(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t* state_map, int32_t J,
-              const double* hvec, const double* Pinf) {
+// checks one model's host arrays and packs them
+int pack_model(QModel* out, const double* leaves, int32_t nleaves, const int32_t* state_map, int32_t J,
+               const double* hvec, const double* Pinf) {
   TGP_ARG_CHECK(J >= 1 && J <= QJ, "quasiseparable state dimension must be 1..%d (got %d)", QJ, J);
   TGP_ARG_CHECK(nleaves >= 1 && nleaves <= QL, "quasiseparable kernels hold 1..%d leaves (got %d)", QL, nleaves);
   TGP_ARG_CHECK(leaves && state_map && hvec && Pinf, "null model array");
@@ -1186,6 +1238,14 @@ int set_model(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t*
     m.h[r] = hvec[r];
     for (int c = 0; c < J; ++c) m.P[r * QJ + c] = Pinf[r * J + c];
   }
+  *out = m;
+  return TGP_OK;
+}
+
+int set_model(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t* state_map, int32_t J,
+              const double* hvec, const double* Pinf) {
+  QModel m{};
+  TGP_TRY(pack_model(&m, leaves, nleaves, state_map, J, hvec, Pinf));
   q->host_model = m;
   q->J = J;
   TGP_HIP_TRY(hipMemcpyAsync(q->model, &q->host_model, sizeof(QModel), hipMemcpyHostToDevice, q->ctx->stream));
@@ -1199,14 +1259,14 @@ int factor(tgp_qsep* q, const double* noise_host, double* keep = nullptr) {
   TGP_ARG_CHECK(noise_host != nullptr, "null noise array");
   TGP_HIP_TRY(hipMemcpyAsync(q->noise, noise_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
   TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_RIC, nc, 1)));
-  qs_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, n, q->lc, nc, q->work);
+  qs_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, 0, n, q->lc, nc, q->work, 0);
   double* prefix = nullptr;
-  TGP_TRY(run_scan(q, st, SCAN_RIC, nc, 1, q->work, &prefix));
+  TGP_TRY(run_scan(q->model, st, SCAN_RIC, nc, 1, q->work, &prefix));
   if (keep)
     TGP_HIP_TRY(hipMemcpyAsync(keep, prefix, size_t(nc) * WAVE * sizeof(double), hipMemcpyDeviceToDevice, st));
-  qs_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, n, q->lc, nc, prefix, q->c, q->w,
-                                                 q->red, q->bad);
-  qs_finish<<<1, WAVE, 0, st>>>(q->red, nc, nullptr, 0, q->bad, q->red + 2 * nc, q->bad + nc);
+  qs_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, 0, n, q->lc, nc, prefix, 0, q->c, q->w,
+                                                 q->red, 0, q->bad);
+  qs_finish<<<1, WAVE, 0, st>>>(q->red, nc, nullptr, 0, q->bad, q->red + 2 * nc, q->bad + nc, 0, 0, 0);
   TGP_HIP_TRY(hipGetLastError());
   double sums[2];
   int64_t bad = 0;
@@ -1226,15 +1286,15 @@ int affine(tgp_qsep* q, int op, int64_t nrhs, const double* y, double* out, doub
   const int64_t n = q->n, nc = q->nchunks, ncg = ceil_div(nrhs, 8);
   TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_AFF, nc, ncg)));
   qs_aff_fold<<<blocks_for(nc * ncg), WAVE * WPB, 0, st>>>(op, q->model, q->t, q->c, q->w, n, q->lc, nc, nrhs, ncg,
-                                                            y, q->work);
+                                                            y, 0, q->work, 0);
   double* prefix = nullptr;
-  TGP_TRY(run_scan(q, st, SCAN_AFF, nc, ncg, q->work, &prefix));
+  TGP_TRY(run_scan(q->model, st, SCAN_AFF, nc, ncg, q->work, &prefix));
   if (keep)
     TGP_HIP_TRY(hipMemcpyAsync(keep, prefix, size_t(nc * ncg) * WAVE * sizeof(double), hipMemcpyDeviceToDevice, st));
   qs_aff_emit<<<blocks_for(nc * ncg), WAVE * WPB, 0, st>>>(op, q->model, q->t, q->c, q->w, n, q->lc, nc, nrhs, ncg,
-                                                            prefix, y, out, sumsq ? q->red : nullptr);
+                                                            prefix, 0, y, 0, out, sumsq ? q->red : nullptr, 0);
   if (sumsq) {
-    qs_finish<<<1, WAVE, 0, st>>>(q->red, nc * ncg, nullptr, 0, nullptr, q->red + 2 * nc * ncg, nullptr);
+    qs_finish<<<1, WAVE, 0, st>>>(q->red, nc * ncg, nullptr, 0, nullptr, q->red + 2 * nc * ncg, nullptr, 0, 0, 0);
     TGP_HIP_TRY(hipMemcpyAsync(sumsq, q->red + 2 * nc * ncg, sizeof(double), hipMemcpyDeviceToHost, st));
   }
   TGP_HIP_TRY(hipGetLastError());
@@ -1314,7 +1374,7 @@ int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const 
     qs_pred_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
                                                         n, q->lc, nc, q->work);
     double* prefix = nullptr;
-    TGP_TRY(run_scan(q, st, SCAN_PRED, nc, 1, q->work, &prefix));
+    TGP_TRY(run_scan(q->model, st, SCAN_PRED, nc, 1, q->work, &prefix));
     qs_pred_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
                                                         n, q->lc, nc, prefix, xt, sidx, order, m, gv, nterms, pt,
                                                         mean, var);
@@ -1372,16 +1432,16 @@ int grad_directions(tgp_qsep* q, int32_t ndir, const double* dleaves, const doub
     double* res = q->gred + 2 * nb * nc;
     double* prefix = nullptr;
     qs_gfac_fold<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->noise, n, q->lc, nc, prefixP, q->work);
-    TGP_TRY(run_scan(q, st, SCAN_CONG, nc, nb, q->work, &prefix));
+    TGP_TRY(run_scan(q->model, st, SCAN_CONG, nc, nb, q->work, &prefix));
     qs_gfac_emit<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->noise, n, q->lc, nc, prefixP, prefix, dcb, dwb,
                                               dsum);
     qs_gsol<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->c, q->w, dcb, dwb, q->io, n, q->lc, nc, prefixS,
                                          nullptr, q->work, nullptr);
-    TGP_TRY(run_scan(q, st, SCAN_AFF, nc, nb, q->work, &prefix));
+    TGP_TRY(run_scan(q->model, st, SCAN_AFF, nc, nb, q->work, &prefix));
     qs_gsol<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->c, q->w, dcb, dwb, q->io, n, q->lc, nc, prefixS,
                                          prefix, nullptr, dsum2);
     for (int64_t b = 0; b < nb; ++b)
-      qs_finish<<<1, WAVE, 0, st>>>(dsum + b * nc, nc, dsum2 + b * nc, nc, nullptr, res + 2 * b, nullptr);
+      qs_finish<<<1, WAVE, 0, st>>>(dsum + b * nc, nc, dsum2 + b * nc, nc, nullptr, res + 2 * b, nullptr, 0, 0, 0);
     TGP_HIP_TRY(hipGetLastError());
     // the host vectors are reused by the next batch: wait for this one
     TGP_HIP_TRY(hipMemcpyAsync(sums.data(), res, size_t(2 * nb) * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1404,13 +1464,97 @@ int grad_vectors(tgp_qsep* q, double* gnoise_host, double* alpha_host) {
     qs_pred_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(1, 0, 1, q->model, q->t, q->c, q->w, nullptr, n, q->lc, nc,
                                                         q->work);
     double* prefix = nullptr;
-    TGP_TRY(run_scan(q, st, SCAN_PRED, nc, 1, q->work, &prefix));
+    TGP_TRY(run_scan(q->model, st, SCAN_PRED, nc, 1, q->work, &prefix));
     qs_invdiag_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->c, q->w, q->io, n, q->lc, nc, prefix,
                                                            q->gout);
     TGP_HIP_TRY(hipGetLastError());
     TGP_HIP_TRY(hipMemcpyAsync(gnoise_host, q->gout, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   TGP_HIP_TRY(hipStreamSynchronize(st));
+  return TGP_OK;
+}
+
+// the log-probability from sum z^2 and sum log c; one function, so that single and batched calls round alike
+__attribute__((noinline)) double logprob_value(double zz, double logdet, int64_t n) {
+  return -0.5 * zz - 0.5 * logdet - 0.5 * double(n) * kLog2Pi;
+}
+
+// ---- batches of models over the one series -----------------------------------------------------------------------------
+// A launch chain evaluates up to BATCH_MAX_MEMBERS models, and as many as keep the handle's batch buffer at or under
+// BATCH_SCRATCH_BYTES.  The buffer, in doubles:
+//   fixed        BATCH_MAX_MEMBERS models (MODEL_DOUBLES each) | the noise, if shared (n) | the residual, if shared (n)
+//   per member   noise, if its own (n) | residual, if its own (n) | c (n) | w (n J) | z (n) | scan work space (W) |
+//                per-chunk sums of log c and of z^2 (2 nchunks) | bad-pivot slots (nchunks) | results (3)
+// with W = 4 WAVE sum of the scan's level sizes, the Riccati scan's need (the affine scan's 3 WAVE fits inside).
+constexpr int64_t BATCH_MAX_MEMBERS = 64;
+constexpr int64_t BATCH_SCRATCH_BYTES = int64_t(1) << 30;
+static_assert(sizeof(QModel) % sizeof(double) == 0, "models are laid out in a buffer of doubles");
+constexpr int64_t MODEL_DOUBLES = sizeof(QModel) / sizeof(double);
+
+struct BatchLayout {
+  int64_t fixed, per_member, work;  // doubles
+};
+
+BatchLayout batch_layout(int64_t n, int64_t nc, int64_t J, bool own_noise, bool own_resid) {
+  BatchLayout l;
+  l.work = std::max(scan_work(SCAN_RIC, nc, 1), scan_work(SCAN_AFF, nc, 1));
+  l.fixed = BATCH_MAX_MEMBERS * MODEL_DOUBLES + (own_noise ? 0 : n) + (own_resid ? 0 : n);
+  l.per_member = (own_noise ? n : 0) + (own_resid ? n : 0) + n * (2 + J) + l.work + 3 * nc + 3;
+  return l;
+}
+
+// one launch chain: members [0, nb) of the arrays given; shared noise / residual are on the device already
+int batch_chain(tgp_qsep* q, const BatchLayout& lay, int64_t cap, int64_t nb, const QModel* models_host, int64_t J,
+                const double* noise_host, int64_t noise_stride, const double* resid_host, int64_t resid_stride,
+                int32_t* info, double* out) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks, W = lay.work;
+  // the buffer is carved for `cap` members, whatever this chain holds: the layout depends on the call alone
+  QModel* models = reinterpret_cast<QModel*>(q->bat);
+  double* p = q->bat + BATCH_MAX_MEMBERS * MODEL_DOUBLES;
+  auto take = [&](int64_t shared, int64_t stride) {
+    double* r = p;
+    p += stride ? cap * stride : shared;
+    return r;
+  };
+  double* noise = take(n, noise_stride);
+  double* resid = take(n, resid_stride);
+  double* cbuf = take(0, n);
+  double* wbuf = take(0, n * J);
+  double* z = take(0, n);
+  double* work = take(0, W);
+  double* red = take(0, 2 * nc);
+  int64_t* bad = reinterpret_cast<int64_t*>(take(0, nc));
+  double* res = take(0, 3);
+  TGP_HIP_TRY(hipMemcpyAsync(models, models_host, size_t(nb) * sizeof(QModel), hipMemcpyHostToDevice, st));
+  if (noise_stride)
+    TGP_HIP_TRY(hipMemcpyAsync(noise, noise_host, size_t(nb * n) * sizeof(double), hipMemcpyHostToDevice, st));
+  if (resid_stride)
+    TGP_HIP_TRY(hipMemcpyAsync(resid, resid_host, size_t(nb * n) * sizeof(double), hipMemcpyHostToDevice, st));
+  const dim3 grid(unsigned(blocks_for(nc)), unsigned(nb));
+  double* prefix = nullptr;
+  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, noise_stride, n, q->lc, nc, work, W);
+  TGP_TRY(run_scan(models, st, SCAN_RIC, nc, 1, work, &prefix, nb, W));
+  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, noise_stride, n, q->lc, nc, prefix, W, cbuf, wbuf, red,
+                                       2 * nc, bad);
+  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, q->t, cbuf, wbuf, n, q->lc, nc, 1, 1, resid,
+                                           resid_stride, work, W);
+  TGP_TRY(run_scan(models, st, SCAN_AFF, nc, 1, work, &prefix, nb, W));
+  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, q->t, cbuf, wbuf, n, q->lc, nc, 1, 1, prefix, W, resid,
+                                           resid_stride, z, red + nc, 2 * nc);
+  // per member: (sum log c, sum z^2, first bad pivot), the third an int64 in a double's slot
+  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(red, nc, red + nc, nc, bad, res, reinterpret_cast<int64_t*>(res) + 2,
+                                           2 * nc, nc, 3);
+  TGP_HIP_TRY(hipGetLastError());
+  std::vector<double> got(size_t(3 * nb));
+  TGP_HIP_TRY(hipMemcpyAsync(got.data(), res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t b = 0; b < nb; ++b) {
+    int64_t first_bad;
+    memcpy(&first_bad, &got[size_t(3 * b + 2)], sizeof(first_bad));
+    info[b] = first_bad == INT64_MAX ? 0 : int32_t(first_bad + 1);
+    out[b] = info[b] ? NAN : logprob_value(got[size_t(3 * b + 1)], got[size_t(3 * b)], n);
+  }
   return TGP_OK;
 }
 
@@ -1483,7 +1627,8 @@ int tgp_qsep_destroy(tgp_qsep* q) {
     hipStreamSynchronize(q->ctx->stream);
   }
   void* bufs[] = {q->model, q->t,    q->noise, q->c,     q->w,    q->io,   q->io2,  q->work, q->red,
-                  q->bad,   q->pred, q->pidx,  q->gkeep, q->gdir, q->gtan, q->gred, q->gout, q->gvec};
+                  q->bad,   q->pred, q->pidx,  q->gkeep, q->gdir, q->gtan, q->gred, q->gout, q->gvec,
+                  q->bat};
   for (void* b : bufs)
     if (b) hipFree(b);
   delete q;
@@ -1514,7 +1659,7 @@ int tgp_qsep_factor_logprob(tgp_qsep* q, const double* leaves, int32_t nleaves, 
   TGP_HIP_TRY(hipMemcpyAsync(q->io, resid_host, size_t(q->n) * sizeof(double), hipMemcpyHostToDevice, st));
   TGP_TRY(affine(q, TGP_QS_FWD, 1, q->io, q->io2, &zz));
   TGP_HIP_TRY(hipStreamSynchronize(st));
-  *out = -0.5 * zz - 0.5 * q->logdet - 0.5 * double(q->n) * kLog2Pi;
+  *out = logprob_value(zz, q->logdet, q->n);
   return TGP_OK;
 }
 
@@ -1538,7 +1683,7 @@ int tgp_qsep_grad(tgp_qsep* q, const double* leaves, int32_t nleaves, const int3
   TGP_HIP_TRY(hipMemcpyAsync(q->io, resid_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
   TGP_TRY(affine(q, TGP_QS_FWD, 1, q->io, q->io2, &zz, q->gkeep + nc * WAVE));
   TGP_HIP_TRY(hipStreamSynchronize(st));
-  *out = -0.5 * zz - 0.5 * q->logdet - 0.5 * double(n) * kLog2Pi;
+  *out = logprob_value(zz, q->logdet, n);
   if (q->info != 0) {  // failed factor: c and w are not a factor of anything
     for (int32_t d = 0; d < ndir; ++d) dout[d] = NAN;
     for (int64_t i = 0; i < n; ++i) {
@@ -1549,6 +1694,52 @@ int tgp_qsep_grad(tgp_qsep* q, const double* leaves, int32_t nleaves, const int3
   }
   if (ndir > 0) TGP_TRY(grad_directions(q, ndir, dleaves, dh, dPinf, dout));
   if (gnoise_host || alpha_host) TGP_TRY(grad_vectors(q, gnoise_host, alpha_host));
+  return TGP_OK;
+}
+
+int tgp_qsep_logprob_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                           int32_t J, const double* hvec, const double* Pinf, const double* noise_host,
+                           int64_t noise_stride, const double* resid_host, int64_t resid_stride, int32_t* info,
+                           double* out, int32_t* nchains) {
+  QS_GUARD(q);
+  TGP_ARG_CHECK(nb >= 0, "negative number of models (%d)", nb);
+  if (nchains) *nchains = 0;
+  if (nb == 0) return TGP_OK;
+  const int64_t n = q->n, nc = q->nchunks;
+  TGP_ARG_CHECK(leaves && state_map && hvec && Pinf, "null model array");
+  TGP_ARG_CHECK(noise_host && resid_host && info && out, "null argument");
+  TGP_ARG_CHECK(noise_stride == 0 || noise_stride == n, "the noise stride must be 0 (shared) or n (got %lld)",
+                (long long)noise_stride);
+  TGP_ARG_CHECK(resid_stride == 0 || resid_stride == n, "the residual stride must be 0 (shared) or n (got %lld)",
+                (long long)resid_stride);
+  std::vector<QModel> models(size_t(nb), QModel{});
+  for (int64_t b = 0; b < nb; ++b)
+    TGP_TRY(pack_model(&models[size_t(b)], leaves + b * nleaves * 5, nleaves, state_map, J, hvec + b * J,
+                       Pinf + b * J * J));
+  const BatchLayout lay = batch_layout(n, nc, J, noise_stride != 0, resid_stride != 0);
+  const int64_t budget = BATCH_SCRATCH_BYTES / int64_t(sizeof(double)) - lay.fixed;
+  TGP_ARG_CHECK(budget >= lay.per_member,
+                "the batch's scratch for one model (%lld doubles, %lld shared) exceeds its cap of %lld bytes",
+                (long long)lay.per_member, (long long)lay.fixed, (long long)BATCH_SCRATCH_BYTES);
+  const int64_t cap = std::min<int64_t>({int64_t(nb), BATCH_MAX_MEMBERS, budget / lay.per_member});
+  TGP_TRY(grow(&q->bat, &q->bat_elems, lay.fixed + cap * lay.per_member));
+  hipStream_t st = q->ctx->stream;
+  double* shared = q->bat + BATCH_MAX_MEMBERS * MODEL_DOUBLES;
+  if (!noise_stride) {
+    TGP_HIP_TRY(hipMemcpyAsync(shared, noise_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+    shared += n;
+  } else {
+    shared += cap * n;
+  }
+  if (!resid_stride)
+    TGP_HIP_TRY(hipMemcpyAsync(shared, resid_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+  int32_t chains = 0;
+  for (int64_t b0 = 0; b0 < nb; b0 += cap, ++chains) {
+    const int64_t cnt = std::min<int64_t>(cap, nb - b0);
+    TGP_TRY(batch_chain(q, lay, cap, cnt, models.data() + b0, J, noise_host + b0 * noise_stride, noise_stride,
+                        resid_host + b0 * resid_stride, resid_stride, info + b0, out + b0));
+  }
+  if (nchains) *nchains = chains;
   return TGP_OK;
 }
 

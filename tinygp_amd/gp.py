@@ -148,6 +148,39 @@ class GaussianProcess:
             return fused(resid)
         return self._compute_log_prob(self.solver.solve_triangular(resid))
 
+    def log_probability_batch(self, y, kernels, *, diags=None, means=None):
+        """The log-probabilities of ``y`` under B models that share this GP's coordinates, evaluated together
+        (the reference's ``jax.vmap`` over the function that builds the GP): the walkers of an ensemble sampler, the
+        starts of an optimiser, a grid over a period.
+
+        ``kernels``: B kernels of one structure.  ``diags``: ``None`` (this GP's noise), (B,) one value per member or
+        (B, N) diagonals.  ``means``: ``None`` (this GP's mean vector), (B,) constants or (B, N) vectors.  Returns B
+        values; member b equals ``GaussianProcess(kernels[b], X, diag=diags[b], mean=means[b]).log_probability(y)``
+        to the bit.  Needs a solver with ``log_probability_batch`` (:class:`tinygp_amd.solvers.QuasisepSolver`)."""
+        fused = getattr(self.solver, "log_probability_batch", None)
+        if fused is None:
+            raise NotImplementedError(f"{type(self.solver).__name__} has no log_probability_batch: batches of models "
+                                      "are evaluated by QuasisepSolver (a kernels.quasisep kernel on sorted 1-D "
+                                      "inputs)")
+        kernels = list(kernels)
+        nb, n = len(kernels), self.num_data
+
+        def per_member(a, what):  # (B,) -> (B, N) of this GP's dtype, (B, N) kept
+            a = np.asarray(a)
+            if a.shape not in ((nb,), (nb, n)):
+                raise ValueError(f"{what} must have shape ({nb},) or ({nb}, {n}); got {a.shape}")
+            a = a.astype(self.dtype, copy=False)
+            return np.broadcast_to(a[:, None], (nb, n)) if a.ndim == 1 else a
+
+        if means is None:
+            resid = self._residual(y)
+        else:
+            resid = (np.asarray(y) - per_member(means, "means")).astype(self.dtype, copy=False)
+            if resid.shape != (nb, n):
+                raise ValueError(f"y must broadcast against the means of shape ({nb}, {n})")
+        noise = None if diags is None else per_member(diags, "diags")
+        return fused(kernels, resid, noise)
+
     def log_probability_and_grad(self, y):
         """``(log_probability, grads)``; see :meth:`solvers.DirectSolver.log_probability_and_grad`.
         ``grads["kernel"]`` follows ``self.kernel.parameters()``.  A solver with a ``value_and_grad`` of its own

@@ -33,7 +33,7 @@ from tinygp_amd.kernels import base
 from tinygp_amd.kernels.distance import L1Distance
 
 __all__ = ["Quasisep", "Sum", "Product", "Scale", "Celerite", "SHO", "Exp", "Matern32", "Matern52", "Cosine",
-           "MAX_STATE", "MAX_LEAVES", "SSMTangent", "leaf_phi", "leaf_dphi", "model_dphi"]
+           "MAX_STATE", "MAX_LEAVES", "SSMTangent", "leaf_phi", "leaf_dphi", "model_dphi", "pack_batch"]
 
 MAX_STATE = 8   # TGP_QSEP_MAX_J of include/tgp_hip.h
 MAX_LEAVES = 8  # TGP_QSEP_MAX_LEAVES
@@ -75,6 +75,34 @@ def _coords(X) -> np.ndarray:
     if X.ndim != 1:
         raise ValueError(f"quasiseparable kernels take coordinates of shape (N,) or (N, 1); got {X.shape}")
     return X
+
+
+def pack_batch(kernels):
+    """Lower B kernels of one structure for ``tgp_qsep_logprob_batch``: ``(leaves (B, L, 5), state_map (J, L) int32,
+    h (B, J), Pinf (B, J, J))``, float64 and contiguous.  Every member must have the first one's state dimension, leaf
+    count and ``state_map``; leaf kinds may differ (an ``SHO`` in another damping regime).  A mismatch raises
+    ``ValueError`` naming the member and what differs; J > 8 raises :class:`tinygp_amd._device.DeviceLimit`."""
+    kernels = list(kernels)
+    if not kernels:
+        raise ValueError("pack_batch needs at least one kernel")
+    for i, k in enumerate(kernels):
+        if not isinstance(k, Quasisep):
+            raise TypeError(f"kernel {i} of the batch is no kernels.quasisep.Quasisep kernel ({type(k).__name__})")
+    ssms = [k._lower_ssm() for k in kernels]
+    first = ssms[0]
+    smap = np.ascontiguousarray(first.state_map, dtype=np.int32)
+    for i, s in enumerate(ssms[1:], start=1):
+        if s.J != first.J:
+            raise ValueError(f"kernel {i} of the batch has state dimension J = {s.J}, kernel 0 has J = {first.J}")
+        if len(s.leaves) != len(first.leaves):
+            raise ValueError(f"kernel {i} of the batch has {len(s.leaves)} leaf kernels, kernel 0 has "
+                             f"{len(first.leaves)}")
+        if not np.array_equal(np.asarray(s.state_map, dtype=np.int32), smap):
+            raise ValueError(f"kernel {i} of the batch has another state_map than kernel 0: the sums and products "
+                             "must be nested alike")
+    stack = lambda field: np.ascontiguousarray(  # noqa: E731
+        np.stack([np.asarray(getattr(s, field), dtype=np.float64) for s in ssms]))
+    return stack("leaves"), smap, stack("h"), stack("Pinf")
 
 
 class Quasisep(base.Kernel):

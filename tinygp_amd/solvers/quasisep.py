@@ -5,8 +5,9 @@ factor described by O(N J) numbers (``c_n``, ``w_n``; ``tests/_quasisep_np.py`` 
 ``tgp_qsep`` handle (C ABI, ``include/tgp_hip.h``) keeps t, the noise and that factor resident on the device; the
 factorisation, both triangular solves and ``L @ z`` are chunked reduce-then-scan recurrences in
 ``csrc/qsep.hip``, and so are the conditional mean and variance at M test points (``predict_mean_var``; O(N + M),
-nothing of size N x M), the same for every term of a sum at once (``predict_terms``; also at the data themselves)
-and the gradient of the log-probability (``value_and_grad``; O(N) per parameter).  Nothing
+nothing of size N x M), the same for every term of a sum at once (``predict_terms``; also at the data themselves),
+the gradient of the log-probability (``value_and_grad``; O(N) per parameter) and the log-probabilities of many
+hyper-parameter sets over the one series in one launch chain (``log_probability_batch``).  Nothing
 of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
 reference); the full conditional covariance and conditioning on another kernel keep the reference's dense route.
 
@@ -270,6 +271,44 @@ class QuasisepSolver(Solver):
         if self._info or not np.isfinite(v):
             v = -np.inf
         return self.dtype.type(v)
+
+    def log_probability_batch(self, kernels, resid, noise=None, *, return_info: bool = False):
+        """The log-probabilities of B models over this solver's coordinates, evaluated together on the device
+        (``tgp_qsep_logprob_batch``: one model per grid row, so that a short series still fills the card).
+
+        ``kernels``: a sequence of B :class:`~tinygp_amd.kernels.quasisep.Quasisep` kernels of one structure
+        (:func:`tinygp_amd.kernels.quasisep.pack_batch`).  ``resid``: (N,) shared or (B, N).  ``noise``: ``None`` (the
+        solver's own diagonal), (N,) shared or (B, N) diagonals.  Returns B values, each with the bits of
+        :meth:`log_probability` of a solver built with that member's kernel and noise; a failed or non-finite member
+        gives ``-inf``.  With ``return_info`` also the B ``info`` values.  fp32 inputs are computed in fp64 and
+        returned as fp32.  The solver's own kernel and factor are neither used nor changed."""
+        from tinygp_amd.kernels.quasisep import pack_batch
+
+        kernels = list(kernels)
+        nb = len(kernels)
+        if nb == 0:
+            out = np.empty(0, dtype=self.dtype)
+            return (out, np.empty(0, dtype=np.int32)) if return_info else out
+        leaves, smap, h, P = pack_batch(kernels)
+
+        def rows(a, what):  # (N,) -> shared, (B, N) -> one per member
+            a = np.asarray(a)
+            if a.shape == (self.n,):
+                return _f64(a), 0
+            if a.shape == (nb, self.n):
+                return _f64(a), self.n
+            raise ValueError(f"{what} must have shape ({self.n},) or ({nb}, {self.n}); got {a.shape}")
+
+        r, r_stride = rows(resid, "resid")
+        d, d_stride = (self._noise, 0) if noise is None else rows(noise, "noise")
+        info, out = np.zeros(nb, dtype=np.int32), np.empty(nb)
+        _ffi.check(_ffi.lib().tgp_qsep_logprob_batch(self._handle, nb, _ffi.ptr(leaves), leaves.shape[1],
+                                                     _ffi.ptr(smap), h.shape[1], _ffi.ptr(h), _ffi.ptr(P),
+                                                     _ffi.ptr(d), d_stride, _ffi.ptr(r), r_stride, _ffi.ptr(info),
+                                                     _ffi.ptr(out), None), "tgp_qsep_logprob_batch")
+        out[(info != 0) | ~np.isfinite(out)] = -np.inf
+        out = out.astype(self.dtype, copy=False)
+        return (out, info) if return_info else out
 
     def alpha(self, resid):
         """``(K^-1 r, log_probability)``."""
