@@ -9,9 +9,9 @@
 //   1. qs_fold     one wavefront per chunk folds its steps into one associative filtering element (A, C, J) of
 //                  the parallel Kalman filter (Sarkka & Garcia-Fernandez 2021, covariance part).  One scalar
 //                  observation per step: the step's J is rank one and the fold needs no inverse (Sherman-Morrison).
-//   2. qs_reduce / qs_down   hierarchical exclusive scan of the chunk elements, 64 per group; the full combine
-//                  (a J x J solve by Gauss-Jordan with partial pivoting) runs only here.  Going down, only the
-//                  filtered covariance is carried: P <- A (I + P J)^-1 P A^T + C.
+//   2. qs_scan_reduce / qs_scan_down   hierarchical exclusive scan of the chunk elements, 64 per group; the full
+//                  combine (a J x J solve by Gauss-Jordan with partial pivoting) runs only here.  Going down, only
+//                  the filtered covariance is carried: P <- A (I + P J)^-1 P A^T + C.
 //   3. qs_emit     each chunk re-runs the sequential recursion from its incoming P, writing c_n, w_n and a
 //                  per-chunk sum of log c_n and its first non-positive pivot.
 // L^-1 y, L^-T y and L z are affine recurrences g <- M_n g + v_n over a J-vector per right-hand side (the M_n
@@ -19,16 +19,17 @@
 // A_n is regenerated from dt_n = t_n - t_{n-1} (dt_0 = 0, A = I) in every kernel instead of being stored.
 // Prediction at test points (qs_pred_*) runs two more scans of the same shape, one per direction, whose elements pair
 // a congruence recurrence X <- M X M^T + V (J x J) with an affine one f <- Mf f + Vf (J-vector); see below.
+// Phase 2 is one kernel pair for every recurrence, instantiated over the four element types of "scan policies" below.
 //
 // Layout: one wavefront holds a J x J matrix (or a J x 8 block of right-hand sides) as one entry per lane,
 // lane = 8 r + c; entries outside J x J are zero.  Products read operands through __shfl.  Every reduction runs in
 // a fixed order, so results are bit-identical from run to run.  Arithmetic is fp64 throughout.
 //
-// Batches of models: the kernels of the fused log-probability (qs_fold, qs_reduce / qs_down, qs_emit, qs_aff_fold,
-// qs_aff_reduce / qs_aff_down, qs_aff_emit, qs_finish) serve one model per blockIdx.y (qs_finish: per block) over the
-// shared t: model mp[blockIdx.y], every array of that member `stride` doubles after its neighbour's.  A single
-// evaluation is the batch of one (grid y = 1, where no stride matters), so both run the same code and a member's
-// result has the bits of its single call.
+// Batches of models: the kernels of the fused log-probability (qs_fold, qs_emit, qs_aff_fold, qs_aff_emit, qs_finish)
+// and both scan kernels serve one model per blockIdx.y (qs_finish: per block) over the shared t: model mp[blockIdx.y],
+// every array of that member `stride` doubles after its neighbour's.  A single evaluation is the batch of one (grid
+// y = 1, where no stride matters): launch_factor and launch_affine enqueue the chain for both, so a member's result
+// has the bits of its single call.
 #include "tgp_common.h"
 
 #include <algorithm>
@@ -332,7 +333,7 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_fold(const QModel* __restrict__
   e[L.lane] = A, e[WAVE + L.lane] = C, e[2 * WAVE + L.lane] = Jm;
 }
 
-// ---- factor, phase 2: reduce groups of elements / carry the filtered covariance down --------------------------
+// ---- factor, phase 2: the combine of two filtering elements (the scan itself: qs_scan_reduce / qs_scan_down) ------
 __device__ void ric_combine(double& A, double& C, double& Jm, double A2, double C2, double J2, int J, int r,
                             int c) {
   double G = mm(C, J2, J, r, c) + ((r == c && r < J) ? 1.0 : 0.0);
@@ -344,45 +345,129 @@ __device__ void ric_combine(double& A, double& C, double& Jm, double A2, double 
   A = An, C = Cn, Jm = Jn;
 }
 
-// in, out (and the prefixes of qs_down): member blockIdx.y's lie work_stride doubles after its neighbour's
-__global__ __launch_bounds__(WAVE * WPB) void qs_reduce(const QModel* __restrict__ mp, const double* __restrict__ in,
-                                                        int64_t count, double* __restrict__ out, int64_t ngroups,
-                                                        int64_t work_stride) {
+// ---- scan policies: the element types of phase 2 ------------------------------------------------------------------
+// An element is ESZ lane-blocks (one double per lane each), the state carried down PSZ of them.  combine(a, x) makes
+// the accumulated element a that of "a, then x"; advance(p, x) takes the state p across x.  All but the Riccati scan
+// are built from two steps over (M2, V2) blocks:
+//   lin_step   X <- M2 X + V2              cong_step   X <- sym(M2 X M2^T + V2)
+//   ScanRiccati  (A, C, J)       | P       ric_combine; down: X = (I + P J2)^-1 P by gj_solve, then cong_step(A2, X, C2)
+//   ScanAffine   (M, V)          | X       M <- M2 M, V by lin_step
+//   ScanCong     (M, V)          | X       M <- M2 M, V by cong_step
+//   ScanPred     (M, V, Mf, Vf)  | (X, f)  a ScanCong on blocks 0-1 beside a ScanAffine on blocks 2-3
+__device__ __forceinline__ double lin_step(double M2, double X, double V2, int J, int r, int c) {
+  return mm(M2, X, J, r, c) + V2;
+}
+__device__ __forceinline__ double cong_step(double M2, double X, double V2, int J, int r, int c) {
+  return symm(mm_nt(mm(M2, X, J, r, c), M2, J, r, c) + V2, r, c);
+}
+
+struct ScanRiccati {
+  static constexpr int ESZ = 3, PSZ = 1;
+  static __device__ __forceinline__ void combine(double* a, const double* x, int J, int r, int c) {
+    ric_combine(a[0], a[1], a[2], x[0], x[1], x[2], J, r, c);
+  }
+  static __device__ __forceinline__ void advance(double* p, const double* x, int J, int r, int c) {
+    double G = mm(p[0], x[2], J, r, c) + ((r == c && r < J) ? 1.0 : 0.0);
+    double X = p[0], dummy = 0.0;
+    gj_solve(G, X, dummy, J, r, c);  // (I + P J2)^-1 P
+    p[0] = cong_step(x[0], X, x[1], J, r, c);
+  }
+};
+
+struct ScanAffine {
+  static constexpr int ESZ = 2, PSZ = 1;
+  static __device__ __forceinline__ void combine(double* a, const double* x, int J, int r, int c) {
+    const double Mn = mm(x[0], a[0], J, r, c);
+    a[1] = lin_step(x[0], a[1], x[1], J, r, c);
+    a[0] = Mn;
+  }
+  static __device__ __forceinline__ void advance(double* p, const double* x, int J, int r, int c) {
+    p[0] = lin_step(x[0], p[0], x[1], J, r, c);
+  }
+};
+
+struct ScanCong {
+  static constexpr int ESZ = 2, PSZ = 1;
+  static __device__ __forceinline__ void combine(double* a, const double* x, int J, int r, int c) {
+    a[1] = cong_step(x[0], a[1], x[1], J, r, c);
+    a[0] = mm(x[0], a[0], J, r, c);
+  }
+  static __device__ __forceinline__ void advance(double* p, const double* x, int J, int r, int c) {
+    p[0] = cong_step(x[0], p[0], x[1], J, r, c);
+  }
+};
+
+struct ScanPred {
+  static constexpr int ESZ = 4, PSZ = 2;
+  static __device__ __forceinline__ void combine(double* a, const double* x, int J, int r, int c) {
+    ScanCong::combine(a, x, J, r, c);
+    ScanAffine::combine(a + 2, x + 2, J, r, c);
+  }
+  static __device__ __forceinline__ void advance(double* p, const double* x, int J, int r, int c) {
+    ScanCong::advance(p, x, J, r, c);
+    ScanAffine::advance(p + 1, x + 2, J, r, c);
+  }
+};
+
+// this lane's entries of NB consecutive lane-blocks
+template <int NB>
+__device__ __forceinline__ void load_blocks(double* v, const double* p, int lane) {
+#pragma unroll
+  for (int k = 0; k < NB; ++k) v[k] = p[k * WAVE + lane];
+}
+template <int NB>
+__device__ __forceinline__ void store_blocks(double* p, const double* v, int lane) {
+#pragma unroll
+  for (int k = 0; k < NB; ++k) p[k * WAVE + lane] = v[k];
+}
+
+// One level of a scan: `width` independent scans over `count` elements each, interleaved as element * width + scan;
+// one wavefront per group of GROUP elements of one scan.  Member blockIdx.y: model mp[blockIdx.y], its in, out and
+// prefixes work_stride doubles after its neighbour's.  qs_scan_reduce folds each group into one element of the next
+// level; qs_scan_down writes the state before every element of a group from the state before the group (prefix_in:
+// one per group; nullptr: the top level, which starts from 0).
+template <class S>
+__global__ __launch_bounds__(WAVE * WPB) void qs_scan_reduce(const QModel* __restrict__ mp,
+                                                             const double* __restrict__ in, int64_t count,
+                                                             int64_t width, double* __restrict__ out, int64_t ngroups,
+                                                             int64_t work_stride) {
   const Lane L;
-  if (L.wave >= ngroups) return;
+  if (L.wave >= ngroups * width) return;
   const int64_t mem = blockIdx.y;
   const int J = mp[mem].J;
   in += mem * work_stride, out += mem * work_stride;
-  const int64_t b = L.wave * GROUP, e = min(count, b + GROUP);
-  double A = in[b * 3 * WAVE + L.lane], C = in[b * 3 * WAVE + WAVE + L.lane], Jm = in[b * 3 * WAVE + 2 * WAVE + L.lane];
+  const int64_t g = L.wave / width, d = L.wave % width;
+  const int64_t b = g * GROUP, e = min(count, b + GROUP);
+  double a[S::ESZ], x[S::ESZ];
+  load_blocks<S::ESZ>(a, in + (b * width + d) * S::ESZ * WAVE, L.lane);
   for (int64_t i = b + 1; i < e; ++i) {
-    const double* x = in + i * 3 * WAVE;
-    ric_combine(A, C, Jm, x[L.lane], x[WAVE + L.lane], x[2 * WAVE + L.lane], J, L.r, L.c);
+    load_blocks<S::ESZ>(x, in + (i * width + d) * S::ESZ * WAVE, L.lane);
+    S::combine(a, x, J, L.r, L.c);
   }
-  double* o = out + L.wave * 3 * WAVE;
-  o[L.lane] = A, o[WAVE + L.lane] = C, o[2 * WAVE + L.lane] = Jm;
+  store_blocks<S::ESZ>(out + L.wave * S::ESZ * WAVE, a, L.lane);
 }
 
-// prefix_in: one state per group (nullptr: the top level, start from P = 0); prefix_out: one per element
-__global__ __launch_bounds__(WAVE * WPB) void qs_down(const QModel* __restrict__ mp, const double* __restrict__ elem,
-                                                      int64_t count, const double* __restrict__ prefix_in,
-                                                      double* __restrict__ prefix_out, int64_t ngroups,
-                                                      int64_t work_stride) {
+template <class S>
+__global__ __launch_bounds__(WAVE * WPB) void qs_scan_down(const QModel* __restrict__ mp,
+                                                           const double* __restrict__ elem, int64_t count,
+                                                           int64_t width, const double* __restrict__ prefix_in,
+                                                           double* __restrict__ prefix_out, int64_t ngroups,
+                                                           int64_t work_stride) {
   const Lane L;
-  if (L.wave >= ngroups) return;
+  if (L.wave >= ngroups * width) return;
   const int64_t mem = blockIdx.y;
-  const int J = mp[mem].J, r = L.r, c = L.c;
+  const int J = mp[mem].J;
   elem += mem * work_stride, prefix_out += mem * work_stride;
-  double P = prefix_in ? prefix_in[mem * work_stride + L.wave * WAVE + L.lane] : 0.0;
-  const int64_t b = L.wave * GROUP, e = min(count, b + GROUP);
+  const int64_t g = L.wave / width, d = L.wave % width;
+  const int64_t b = g * GROUP, e = min(count, b + GROUP);
+  double p[S::PSZ], x[S::ESZ];
+#pragma unroll
+  for (int k = 0; k < S::PSZ; ++k) p[k] = 0.0;
+  if (prefix_in) load_blocks<S::PSZ>(p, prefix_in + mem * work_stride + L.wave * S::PSZ * WAVE, L.lane);
   for (int64_t i = b; i < e; ++i) {
-    prefix_out[i * WAVE + L.lane] = P;
-    const double* x = elem + i * 3 * WAVE;
-    const double A2 = x[L.lane], C2 = x[WAVE + L.lane], J2 = x[2 * WAVE + L.lane];
-    double G = mm(P, J2, J, r, c) + ((r == c && r < J) ? 1.0 : 0.0);
-    double X = P, dummy = 0.0;
-    gj_solve(G, X, dummy, J, r, c);  // (I + P J2)^-1 P
-    P = symm(mm_nt(mm(A2, X, J, r, c), A2, J, r, c) + C2, r, c);
+    store_blocks<S::PSZ>(prefix_out + (i * width + d) * S::PSZ * WAVE, p, L.lane);
+    load_blocks<S::ESZ>(x, elem + (i * width + d) * S::ESZ * WAVE, L.lane);
+    S::advance(p, x, J, L.r, L.c);
   }
 }
 
@@ -468,14 +553,18 @@ __device__ __forceinline__ double step_apply(int op, const QModel& m, const Step
   return f + d.w_r * y;
 }
 
-__device__ __forceinline__ int64_t step_index(int op, int64_t k, int64_t nchunks, int64_t lc, int64_t n, int64_t j,
-                                     int64_t* len) {
-  // scan position k -> chunk; BWD walks the chunks and their steps backwards
-  const int64_t chunk = op == TGP_QS_BWD ? nchunks - 1 - k : k;
-  const int64_t n0 = chunk * lc, n1 = min(n, n0 + lc);
-  *len = n1 - n0;
-  return op == TGP_QS_BWD ? n1 - 1 - j : n0 + j;
-}
+// The chunk at scan position k: its steps [n0, n1) and its j-th step.  A backward walk (L^-T y, the backward pass of
+// the prediction) takes the chunks and their steps from the end.
+struct Chunk {
+  int64_t n0, n1;
+  bool back;
+  __device__ Chunk(bool back_, int64_t k, int64_t nchunks, int64_t lc, int64_t n) : back(back_) {
+    n0 = (back ? nchunks - 1 - k : k) * lc;
+    n1 = min(n, n0 + lc);
+  }
+  __device__ int64_t len() const { return n1 - n0; }
+  __device__ int64_t step(int64_t j) const { return back ? n1 - 1 - j : n0 + j; }
+};
 
 __global__ __launch_bounds__(WAVE * WPB) void qs_aff_fold(int op, const QModel* __restrict__ mp,
                                                           const double* __restrict__ t, const double* __restrict__ cbuf,
@@ -491,10 +580,9 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_fold(int op, const QModel* 
   const int r = L.r, c = L.c;
   const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
   double M = (r == c && r < m.J) ? 1.0 : 0.0, V = 0.0, o;
-  int64_t len;
-  step_index(op, k, nchunks, lc, n, 0, &len);
-  for (int64_t j = 0; j < len; ++j) {
-    const int64_t i = step_index(op, k, nchunks, lc, n, j, &len);
+  const Chunk ch(op == TGP_QS_BWD, k, nchunks, lc, n);
+  for (int64_t j = 0, len = ch.len(); j < len; ++j) {
+    const int64_t i = ch.step(j);
     const StepData d = step_data(m, t, cbuf, wbuf, i, r, c);
     const double yv = col < nrhs ? y[i * nrhs + col] : 0.0;
     M = step_apply(op, m, d, M, 0.0, &o, r, c);
@@ -502,49 +590,6 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_fold(int op, const QModel* 
   }
   double* e = elem + L.wave * 2 * WAVE;
   e[L.lane] = M, e[WAVE + L.lane] = V;
-}
-
-__global__ __launch_bounds__(WAVE * WPB) void qs_aff_reduce(const QModel* __restrict__ mp,
-                                                            const double* __restrict__ in, int64_t count, int64_t ncg,
-                                                            double* __restrict__ out, int64_t ngroups,
-                                                            int64_t work_stride) {
-  const Lane L;
-  if (L.wave >= ngroups * ncg) return;
-  const int64_t mem = blockIdx.y;
-  const int J = mp[mem].J;
-  in += mem * work_stride, out += mem * work_stride;
-  const int64_t g = L.wave / ncg, cg = L.wave % ncg;
-  const int64_t b = g * GROUP, e = min(count, b + GROUP);
-  double M = in[(b * ncg + cg) * 2 * WAVE + L.lane], V = in[(b * ncg + cg) * 2 * WAVE + WAVE + L.lane];
-  for (int64_t i = b + 1; i < e; ++i) {
-    const double* x = in + (i * ncg + cg) * 2 * WAVE;
-    const double M2 = x[L.lane], V2 = x[WAVE + L.lane];
-    const double Mn = mm(M2, M, J, L.r, L.c);
-    V = mm(M2, V, J, L.r, L.c) + V2;
-    M = Mn;
-  }
-  double* o = out + L.wave * 2 * WAVE;
-  o[L.lane] = M, o[WAVE + L.lane] = V;
-}
-
-__global__ __launch_bounds__(WAVE * WPB) void qs_aff_down(const QModel* __restrict__ mp,
-                                                          const double* __restrict__ elem, int64_t count, int64_t ncg,
-                                                          const double* __restrict__ prefix_in,
-                                                          double* __restrict__ prefix_out, int64_t ngroups,
-                                                          int64_t work_stride) {
-  const Lane L;
-  if (L.wave >= ngroups * ncg) return;
-  const int64_t mem = blockIdx.y;
-  const int J = mp[mem].J;
-  elem += mem * work_stride, prefix_out += mem * work_stride;
-  const int64_t g = L.wave / ncg, cg = L.wave % ncg;
-  double X = prefix_in ? prefix_in[mem * work_stride + L.wave * WAVE + L.lane] : 0.0;
-  const int64_t b = g * GROUP, e = min(count, b + GROUP);
-  for (int64_t i = b; i < e; ++i) {
-    prefix_out[(i * ncg + cg) * WAVE + L.lane] = X;
-    const double* x = elem + (i * ncg + cg) * 2 * WAVE;
-    X = mm(x[L.lane], X, J, L.r, L.c) + x[WAVE + L.lane];
-  }
 }
 
 __global__ __launch_bounds__(WAVE * WPB) void qs_aff_emit(int op, const QModel* __restrict__ mp,
@@ -563,10 +608,9 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_emit(int op, const QModel* 
   const int r = L.r, c = L.c;
   const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
   double X = prefix[L.wave * WAVE + L.lane], o = 0.0, acc = 0.0;
-  int64_t len;
-  step_index(op, k, nchunks, lc, n, 0, &len);
-  for (int64_t j = 0; j < len; ++j) {
-    const int64_t i = step_index(op, k, nchunks, lc, n, j, &len);
+  const Chunk ch(op == TGP_QS_BWD, k, nchunks, lc, n);
+  for (int64_t j = 0, len = ch.len(); j < len; ++j) {
+    const int64_t i = ch.step(j);
     const StepData d = step_data(m, t, cbuf, wbuf, i, r, c);
     const double yv = col < nrhs ? y[i * nrhs + col] : 0.0;
     X = step_apply(op, m, d, X, yv, &o, r, c);
@@ -666,14 +710,6 @@ __device__ __forceinline__ double lin(int dir, double A, double X, int J, int r,
   return dir == 0 ? mm(A, X, J, r, c) : mm_tn(A, X, J, r, c);
 }
 
-// scan position k -> chunk and its j-th step (the backward direction walks chunks and steps from the end)
-__device__ __forceinline__ int64_t pred_index(int dir, int64_t k, int64_t nchunks, int64_t lc, int64_t n, int64_t j,
-                                              int64_t* n0, int64_t* n1) {
-  const int64_t chunk = dir ? nchunks - 1 - k : k;
-  *n0 = chunk * lc, *n1 = min(n, *n0 + lc);
-  return dir ? *n1 - 1 - j : *n0 + j;
-}
-
 __global__ __launch_bounds__(WAVE * WPB) void qs_pred_fold(int dir, int want_mean, int want_var,
                                                            const QModel* __restrict__ mp, const double* __restrict__ t,
                                                            const double* __restrict__ cbuf,
@@ -687,10 +723,9 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_fold(int dir, int want_mea
   const double Ph_r = Xh(m, m.P[L.lane], r);
   const double I = (r == c && r < J) ? 1.0 : 0.0;
   double M = I, V = 0.0, Mf = I, Vf = 0.0;
-  int64_t n0, n1;
-  pred_index(dir, L.wave, nchunks, lc, n, 0, &n0, &n1);
-  for (int64_t j = 0; j < n1 - n0; ++j) {
-    const int64_t i = pred_index(dir, L.wave, nchunks, lc, n, j, &n0, &n1);
+  const Chunk ch(dir != 0, L.wave, nchunks, lc, n);
+  for (int64_t j = 0, len = ch.len(); j < len; ++j) {
+    const int64_t i = ch.step(j);
     const PredStep s = pred_step(dir, m, t, cbuf, wbuf, want_mean ? alpha : nullptr, n, i, r, c, Ph_r);
     if (want_var) {
       M = lin(dir, s.T, M, J, r, c);
@@ -703,47 +738,6 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_fold(int dir, int want_mea
   }
   double* e = elem + L.wave * 4 * WAVE;
   e[L.lane] = M, e[WAVE + L.lane] = V, e[2 * WAVE + L.lane] = Mf, e[3 * WAVE + L.lane] = Vf;
-}
-
-__global__ __launch_bounds__(WAVE * WPB) void qs_pred_reduce(const QModel* __restrict__ mp,
-                                                             const double* __restrict__ in, int64_t count,
-                                                             double* __restrict__ out, int64_t ngroups) {
-  const Lane L;
-  if (L.wave >= ngroups) return;
-  const int J = mp->J, r = L.r, c = L.c;
-  const int64_t b = L.wave * GROUP, e = min(count, b + GROUP);
-  const double* x = in + b * 4 * WAVE;
-  double M = x[L.lane], V = x[WAVE + L.lane], Mf = x[2 * WAVE + L.lane], Vf = x[3 * WAVE + L.lane];
-  for (int64_t i = b + 1; i < e; ++i) {
-    x = in + i * 4 * WAVE;
-    const double M2 = x[L.lane], Mf2 = x[2 * WAVE + L.lane];
-    V = symm(mm_nt(mm(M2, V, J, r, c), M2, J, r, c) + x[WAVE + L.lane], r, c);
-    M = mm(M2, M, J, r, c);
-    Vf = mm(Mf2, Vf, J, r, c) + x[3 * WAVE + L.lane];
-    Mf = mm(Mf2, Mf, J, r, c);
-  }
-  double* o = out + L.wave * 4 * WAVE;
-  o[L.lane] = M, o[WAVE + L.lane] = V, o[2 * WAVE + L.lane] = Mf, o[3 * WAVE + L.lane] = Vf;
-}
-
-// prefixes: (X, f), 2 x WAVE doubles per element; the top level starts from X = 0, f = 0
-__global__ __launch_bounds__(WAVE * WPB) void qs_pred_down(const QModel* __restrict__ mp,
-                                                           const double* __restrict__ elem, int64_t count,
-                                                           const double* __restrict__ prefix_in,
-                                                           double* __restrict__ prefix_out, int64_t ngroups) {
-  const Lane L;
-  if (L.wave >= ngroups) return;
-  const int J = mp->J, r = L.r, c = L.c;
-  double X = prefix_in ? prefix_in[L.wave * 2 * WAVE + L.lane] : 0.0;
-  double f = prefix_in ? prefix_in[L.wave * 2 * WAVE + WAVE + L.lane] : 0.0;
-  const int64_t b = L.wave * GROUP, e = min(count, b + GROUP);
-  for (int64_t i = b; i < e; ++i) {
-    prefix_out[i * 2 * WAVE + L.lane] = X, prefix_out[i * 2 * WAVE + WAVE + L.lane] = f;
-    const double* x = elem + i * 4 * WAVE;
-    const double M2 = x[L.lane], Mf2 = x[2 * WAVE + L.lane];
-    X = symm(mm_nt(mm(M2, X, J, r, c), M2, J, r, c) + x[WAVE + L.lane], r, c);
-    f = mm(Mf2, f, J, r, c) + x[3 * WAVE + L.lane];
-  }
 }
 
 // The test side of both serves is a J-vector g per term (gv: nterms x 8 doubles, rows zero-padded, wave-uniform
@@ -818,8 +812,8 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_emit(int dir, int want_mea
   const double Ph_r = Xh(m, Pl, r);
   const int64_t ptsz = int64_t(nterms) * PT;
   double X = prefix[L.wave * 2 * WAVE + L.lane], f = prefix[L.wave * 2 * WAVE + WAVE + L.lane];
-  int64_t n0, n1;
-  pred_index(dir, L.wave, nchunks, lc, n, 0, &n0, &n1);
+  const Chunk ch(dir != 0, L.wave, nchunks, lc, n);
+  const int64_t n0 = ch.n0, n1 = ch.n1;
   if (dir == 0) {
     // data point i serves the test points of interval i; chunk 0 also those before the first point (state 0)
     int64_t p = L.wave == 0 ? 0 : lower_bound_idx(sidx, mt, n0);
@@ -913,44 +907,6 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_gfac_fold(const QModel* __restr
   }
   double* e = elem + (L.wave * gridDim.y + blockIdx.y) * 2 * WAVE;
   e[L.lane] = M, e[WAVE + L.lane] = V;
-}
-
-// congruence scans X <- M X M^T + V over (M, V) elements, `width` of them interleaved
-__global__ __launch_bounds__(WAVE * WPB) void qs_cong_reduce(const QModel* __restrict__ mp,
-                                                             const double* __restrict__ in, int64_t count,
-                                                             int64_t width, double* __restrict__ out, int64_t ngroups) {
-  const Lane L;
-  if (L.wave >= ngroups * width) return;
-  const int J = mp->J, r = L.r, c = L.c;
-  const int64_t g = L.wave / width, d = L.wave % width;
-  const int64_t b = g * GROUP, e = min(count, b + GROUP);
-  double M = in[(b * width + d) * 2 * WAVE + L.lane], V = in[(b * width + d) * 2 * WAVE + WAVE + L.lane];
-  for (int64_t i = b + 1; i < e; ++i) {
-    const double* x = in + (i * width + d) * 2 * WAVE;
-    const double M2 = x[L.lane];
-    V = symm(mm_nt(mm(M2, V, J, r, c), M2, J, r, c) + x[WAVE + L.lane], r, c);
-    M = mm(M2, M, J, r, c);
-  }
-  double* o = out + L.wave * 2 * WAVE;
-  o[L.lane] = M, o[WAVE + L.lane] = V;
-}
-
-__global__ __launch_bounds__(WAVE * WPB) void qs_cong_down(const QModel* __restrict__ mp,
-                                                           const double* __restrict__ elem, int64_t count,
-                                                           int64_t width, const double* __restrict__ prefix_in,
-                                                           double* __restrict__ prefix_out, int64_t ngroups) {
-  const Lane L;
-  if (L.wave >= ngroups * width) return;
-  const int J = mp->J, r = L.r, c = L.c;
-  const int64_t g = L.wave / width, d = L.wave % width;
-  double X = prefix_in ? prefix_in[L.wave * WAVE + L.lane] : 0.0;
-  const int64_t b = g * GROUP, e = min(count, b + GROUP);
-  for (int64_t i = b; i < e; ++i) {
-    prefix_out[(i * width + d) * WAVE + L.lane] = X;
-    const double* x = elem + (i * width + d) * 2 * WAVE;
-    const double M2 = x[L.lane];
-    X = symm(mm_nt(mm(M2, X, J, r, c), M2, J, r, c) + x[WAVE + L.lane], r, c);
-  }
 }
 
 // dcbuf: ndir x n, dwbuf: ndir x n x J, dsum: ndir x nchunks
@@ -1049,9 +1005,9 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_invdiag_emit(const QModel* __re
   const QModel& m = *mp;
   const int J = m.J, r = L.r, c = L.c;
   double X = prefix[L.wave * 2 * WAVE + L.lane];
-  int64_t n0, n1;
-  pred_index(1, L.wave, nchunks, lc, n, 0, &n0, &n1);
-  for (int64_t i = n1 - 1; i >= n0; --i) {
+  const Chunk ch(true, L.wave, nchunks, lc, n);
+  for (int64_t j = 0, len = ch.len(); j < len; ++j) {
+    const int64_t i = ch.step(j);
     const PredStep s = pred_step(1, m, t, cbuf, wbuf, nullptr, n, i, r, c, 0.0);
     const double w_r = r < J ? wbuf[i * J + r] : 0.0;
     double u = 0.0, Ou = 0.0, q = 0.0;
@@ -1137,12 +1093,13 @@ namespace {
 
 using tgp::set_error;
 
-int grow(double** p, int64_t* have, int64_t want) {
+template <class T>
+int grow(T** p, int64_t* have, int64_t want) {
   if (*have >= want) return TGP_OK;
   if (*p) hipFree(*p);
   *p = nullptr;
   *have = 0;
-  TGP_HIP_TRY(hipMalloc(p, size_t(want) * sizeof(double)));
+  TGP_HIP_TRY(hipMalloc(p, size_t(want) * sizeof(T)));
   *have = want;
   return TGP_OK;
 }
@@ -1154,19 +1111,14 @@ std::vector<int64_t> level_sizes(int64_t count) {
   return s;
 }
 
-// Riccati (width 1), affine (M, V), prediction (M, V, Mf, Vf; width 1), congruence (M, V)
-enum ScanKind { SCAN_RIC, SCAN_AFF, SCAN_PRED, SCAN_CONG };
-inline int64_t scan_esz(ScanKind k) { return (k == SCAN_RIC ? 3 : k == SCAN_PRED ? 4 : 2) * WAVE; }
-inline int64_t scan_psz(ScanKind k) { return (k == SCAN_PRED ? 2 : 1) * WAVE; }
-
-// Exclusive scan over the elements already in `elem0` (esz doubles each, `width` independent scans interleaved):
-// prefixes (psz doubles each) of level 0 land in the returned pointer.  Work layout: per level, elements then
-// prefixes.  Riccati and affine scans run `members` models at once (grid y): member b uses models[b] and the same
-// layout `work_stride` doubles after member b - 1's; the other kinds serve the handle's own model only.
-int run_scan(const QModel* models, hipStream_t st, ScanKind kind, int64_t count, int64_t width, double* elem0,
-             double** prefix0, int64_t members = 1, int64_t work_stride = 0) {
-  TGP_ARG_CHECK(members == 1 || kind == SCAN_RIC || kind == SCAN_AFF, "this scan serves one model at a time");
-  const int64_t esz = scan_esz(kind), psz = scan_psz(kind);
+// Exclusive scan with elements S (a scan policy) over the `count` elements already in `elem0`, `width` independent
+// scans interleaved: the level-0 prefixes land in the returned pointer.  Work layout: per level, elements then
+// prefixes.  `members` models run at once (grid y): member b uses models[b] and the same layout `work_stride` doubles
+// after member b - 1's.
+template <class S>
+int run_scan(const QModel* models, hipStream_t st, int64_t count, int64_t width, double* elem0, double** prefix0,
+             int64_t members = 1, int64_t work_stride = 0) {
+  constexpr int64_t esz = S::ESZ * WAVE, psz = S::PSZ * WAVE;
   const std::vector<int64_t> sz = level_sizes(count);
   std::vector<double*> el(sz.size()), pre(sz.size());
   el[0] = elem0;
@@ -1181,39 +1133,24 @@ int run_scan(const QModel* models, hipStream_t st, ScanKind kind, int64_t count,
   }
   for (size_t l = 0; l + 1 < sz.size(); ++l) {
     const int64_t g = sz[l + 1];
-    if (kind == SCAN_RIC)
-      qs_reduce<<<dim3(unsigned(blocks_for(g)), unsigned(members)), WAVE * WPB, 0, st>>>(models, el[l], sz[l],
-                                                                                         el[l + 1], g, work_stride);
-    else if (kind == SCAN_PRED)
-      qs_pred_reduce<<<blocks_for(g), WAVE * WPB, 0, st>>>(models, el[l], sz[l], el[l + 1], g);
-    else if (kind == SCAN_CONG)
-      qs_cong_reduce<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(models, el[l], sz[l], width, el[l + 1], g);
-    else
-      qs_aff_reduce<<<dim3(unsigned(blocks_for(g * width)), unsigned(members)), WAVE * WPB, 0, st>>>(
-          models, el[l], sz[l], width, el[l + 1], g, work_stride);
+    qs_scan_reduce<S><<<dim3(unsigned(blocks_for(g * width)), unsigned(members)), WAVE * WPB, 0, st>>>(
+        models, el[l], sz[l], width, el[l + 1], g, work_stride);
   }
   for (size_t l = sz.size(); l-- > 0;) {
     const int64_t g = l + 1 < sz.size() ? sz[l + 1] : 1;
     const double* pin = l + 1 < sz.size() ? pre[l + 1] : nullptr;
-    if (kind == SCAN_RIC)
-      qs_down<<<dim3(unsigned(blocks_for(g)), unsigned(members)), WAVE * WPB, 0, st>>>(models, el[l], sz[l], pin,
-                                                                                       pre[l], g, work_stride);
-    else if (kind == SCAN_PRED)
-      qs_pred_down<<<blocks_for(g), WAVE * WPB, 0, st>>>(models, el[l], sz[l], pin, pre[l], g);
-    else if (kind == SCAN_CONG)
-      qs_cong_down<<<blocks_for(g * width), WAVE * WPB, 0, st>>>(models, el[l], sz[l], width, pin, pre[l], g);
-    else
-      qs_aff_down<<<dim3(unsigned(blocks_for(g * width)), unsigned(members)), WAVE * WPB, 0, st>>>(
-          models, el[l], sz[l], width, pin, pre[l], g, work_stride);
+    qs_scan_down<S><<<dim3(unsigned(blocks_for(g * width)), unsigned(members)), WAVE * WPB, 0, st>>>(
+        models, el[l], sz[l], width, pin, pre[l], g, work_stride);
   }
   TGP_HIP_TRY(hipGetLastError());
   *prefix0 = pre[0];
   return TGP_OK;
 }
 
-int64_t scan_work(ScanKind kind, int64_t count, int64_t width) {
+template <class S>
+int64_t scan_work(int64_t count, int64_t width) {
   int64_t total = 0;
-  for (int64_t s : level_sizes(count)) total += s * width * (scan_esz(kind) + scan_psz(kind));
+  for (int64_t s : level_sizes(count)) total += s * width * (S::ESZ + S::PSZ) * WAVE;
   return total;
 }
 
@@ -1252,20 +1189,54 @@ int set_model(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t*
   return TGP_OK;
 }
 
+// The factor of `members` models (grid y) over the handle's t: qs_fold, the Riccati scan, qs_emit.  Member b: model
+// models[b], its noise noise_stride, its scan work space work_stride, its per-chunk sums of log c red_stride doubles
+// after member b - 1's; c, w and the bad-pivot slots as in qs_emit.  *prefix: the chunks' incoming filtered
+// covariances (member 0's; nchunks x WAVE), valid until `work` is written again.
+int launch_factor(tgp_qsep* q, const QModel* models, int64_t members, const double* noise, int64_t noise_stride,
+                  double* work, int64_t work_stride, double* cbuf, double* wbuf, double* logsum, int64_t red_stride,
+                  int64_t* bad, double** prefix) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks;
+  const dim3 grid(unsigned(blocks_for(nc)), unsigned(members));
+  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, noise_stride, n, q->lc, nc, work, work_stride);
+  TGP_TRY(run_scan<ScanRiccati>(models, st, nc, 1, work, prefix, members, work_stride));
+  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, noise_stride, n, q->lc, nc, *prefix, work_stride, cbuf,
+                                       wbuf, logsum, red_stride, bad);
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
+// out = op(y) for nrhs columns (N x nrhs, row-major) against the factors c, w of `members` models: qs_aff_fold, the
+// affine scan, qs_aff_emit.  Member b: its y y_stride, its work space work_stride, its per-chunk sums of out^2
+// (sumsq; optional) red_stride doubles after member b - 1's.  *prefix: the chunks' incoming states (member 0's;
+// nchunks x ncg x WAVE), valid until `work` is written again.
+int launch_affine(tgp_qsep* q, int op, const QModel* models, int64_t members, const double* cbuf, const double* wbuf,
+                  int64_t nrhs, const double* y, int64_t y_stride, double* work, int64_t work_stride, double* out,
+                  double* sumsq, int64_t red_stride, double** prefix) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks, ncg = ceil_div(nrhs, 8);
+  const dim3 grid(unsigned(blocks_for(nc * ncg)), unsigned(members));
+  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(op, models, q->t, cbuf, wbuf, n, q->lc, nc, nrhs, ncg, y, y_stride, work,
+                                           work_stride);
+  TGP_TRY(run_scan<ScanAffine>(models, st, nc, ncg, work, prefix, members, work_stride));
+  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(op, models, q->t, cbuf, wbuf, n, q->lc, nc, nrhs, ncg, *prefix, work_stride,
+                                           y, y_stride, out, sumsq, red_stride);
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
 // keep: optional device buffer (nchunks x WAVE) that receives the chunks' incoming filtered covariances
 int factor(tgp_qsep* q, const double* noise_host, double* keep = nullptr) {
   hipStream_t st = q->ctx->stream;
   const int64_t n = q->n, nc = q->nchunks;
   TGP_ARG_CHECK(noise_host != nullptr, "null noise array");
   TGP_HIP_TRY(hipMemcpyAsync(q->noise, noise_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
-  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_RIC, nc, 1)));
-  qs_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, 0, n, q->lc, nc, q->work, 0);
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanRiccati>(nc, 1)));
   double* prefix = nullptr;
-  TGP_TRY(run_scan(q->model, st, SCAN_RIC, nc, 1, q->work, &prefix));
+  TGP_TRY(launch_factor(q, q->model, 1, q->noise, 0, q->work, 0, q->c, q->w, q->red, 0, q->bad, &prefix));
   if (keep)
     TGP_HIP_TRY(hipMemcpyAsync(keep, prefix, size_t(nc) * WAVE * sizeof(double), hipMemcpyDeviceToDevice, st));
-  qs_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->noise, 0, n, q->lc, nc, prefix, 0, q->c, q->w,
-                                                 q->red, 0, q->bad);
   qs_finish<<<1, WAVE, 0, st>>>(q->red, nc, nullptr, 0, q->bad, q->red + 2 * nc, q->bad + nc, 0, 0, 0);
   TGP_HIP_TRY(hipGetLastError());
   double sums[2];
@@ -1283,16 +1254,13 @@ int factor(tgp_qsep* q, const double* noise_host, double* keep = nullptr) {
 // keep: optional device buffer (nchunks x ncg x WAVE) that receives the chunks' incoming states
 int affine(tgp_qsep* q, int op, int64_t nrhs, const double* y, double* out, double* sumsq, double* keep = nullptr) {
   hipStream_t st = q->ctx->stream;
-  const int64_t n = q->n, nc = q->nchunks, ncg = ceil_div(nrhs, 8);
-  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_AFF, nc, ncg)));
-  qs_aff_fold<<<blocks_for(nc * ncg), WAVE * WPB, 0, st>>>(op, q->model, q->t, q->c, q->w, n, q->lc, nc, nrhs, ncg,
-                                                            y, 0, q->work, 0);
+  const int64_t nc = q->nchunks, ncg = ceil_div(nrhs, 8);
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanAffine>(nc, ncg)));
   double* prefix = nullptr;
-  TGP_TRY(run_scan(q->model, st, SCAN_AFF, nc, ncg, q->work, &prefix));
+  TGP_TRY(launch_affine(q, op, q->model, 1, q->c, q->w, nrhs, y, 0, q->work, 0, out, sumsq ? q->red : nullptr, 0,
+                        &prefix));
   if (keep)
     TGP_HIP_TRY(hipMemcpyAsync(keep, prefix, size_t(nc * ncg) * WAVE * sizeof(double), hipMemcpyDeviceToDevice, st));
-  qs_aff_emit<<<blocks_for(nc * ncg), WAVE * WPB, 0, st>>>(op, q->model, q->t, q->c, q->w, n, q->lc, nc, nrhs, ncg,
-                                                            prefix, 0, y, 0, out, sumsq ? q->red : nullptr, 0);
   if (sumsq) {
     qs_finish<<<1, WAVE, 0, st>>>(q->red, nc * ncg, nullptr, 0, nullptr, q->red + 2 * nc * ncg, nullptr, 0, 0, 0);
     TGP_HIP_TRY(hipMemcpyAsync(sumsq, q->red + 2 * nc * ncg, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1329,12 +1297,7 @@ int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const 
   const int want_mean = mean_host != nullptr, want_var = var_host != nullptr;
   // pred: xt (m) | pt (m x nterms x PT) | mean (nterms x m) | var (nterms x m);  pidx: idx (m) | sidx (m) | order (m)
   TGP_TRY(grow(&q->pred, &q->pred_elems, m * (1 + int64_t(nterms) * (PT + 2))));
-  if (q->pidx_elems < 3 * m) {
-    if (q->pidx) hipFree(q->pidx);
-    q->pidx = nullptr, q->pidx_elems = 0;
-    TGP_HIP_TRY(hipMalloc(&q->pidx, size_t(3 * m) * sizeof(int64_t)));
-    q->pidx_elems = 3 * m;
-  }
+  TGP_TRY(grow(&q->pidx, &q->pidx_elems, 3 * m));
   double *pt = q->pred + m, *mean = pt + m * nterms * PT, *var = mean + m * nterms;
   const double* xt = xtest_host ? q->pred : q->t;
   int64_t *idx = q->pidx, *sidx = idx + m, *order = sidx + m;
@@ -1369,12 +1332,12 @@ int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const 
     TGP_HIP_TRY(hipMemcpyAsync(sidx, h_sidx.data(), size_t(m) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     TGP_HIP_TRY(hipMemcpyAsync(order, h_order.data(), size_t(m) * sizeof(int64_t), hipMemcpyHostToDevice, st));
   }
-  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_PRED, nc, 1)));
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanPred>(nc, 1)));
   for (int dir = 0; dir < 2; ++dir) {
     qs_pred_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
                                                         n, q->lc, nc, q->work);
     double* prefix = nullptr;
-    TGP_TRY(run_scan(q->model, st, SCAN_PRED, nc, 1, q->work, &prefix));
+    TGP_TRY(run_scan<ScanPred>(q->model, st, nc, 1, q->work, &prefix));
     qs_pred_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
                                                         n, q->lc, nc, prefix, xt, sidx, order, m, gv, nterms, pt,
                                                         mean, var);
@@ -1408,7 +1371,7 @@ int grad_directions(tgp_qsep* q, int32_t ndir, const double* dleaves, const doub
   TGP_TRY(grow(&q->gdir, &q->gdir_elems, batch * DIR_DOUBLES));
   TGP_TRY(grow(&q->gtan, &q->gtan_elems, batch * per_dir));
   TGP_TRY(grow(&q->gred, &q->gred_elems, batch * (2 * nc + 2)));
-  TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_CONG, nc, batch)));
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanCong>(nc, batch)));
   const double *prefixP = q->gkeep, *prefixS = q->gkeep + nc * WAVE;
   const QDir* dirs = reinterpret_cast<const QDir*>(q->gdir);
   std::vector<QDir> hd(size_t(batch), QDir{});
@@ -1432,16 +1395,16 @@ int grad_directions(tgp_qsep* q, int32_t ndir, const double* dleaves, const doub
     double* res = q->gred + 2 * nb * nc;
     double* prefix = nullptr;
     qs_gfac_fold<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->noise, n, q->lc, nc, prefixP, q->work);
-    TGP_TRY(run_scan(q->model, st, SCAN_CONG, nc, nb, q->work, &prefix));
+    TGP_TRY(run_scan<ScanCong>(q->model, st, nc, nb, q->work, &prefix));
     qs_gfac_emit<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->noise, n, q->lc, nc, prefixP, prefix, dcb, dwb,
                                               dsum);
     qs_gsol<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->c, q->w, dcb, dwb, q->io, n, q->lc, nc, prefixS,
                                          nullptr, q->work, nullptr);
-    TGP_TRY(run_scan(q->model, st, SCAN_AFF, nc, nb, q->work, &prefix));
+    TGP_TRY(run_scan<ScanAffine>(q->model, st, nc, nb, q->work, &prefix));
     qs_gsol<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->c, q->w, dcb, dwb, q->io, n, q->lc, nc, prefixS,
                                          prefix, nullptr, dsum2);
-    for (int64_t b = 0; b < nb; ++b)
-      qs_finish<<<1, WAVE, 0, st>>>(dsum + b * nc, nc, dsum2 + b * nc, nc, nullptr, res + 2 * b, nullptr, 0, 0, 0);
+    // block b: direction b's two sums (dsum2 lies nb nc doubles after dsum, like its rows)
+    qs_finish<<<unsigned(nb), WAVE, 0, st>>>(dsum, nc, dsum2, nc, nullptr, res, nullptr, nc, 0, 2);
     TGP_HIP_TRY(hipGetLastError());
     // the host vectors are reused by the next batch: wait for this one
     TGP_HIP_TRY(hipMemcpyAsync(sums.data(), res, size_t(2 * nb) * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1460,11 +1423,11 @@ int grad_vectors(tgp_qsep* q, double* gnoise_host, double* alpha_host) {
     TGP_HIP_TRY(hipMemcpyAsync(alpha_host, q->io, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, st));
   if (gnoise_host) {
     TGP_TRY(grow(&q->gout, &q->gout_elems, n));
-    TGP_TRY(grow(&q->work, &q->work_elems, scan_work(SCAN_PRED, nc, 1)));
+    TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanPred>(nc, 1)));
     qs_pred_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(1, 0, 1, q->model, q->t, q->c, q->w, nullptr, n, q->lc, nc,
                                                         q->work);
     double* prefix = nullptr;
-    TGP_TRY(run_scan(q->model, st, SCAN_PRED, nc, 1, q->work, &prefix));
+    TGP_TRY(run_scan<ScanPred>(q->model, st, nc, 1, q->work, &prefix));
     qs_invdiag_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->c, q->w, q->io, n, q->lc, nc, prefix,
                                                            q->gout);
     TGP_HIP_TRY(hipGetLastError());
@@ -1485,7 +1448,7 @@ __attribute__((noinline)) double logprob_value(double zz, double logdet, int64_t
 //   fixed        BATCH_MAX_MEMBERS models (MODEL_DOUBLES each) | the noise, if shared (n) | the residual, if shared (n)
 //   per member   noise, if its own (n) | residual, if its own (n) | c (n) | w (n J) | z (n) | scan work space (W) |
 //                per-chunk sums of log c and of z^2 (2 nchunks) | bad-pivot slots (nchunks) | results (3)
-// with W = 4 WAVE sum of the scan's level sizes, the Riccati scan's need (the affine scan's 3 WAVE fits inside).
+// with W the larger need of the chain's two scans (the Riccati one's: 4 lane-blocks per element and level).
 constexpr int64_t BATCH_MAX_MEMBERS = 64;
 constexpr int64_t BATCH_SCRATCH_BYTES = int64_t(1) << 30;
 static_assert(sizeof(QModel) % sizeof(double) == 0, "models are laid out in a buffer of doubles");
@@ -1497,7 +1460,7 @@ struct BatchLayout {
 
 BatchLayout batch_layout(int64_t n, int64_t nc, int64_t J, bool own_noise, bool own_resid) {
   BatchLayout l;
-  l.work = std::max(scan_work(SCAN_RIC, nc, 1), scan_work(SCAN_AFF, nc, 1));
+  l.work = std::max(scan_work<ScanRiccati>(nc, 1), scan_work<ScanAffine>(nc, 1));
   l.fixed = BATCH_MAX_MEMBERS * MODEL_DOUBLES + (own_noise ? 0 : n) + (own_resid ? 0 : n);
   l.per_member = (own_noise ? n : 0) + (own_resid ? n : 0) + n * (2 + J) + l.work + 3 * nc + 3;
   return l;
@@ -1531,17 +1494,10 @@ int batch_chain(tgp_qsep* q, const BatchLayout& lay, int64_t cap, int64_t nb, co
     TGP_HIP_TRY(hipMemcpyAsync(noise, noise_host, size_t(nb * n) * sizeof(double), hipMemcpyHostToDevice, st));
   if (resid_stride)
     TGP_HIP_TRY(hipMemcpyAsync(resid, resid_host, size_t(nb * n) * sizeof(double), hipMemcpyHostToDevice, st));
-  const dim3 grid(unsigned(blocks_for(nc)), unsigned(nb));
   double* prefix = nullptr;
-  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, noise_stride, n, q->lc, nc, work, W);
-  TGP_TRY(run_scan(models, st, SCAN_RIC, nc, 1, work, &prefix, nb, W));
-  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, noise_stride, n, q->lc, nc, prefix, W, cbuf, wbuf, red,
-                                       2 * nc, bad);
-  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, q->t, cbuf, wbuf, n, q->lc, nc, 1, 1, resid,
-                                           resid_stride, work, W);
-  TGP_TRY(run_scan(models, st, SCAN_AFF, nc, 1, work, &prefix, nb, W));
-  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, q->t, cbuf, wbuf, n, q->lc, nc, 1, 1, prefix, W, resid,
-                                           resid_stride, z, red + nc, 2 * nc);
+  TGP_TRY(launch_factor(q, models, nb, noise, noise_stride, work, W, cbuf, wbuf, red, 2 * nc, bad, &prefix));
+  TGP_TRY(launch_affine(q, TGP_QS_FWD, models, nb, cbuf, wbuf, 1, resid, resid_stride, work, W, z, red + nc, 2 * nc,
+                        &prefix));
   // per member: (sum log c, sum z^2, first bad pivot), the third an int64 in a double's slot
   qs_finish<<<unsigned(nb), WAVE, 0, st>>>(red, nc, red + nc, nc, bad, res, reinterpret_cast<int64_t*>(res) + 2,
                                            2 * nc, nc, 3);
