@@ -17,6 +17,7 @@ from tinygp_amd.solvers import QuasisepSolver
 
 import _quasisep_grad_np as og
 from _quasisep_cases import CASES
+from _quasisep_edges import _levels
 
 pytestmark = pytest.mark.gpu
 
@@ -32,16 +33,6 @@ def _series(n, seed=0):
     if n > 8:
         t[n // 3] = t[n // 3 - 1]  # a repeated coordinate
     return t, rng.uniform(0.05, 0.2, n), rng.standard_normal(n)
-
-
-def _levels(n):
-    lc = 16
-    while lc < 256 and lc * 4096 < n:
-        lc *= 2
-    count, levels = -(-n // lc), 1
-    while count > 64:
-        count, levels = -(-count // 64), levels + 1
-    return lc, levels
 
 
 _ORACLE = {}

@@ -12,6 +12,7 @@ from tinygp_amd.solvers import DirectSolver, QuasisepSolver
 
 import _quasisep_predict_np as po
 from _quasisep_cases import CASES
+from _quasisep_edges import _test_points
 
 pytestmark = pytest.mark.gpu
 
@@ -28,23 +29,6 @@ def _series(n, seed=0):
     rng = np.random.default_rng(seed)
     t = np.sort(rng.uniform(0, 0.05 * n + 1, n))
     return t, rng.uniform(0.05, 0.2, n), rng.standard_normal(n)
-
-
-def _test_points(t, m, seed, lc=LC):
-    """Unsorted; outside the range on both sides, on data points (tied ones too), in the first and the last chunk
-    and exactly on the data points either side of chunk boundaries."""
-    rng = np.random.default_rng(seed)
-    n = len(t)
-    edges = np.unique(np.clip(np.concatenate([np.arange(lc - 1, n, lc), np.arange(lc, n, lc), [0, n - 1]]), 0, n - 1))
-    edges = edges[rng.permutation(len(edges))[:60]]
-    special = np.concatenate([
-        t[edges], t[[0, n - 1]], t[:3], t[-3:],
-        rng.uniform(t[0], t[min(lc, n) - 1], 8),            # inside the first chunk
-        rng.uniform(t[max(0, n - lc // 2)], t[-1], 8),      # inside the last chunk
-        t[0] - rng.uniform(0, 3, 6), t[-1] + rng.uniform(0, 3, 6), [t[0] - 40.0, t[-1] + 40.0],
-    ])
-    xt = np.concatenate([rng.uniform(t[0] - 1, t[-1] + 1, max(0, m - len(special))), special])
-    return xt[rng.permutation(len(xt))]
 
 
 def _report(tag, mean, var, wmean, wvar):

@@ -14,6 +14,7 @@ from tinygp_amd.solvers import QuasisepSolver
 
 import _quasisep_np as o
 from _quasisep_cases import CASES
+from _quasisep_edges import _levels
 
 pytestmark = pytest.mark.gpu
 
@@ -38,16 +39,6 @@ def _series(n, seed=0, clustered=False):
     else:
         t = np.sort(rng.uniform(0, 0.05 * n + 1, n))
     return t, rng.uniform(0.05, 0.2, n), rng.standard_normal(n)
-
-
-def _levels(n):
-    lc = 16
-    while lc < 256 and lc * 4096 < n:
-        lc *= 2
-    count, levels = -(-n // lc), 1
-    while count > 64:
-        count, levels = -(-count // 64), levels + 1
-    return lc, levels
 
 
 def test_sizes_reach_the_shapes_they_name():
