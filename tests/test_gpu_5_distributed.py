@@ -231,12 +231,13 @@ def test_resident_solves_on_the_hip_path(pg):
     s.ops.close()
 
 
-@pytest.mark.parametrize("n,nb,chunk", [(2000, 256, 512), (3000, 512, 384), (1500, 128, 2048)])
+@pytest.mark.parametrize("n,nb,chunk", [(2000, 256, 512), (3000, 512, 384), (1500, 128, 2048), (300, 128, 128)])
 def test_gradient_on_the_block_column_path_hip(pg, n, nb, chunk):
     """Value-and-gradient through the REAL per-rank operations at world size 1 (RCCL self-collectives): the chunked K^-1
     solves (fan-in forward of identity columns, right-looking multi-RHS backward: csrc/dist.hip), the column-chunk
-    contraction kernel (kgrad_cols_kernel) and the all-reduce -- against the gradient oracle (trace identity in NumPy),
-    at the single-GPU gradient's tolerances (tests/test_gpu_2_grad.py)."""
+    contraction kernel (kgrad_tile_kernel on ChunkKinv) and the all-reduce -- against the gradient oracle (trace identity in NumPy),
+    at the single-GPU gradient's tolerances (tests/test_gpu_2_grad.py).  N = 300 with nb = 128 and chunks of 128: three
+    chunks, the later ones starting past column 0, a ragged last chunk and last tile row."""
     from oracle import grad_np
     from tinygp_amd import kernels
     from tinygp_amd.distributed import BlockCyclicCholesky

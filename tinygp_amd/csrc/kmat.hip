@@ -233,6 +233,68 @@ __device__ __forceinline__ T eval_kprog_deriv_dim(const KProg& kp, T r1, T r2, T
 
 constexpr int KT = 128;  // tile edge
 
+// Zero-padded load of two 128-point tiles -- rows r0.. of X1 into s1, rows c0.. of X2 into s2, [KT][d] each -- by the
+// block's 256 threads, and the barrier after it.
+template <typename T>
+__device__ __forceinline__ void load_tile_pair(T* s1, T* s2, const T* __restrict__ X1, const T* __restrict__ X2,
+                                               int64_t r0, int64_t c0, int64_t n1, int64_t n2, int d) {
+  for (int t = threadIdx.x; t < KT * d; t += 256) {
+    const int64_t gi = r0 + t / d, gj = c0 + t / d;
+    s1[t] = (gi < n1) ? X1[gi * d + t % d] : T(0);
+    s2[t] = (gj < n2) ? X2[gj * d + t % d] : T(0);
+  }
+  __syncthreads();
+}
+
+struct NoCapture {
+  template <typename T> __device__ __forceinline__ void operator()(int, T, T, T) const {}
+};
+
+// The distances of one pair of points a, b: r1 = sum |a_t - b_t|, r2 = sum (a_t - b_t)^2 and, FAM = 2 only,
+// r3 = sum a_t b_t, dimension by dimension in this order.  D > 0: an unrolled loop over D coordinates with the row
+// point `a` in registers (PARTIAL: only the first d <= D of them exist); D = 0: the dynamic loop over d.
+// `capture(t, dx, a_t, b_t)` sees every dimension (the gradient keeps one of them).
+template <typename T, int FAM, int D, bool PARTIAL = false, typename Capture = NoCapture>
+__device__ __forceinline__ void pair_dist(const T* a, const T* b, int d, T& r1, T& r2, T& r3,
+                                          Capture capture = Capture()) {
+  r1 = r2 = r3 = T(0);
+  auto step = [&](int t) {
+    const T dx = a[t] - b[t];
+    r1 += fabs(dx);
+    r2 += dx * dx;
+    if constexpr (FAM == 2) r3 += a[t] * b[t];
+    capture(t, dx, a[t], b[t]);
+  };
+  if constexpr (D > 0) {
+#pragma unroll
+    for (int t = 0; t < D; ++t)
+      if (!PARTIAL || t < d) step(t);
+  } else {
+    for (int t = 0; t < d; ++t) step(t);
+  }
+}
+
+// acc[a] <- the sum of acc[a] over the block's NT threads, valid in thread 0: a fixed LDS tree (t pairs with t + NT/2,
+// then with t + NT/4, ...), so the result does not depend on timing.
+template <int NT, int NACC>
+__device__ __forceinline__ void block_sum(double (&acc)[NACC]) {
+  __shared__ double red[NACC][NT];
+#pragma unroll
+  for (int a = 0; a < NACC; ++a) red[a][threadIdx.x] = acc[a];
+  __syncthreads();
+  for (int sft = NT / 2; sft > 0; sft >>= 1) {
+    if ((int)threadIdx.x < sft) {
+#pragma unroll
+      for (int a = 0; a < NACC; ++a) red[a][threadIdx.x] += red[a][threadIdx.x + sft];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) acc[a] = red[a][0];
+  }
+}
+
 // ---- fast path: the program is one exp-family leaf, optionally times a constant ("amp * leaf") --
 // OP and the metric are template parameters, so the inner loops below are straight-line code the
 // compiler can unroll and interleave across elements (the general evaluator runs a chain of
@@ -427,12 +489,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(KProg kp, int64_t n1, int64_t
   T* s1 = reinterpret_cast<T*>(smem);  // [KT][d]
   T* s2 = s1 + KT * d;                 // [KT][d]
   const int64_t r0 = int64_t(tr) * KT, c0 = int64_t(tc) * KT;
-  for (int t = threadIdx.x; t < KT * d; t += 256) {
-    const int64_t gi = r0 + t / d, gj = c0 + t / d;
-    s1[t] = (gi < n1) ? X1[gi * d + t % d] : T(0);
-    s2[t] = (gj < n2) ? X2[gj * d + t % d] : T(0);
-  }
-  __syncthreads();
+  load_tile_pair(s1, s2, X1, X2, r0, c0, n1, n2, d);
 
   const int il = threadIdx.x & (KT - 1);
   const int g = threadIdx.x >> 7;  // column half
@@ -450,23 +507,9 @@ __global__ __launch_bounds__(256) void kmat_kernel(KProg kp, int64_t n1, int64_t
     if (gj >= cols_out) break;
     T v;
     if (gi < n1 && gj < n2) {
-      T r1 = 0, r2 = 0, r3 = 0;
-      if constexpr (D > 0) {
-#pragma unroll
-        for (int t = 0; t < D; ++t) {
-          const T dx = xr[t] - s2[jl * D + t];
-          r1 += fabs(dx);
-          r2 += dx * dx;
-          if constexpr (FAM == 2) r3 += xr[t] * s2[jl * D + t];
-        }
-      } else {
-        for (int t = 0; t < d; ++t) {
-          const T dx = s1[il * d + t] - s2[jl * d + t];
-          r1 += fabs(dx);
-          r2 += dx * dx;
-          if constexpr (FAM == 2) r3 += s1[il * d + t] * s2[jl * d + t];
-        }
-      }
+      T r1, r2, r3;
+      if constexpr (D > 0) pair_dist<T, FAM, D>(xr, s2 + jl * D, d, r1, r2, r3);
+      else pair_dist<T, FAM, 0>(s1 + il * d, s2 + jl * d, d, r1, r2, r3);
       v = eval_kprog<T, FAM>(kp, r1, r2, r3);
       if (diag != nullptr && gi == gj) v += dg;  // noise.py:77-78 fused
     } else {
@@ -476,144 +519,161 @@ __global__ __launch_bounds__(256) void kmat_kernel(KProg kp, int64_t n1, int64_t
   }
 }
 
-// One lower 128x128 tile: sum of w_ij (alpha_i alpha_j - Kinv_ij) dK_ij/dtheta, w = 1/2 on the
-// diagonal, 1 strictly below it, 0 above (the 1/2 of 1/2 tr(G dK) folded with symmetry).
-// partial[tile] gets the tile's sum; fixed LDS tree -> deterministic.  FAM: 0, or 2 (kfamily()).
+// d(leaf)/d(scale), the expressions of leaf_deriv with op and metric fixed at compile time
+template <typename T, int OP, int L2>
+__device__ __forceinline__ T leaf_deriv_fast(T r1, T r2, T p0) {
+  if constexpr (OP == TGP_K_EXPSQ) {
+    const T sq = L2 ? r2 : r1 * r1;
+    return exp(T(-0.5) * (sq / (p0 * p0))) * sq / (p0 * p0 * p0);
+  } else {
+    const T dist = L2 ? ((r2 == T(0)) ? r1 : sqrt(r2)) : r1;
+    if constexpr (OP == TGP_K_EXP) {
+      return exp(-dist / p0) * dist / (p0 * p0);
+    } else if constexpr (OP == TGP_K_M32) {
+      const T a = MathC<T>::SQRT3 * (dist / p0);
+      return a * a * exp(-a) / p0;
+    } else {
+      const T a = MathC<T>::SQRT5 * (dist / p0);
+      return (a * a / T(3)) * (T(1) + a) * exp(-a) / p0;
+    }
+  }
+}
+
+// ---- what is evaluated per pair: the two evaluators of the gradient and the matrix-vector kernels -------------------
+// value(): the kernel at the pair's distances.  capture() / add_sums(): the gradient's side -- NSUM derivatives of the
+// kernel, each weighted with gij = alpha_i alpha_j - Kinv_ij and `half` (1/2 on the diagonal, 1 below it) into acc[].
+// Each evaluator keeps the order of its own products (gij * dk * half here, (gij * half) * dk in FastEval).
+
+// Any program: one derivative per pass, with respect to parameter `which_param` of op `which_op` (>= 0), or to the
+// log-scale of input dimension -1 - which_op (< 0), whose dx and (FAM = 2) x_i x_j capture() keeps.
 template <typename T, int FAM>
-__global__ __launch_bounds__(256) void kgrad_kernel(KProg kp, int which_op, int which_param,
-                                                    int64_t n, int d, const T* __restrict__ X,
-                                                    const T* __restrict__ alpha,
-                                                    const T* __restrict__ Kinv, int64_t ld,
-                                                    double* __restrict__ partial) {
+struct GeneralEval {
+  static constexpr int FAMILY = FAM, NSUM = 1, UNROLL = 1;
+  KProg kp;
+  int which_op, which_param;
+  struct Pair { T dxd = 0, zz = 0; };
+  __device__ __forceinline__ T value(T r1, T r2, T r3) const { return eval_kprog<T, FAM>(kp, r1, r2, r3); }
+  __device__ __forceinline__ void capture(Pair& p, int t, T dx, T a, T b) const {
+    if (t == -1 - which_op) p.dxd = dx;
+    if constexpr (FAM == 2) {
+      if (t == -1 - which_op) p.zz = a * b;
+    }
+  }
+  __device__ __forceinline__ void add_sums(const Pair& p, T r1, T r2, T r3, T gij, double half,
+                                           double (&acc)[NSUM]) const {
+    const T dk = which_op >= 0 ? eval_kprog_deriv<T, FAM>(kp, which_op, which_param, r1, r2, r3)
+                               : eval_kprog_deriv_dim<T, FAM>(kp, r1, r2, r1 > T(0) ? fabs(p.dxd) / r1 : T(0),
+                                                              r2 > T(0) ? p.dxd * p.dxd / r2 : T(0), r3, p.zz);
+    acc[0] += double(gij) * double(dk) * half;
+  }
+};
+
+// "leaf" / "amp * leaf" programs (fast_prog()): straight-line code (see kmat_fast_kernel), and BOTH derivatives in
+// one pass over K^-1: acc[0] for d/d amp = leaf, acc[1] for d/d scale = amp * d leaf.
+template <typename T, int OP, int L2>
+struct FastEval {
+  static constexpr int FAMILY = 0, NSUM = 2, UNROLL = 2;
+  T p0, amp;
+  struct Pair {};
+  __device__ __forceinline__ T value(T r1, T r2, T) const { return amp * leaf_fast<T, OP, L2>(r1, r2, p0, p0 * p0); }
+  __device__ __forceinline__ void capture(Pair&, int, T, T, T) const {}
+  __device__ __forceinline__ void add_sums(const Pair&, T r1, T r2, T, T gij, double half, double (&acc)[NSUM]) const {
+    const T leaf = leaf_fast<T, OP, L2>(r1, r2, p0, p0 * p0);
+    const T dk = amp * leaf_deriv_fast<T, OP, L2>(r1, r2, p0);
+    const double w = double(gij) * half;
+    acc[0] += w * double(leaf);
+    acc[1] += w * double(dk);
+  }
+};
+
+// ---- where Kinv_ij lives and which tiles contribute ------------------------------------------------------------
+// The square matrix, column-major: the tiles on and below the diagonal; the result overwrites.
+template <typename T>
+struct SquareKinv {
+  static constexpr bool ACCUMULATE = false;
+  const T* Kinv;
+  int64_t ld;
+  __device__ __forceinline__ int64_t first_col() const { return 0; }
+  __device__ __forceinline__ bool skip(int64_t r0, int64_t c0, int64_t) const { return r0 < c0; }
+  __device__ __forceinline__ T at(int64_t gi, int64_t gj) const { return Kinv[gj * ld + gi]; }
+};
+
+// A CHUNK OF COLUMNS of K^-1 held as rows (the gradient on the block-column path): `Kc` is (n_pad, R) ROW-major --
+// K^-1[i, c0 + r] at i * R + r, the layout of the distributed solves' right-hand sides --, and only row tiles inside
+// block rows THIS RANK owns contribute (block row b = row / nb belongs to rank b mod G): the ranks' partial sums add up
+// to the lower triangle of the chunk, and the chunks add up in the result.
+template <typename T>
+struct ChunkKinv {
+  static constexpr bool ACCUMULATE = true;
+  const T* Kc;
+  int64_t R, c0, nb;
+  int G, rank;
+  __device__ __forceinline__ int64_t first_col() const { return c0; }
+  __device__ __forceinline__ bool skip(int64_t r0, int64_t cc0, int64_t n) const {
+    const bool mine = int((r0 / nb) % G) == rank;
+    return !mine || r0 + KT <= cc0 || cc0 >= n || r0 >= n;  // not this rank's rows, or strictly above the diagonal
+  }
+  __device__ __forceinline__ T at(int64_t gi, int64_t gj) const { return Kc[gi * R + (gj - c0)]; }
+};
+
+// One 128x128 tile (rows tr * 128 .., columns src.first_col() + tc * 128 ..) of
+//   sum w_ij (alpha_i alpha_j - Kinv_ij) dK_ij/dtheta,  w = 1/2 on the diagonal, 1 strictly below it, 0 above
+// (the 1/2 of 1/2 tr(G dK) folded with symmetry), for each of the evaluator's NSUM derivatives:
+// partial[s * ntiles + tile] gets the tile's sum (zero for a tile that does not contribute); fixed LDS tree ->
+// deterministic.
+template <typename T, typename Eval, typename Src>
+__global__ __launch_bounds__(256) void kgrad_tile_kernel(Eval ev, Src src, int64_t n, int d,
+                                                         const T* __restrict__ X, const T* __restrict__ alpha,
+                                                         double* __restrict__ partial) {
+  constexpr int NSUM = Eval::NSUM;
   const int tr = blockIdx.x, tc = blockIdx.y;
-  const int tile_id = tr * gridDim.y + tc;
-  if (tr < tc) {
-    if (threadIdx.x == 0) partial[tile_id] = 0.0;
+  const int tile_id = tr * gridDim.y + tc, ntiles = gridDim.x * gridDim.y;
+  const int64_t r0 = int64_t(tr) * KT, c0 = src.first_col() + int64_t(tc) * KT;
+  if (src.skip(r0, c0, n)) {
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int s = 0; s < NSUM; ++s) partial[s * ntiles + tile_id] = 0.0;
+    }
     return;
   }
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* s1 = reinterpret_cast<T*>(smem);  // [KT][d]
   T* s2 = s1 + KT * d;                 // [KT][d]
-  __shared__ double red[256];
-  const int64_t r0 = int64_t(tr) * KT, c0 = int64_t(tc) * KT;
-  for (int t = threadIdx.x; t < KT * d; t += 256) {
-    const int64_t gi = r0 + t / d, gj = c0 + t / d;
-    s1[t] = (gi < n) ? X[gi * d + t % d] : T(0);
-    s2[t] = (gj < n) ? X[gj * d + t % d] : T(0);
-  }
-  __syncthreads();
+  load_tile_pair(s1, s2, X, X, r0, c0, n, n, d);
   const int il = threadIdx.x & (KT - 1), g = threadIdx.x >> 7;
   const int64_t gi = r0 + il;
   const T ai = (gi < n) ? alpha[gi] : T(0);
-  double acc = 0.0;
+  double acc[NSUM] = {};
   if (gi < n) {
     for (int c = 0; c < KT / 2; ++c) {
       const int jl = g * (KT / 2) + c;
       const int64_t gj = c0 + jl;
       if (gj >= n || gj > gi) continue;
-      T r1 = 0, r2 = 0, r3 = 0, dxd = 0, zz = 0;
-      for (int t = 0; t < d; ++t) {
-        const T dx = s1[il * d + t] - s2[jl * d + t];
-        r1 += fabs(dx);
-        r2 += dx * dx;
-        if constexpr (FAM == 2) r3 += s1[il * d + t] * s2[jl * d + t];
-        if (t == -1 - which_op) dxd = dx;  // (which_op < 0: the log-scale of input dimension -1 - which_op)
-        if constexpr (FAM == 2) {
-          if (t == -1 - which_op) zz = s1[il * d + t] * s2[jl * d + t];
-        }
-      }
-      const T dk = which_op >= 0 ? eval_kprog_deriv<T, FAM>(kp, which_op, which_param, r1, r2, r3)
-                                 : eval_kprog_deriv_dim<T, FAM>(kp, r1, r2, r1 > T(0) ? fabs(dxd) / r1 : T(0),
-                                                                r2 > T(0) ? dxd * dxd / r2 : T(0), r3, zz);
-      const T gij = ai * alpha[gj] - Kinv[gj * ld + gi];
-      acc += double(gij) * double(dk) * (gi == gj ? 0.5 : 1.0);
+      typename Eval::Pair p;
+      T r1, r2, r3;
+      pair_dist<T, Eval::FAMILY, 0>(s1 + il * d, s2 + jl * d, d, r1, r2, r3,
+                                    [&](int t, T dx, T a, T b) { ev.capture(p, t, dx, a, b); });
+      ev.add_sums(p, r1, r2, r3, ai * alpha[gj] - src.at(gi, gj), gi == gj ? 0.5 : 1.0, acc);
     }
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int sft = 128; sft > 0; sft >>= 1) {
-    if ((int)threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
-    __syncthreads();
+  block_sum<256, NSUM>(acc);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int s = 0; s < NSUM; ++s) partial[s * ntiles + tile_id] = acc[s];
   }
-  if (threadIdx.x == 0) partial[tile_id] = red[0];
 }
 
-// The same sum for a CHUNK OF COLUMNS of K^-1 held as rows (round 5: the gradient on the block-column path).  `Kc` is
-// (n_pad, R) ROW-major -- K^-1[i, c0 + r] at i * R + r, the layout of the distributed solves' right-hand sides --, and
-// only row tiles inside block rows THIS RANK owns contribute (block row b = row / nb belongs to rank b mod G): the ranks'
-// partial sums add up to the lower triangle of the chunk.  Tile (tr, tc): rows tr * 128 .., columns c0 + tc * 128 ...
-template <typename T, int FAM>
-__global__ __launch_bounds__(256) void kgrad_cols_kernel(KProg kp, int which_op, int which_param, int64_t n, int d,
-                                                         const T* __restrict__ X, const T* __restrict__ alpha,
-                                                         const T* __restrict__ Kc, int64_t R, int64_t c0, int64_t nb,
-                                                         int G, int rank, double* __restrict__ partial) {
-  const int tr = blockIdx.x, tc = blockIdx.y;
-  const int tile_id = tr * gridDim.y + tc;
-  const int64_t r0 = int64_t(tr) * KT, cc0 = c0 + int64_t(tc) * KT;
-  const bool mine = int((r0 / nb) % G) == rank;
-  if (!mine || r0 + KT <= cc0 || cc0 >= n || r0 >= n) {  // not this rank's rows, or strictly above the diagonal
-    if (threadIdx.x == 0) partial[tile_id] = 0.0;
-    return;
-  }
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* s1 = reinterpret_cast<T*>(smem);  // [KT][d]
-  T* s2 = s1 + KT * d;                 // [KT][d]
-  __shared__ double red[256];
-  for (int t = threadIdx.x; t < KT * d; t += 256) {
-    const int64_t gi = r0 + t / d, gj = cc0 + t / d;
-    s1[t] = (gi < n) ? X[gi * d + t % d] : T(0);
-    s2[t] = (gj < n) ? X[gj * d + t % d] : T(0);
-  }
-  __syncthreads();
-  const int il = threadIdx.x & (KT - 1), g = threadIdx.x >> 7;
-  const int64_t gi = r0 + il;
-  const T ai = (gi < n) ? alpha[gi] : T(0);
-  double acc = 0.0;
-  if (gi < n) {
-    for (int c = 0; c < KT / 2; ++c) {
-      const int jl = g * (KT / 2) + c;
-      const int64_t gj = cc0 + jl;
-      if (gj >= n || gj > gi) continue;
-      T r1 = 0, r2 = 0, r3 = 0, dxd = 0, zz = 0;
-      for (int t = 0; t < d; ++t) {
-        const T dx = s1[il * d + t] - s2[jl * d + t];
-        r1 += fabs(dx);
-        r2 += dx * dx;
-        if constexpr (FAM == 2) r3 += s1[il * d + t] * s2[jl * d + t];
-        if (t == -1 - which_op) dxd = dx;
-        if constexpr (FAM == 2) {
-          if (t == -1 - which_op) zz = s1[il * d + t] * s2[jl * d + t];
-        }
-      }
-      const T dk = which_op >= 0 ? eval_kprog_deriv<T, FAM>(kp, which_op, which_param, r1, r2, r3)
-                                 : eval_kprog_deriv_dim<T, FAM>(kp, r1, r2, r1 > T(0) ? fabs(dxd) / r1 : T(0),
-                                                                r2 > T(0) ? dxd * dxd / r2 : T(0), r3, zz);
-      const T gij = ai * alpha[gj] - Kc[gi * R + (gj - c0)];
-      acc += double(gij) * double(dk) * (gi == gj ? 0.5 : 1.0);
-    }
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int sft = 128; sft > 0; sft >>= 1) {
-    if ((int)threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[tile_id] = red[0];
-}
-
-// *out += sum(partial) (one workgroup, fixed tree: deterministic)
-__global__ __launch_bounds__(1024) void add_partials_kernel(int64_t count, const double* __restrict__ partial,
+// *out = sum(partial), or *out += sum(partial) (one workgroup, fixed tree: deterministic)
+template <bool ACCUMULATE>
+__global__ __launch_bounds__(1024) void sum_partials_kernel(int64_t count, const double* __restrict__ partial,
                                                             double* __restrict__ out) {
-  __shared__ double red[1024];
-  double acc = 0;
-  for (int64_t i = threadIdx.x; i < count; i += 1024) acc += partial[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int sft = 512; sft > 0; sft >>= 1) {
-    if ((int)threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
-    __syncthreads();
+  double acc[1] = {0};
+  for (int64_t i = threadIdx.x; i < count; i += 1024) acc[0] += partial[i];
+  block_sum<1024, 1>(acc);
+  if (threadIdx.x == 0) {
+    if constexpr (ACCUMULATE) *out += acc[0];
+    else *out = acc[0];
   }
-  if (threadIdx.x == 0) *out += red[0];
 }
 
 // diag[c0 + r] = Kc[c0 + r, r] for the chunk's columns (K^-1_jj: the noise gradient's second term)
@@ -622,20 +682,6 @@ __global__ __launch_bounds__(256) void kcols_diag_kernel(int64_t n, const T* __r
                                                          T* __restrict__ diag) {
   const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
   if (r < R && c0 + r < n) diag[c0 + r] = Kc[(c0 + r) * R + r];
-}
-
-__global__ __launch_bounds__(1024) void sum_partials_kernel(int64_t count, const double* __restrict__ partial,
-                                                            double* __restrict__ out) {
-  __shared__ double red[1024];
-  double acc = 0;
-  for (int64_t i = threadIdx.x; i < count; i += 1024) acc += partial[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int sft = 512; sft > 0; sft >>= 1) {
-    if ((int)threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = red[0];
 }
 
 // d loglik / d noise_i = 1/2 (alpha_i^2 - Kinv_ii)
@@ -668,10 +714,10 @@ __global__ __launch_bounds__(256) void kdiag_kernel(KProg kp, int64_t n, int d, 
 // Fused K9: partial[chunk][r][i] = sum_{j in chunk} k(X1[i], X2[j]) v[r][j] for up to GV_NV
 // right-hand sides at once (every kernel value is evaluated ONCE per pass, whatever the number
 // of columns of `y` in Kernel.matmul).  One lane per row i, X2 / v chunks staged through LDS and
-// broadcast-read.
+// broadcast-read.  Eval: GeneralEval, or FastEval with its inner loop unrolled twice.
 constexpr int GV_ROWS = 256, GV_JB = 256, GV_NV = 8;
-template <typename T, int FAM>
-__global__ __launch_bounds__(256) void kmat_gemv_kernel(KProg kp, int64_t n1, int64_t n2, int d,
+template <typename T, typename Eval>
+__global__ __launch_bounds__(256) void kmat_gemv_kernel(Eval ev, int64_t n1, int64_t n2, int d,
                                                         const T* __restrict__ X1,
                                                         const T* __restrict__ X2,
                                                         const T* __restrict__ v, int nv,
@@ -697,153 +743,11 @@ __global__ __launch_bounds__(256) void kmat_gemv_kernel(KProg kp, int64_t n1, in
       sv[t] = (r < nv) ? v[int64_t(r) * n2 + jb + jj] : T(0);
     }
     __syncthreads();
+#pragma unroll Eval::UNROLL
     for (int jj = 0; jj < cnt; ++jj) {
-      T r1 = 0, r2 = 0, r3 = 0;
-#pragma unroll
-      for (int t = 0; t < TGP_MAX_DIM; ++t) {
-        if (t < d) {
-          const T dx = xi[t] - sx[jj * d + t];
-          r1 += fabs(dx);
-          r2 += dx * dx;
-          if constexpr (FAM == 2) r3 += xi[t] * sx[jj * d + t];
-        }
-      }
-      const T kv = eval_kprog<T, FAM>(kp, r1, r2, r3);
-#pragma unroll
-      for (int r = 0; r < GV_NV; ++r) acc[r] += kv * sv[jj * GV_NV + r];
-    }
-  }
-  if (i < n1)
-    for (int r = 0; r < nv; ++r) partial[(int64_t(blockIdx.y) * nv + r) * n1 + i] = acc[r];
-}
-
-
-
-// d(leaf)/d(scale), the expressions of leaf_deriv with op and metric fixed at compile time
-template <typename T, int OP, int L2>
-__device__ __forceinline__ T leaf_deriv_fast(T r1, T r2, T p0) {
-  if constexpr (OP == TGP_K_EXPSQ) {
-    const T sq = L2 ? r2 : r1 * r1;
-    return exp(T(-0.5) * (sq / (p0 * p0))) * sq / (p0 * p0 * p0);
-  } else {
-    const T dist = L2 ? ((r2 == T(0)) ? r1 : sqrt(r2)) : r1;
-    if constexpr (OP == TGP_K_EXP) {
-      return exp(-dist / p0) * dist / (p0 * p0);
-    } else if constexpr (OP == TGP_K_M32) {
-      const T a = MathC<T>::SQRT3 * (dist / p0);
-      return a * a * exp(-a) / p0;
-    } else {
-      const T a = MathC<T>::SQRT5 * (dist / p0);
-      return (a * a / T(3)) * (T(1) + a) * exp(-a) / p0;
-    }
-  }
-}
-
-// kgrad_kernel for "leaf" / "amp * leaf" programs: BOTH derivatives (d/d amp = leaf,
-// d/d scale = amp * d leaf) in one pass over K^-1.  partial[tile] and partial[ntiles + tile].
-template <typename T, int OP, int L2>
-__global__ __launch_bounds__(256) void kgrad_fast_kernel(T p0, T amp, int64_t n, int d,
-                                                         const T* __restrict__ X,
-                                                         const T* __restrict__ alpha,
-                                                         const T* __restrict__ Kinv, int64_t ld,
-                                                         double* __restrict__ partial) {
-  const int tr = blockIdx.x, tc = blockIdx.y;
-  const int tile_id = tr * gridDim.y + tc, ntiles = gridDim.x * gridDim.y;
-  if (tr < tc) {
-    if (threadIdx.x == 0) partial[tile_id] = partial[ntiles + tile_id] = 0.0;
-    return;
-  }
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* s1 = reinterpret_cast<T*>(smem);  // [KT][d]
-  T* s2 = s1 + KT * d;                 // [KT][d]
-  __shared__ double red[2][256];
-  const int64_t r0 = int64_t(tr) * KT, c0 = int64_t(tc) * KT;
-  for (int t = threadIdx.x; t < KT * d; t += 256) {
-    const int64_t gi = r0 + t / d, gj = c0 + t / d;
-    s1[t] = (gi < n) ? X[gi * d + t % d] : T(0);
-    s2[t] = (gj < n) ? X[gj * d + t % d] : T(0);
-  }
-  __syncthreads();
-  const int il = threadIdx.x & (KT - 1), g = threadIdx.x >> 7;
-  const int64_t gi = r0 + il;
-  const T ai = (gi < n) ? alpha[gi] : T(0);
-  const T p0sq = p0 * p0;
-  double acc_a = 0.0, acc_s = 0.0;
-  if (gi < n) {
-    for (int c = 0; c < KT / 2; ++c) {
-      const int jl = g * (KT / 2) + c;
-      const int64_t gj = c0 + jl;
-      if (gj >= n || gj > gi) continue;
-      T r1 = 0, r2 = 0;
-      for (int t = 0; t < d; ++t) {
-        const T dx = s1[il * d + t] - s2[jl * d + t];
-        r1 += fabs(dx);
-        r2 += dx * dx;
-      }
-      const T leaf = leaf_fast<T, OP, L2>(r1, r2, p0, p0sq);
-      const T dk = amp * leaf_deriv_fast<T, OP, L2>(r1, r2, p0);
-      const double w = double(ai * alpha[gj] - Kinv[gj * ld + gi]) * (gi == gj ? 0.5 : 1.0);
-      acc_a += w * double(leaf);
-      acc_s += w * double(dk);
-    }
-  }
-  red[0][threadIdx.x] = acc_a;
-  red[1][threadIdx.x] = acc_s;
-  __syncthreads();
-  for (int sft = 128; sft > 0; sft >>= 1) {
-    if ((int)threadIdx.x < sft) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + sft];
-      red[1][threadIdx.x] += red[1][threadIdx.x + sft];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    partial[tile_id] = red[0][0];
-    partial[ntiles + tile_id] = red[1][0];
-  }
-}
-
-// the same for "leaf" / "amp * leaf" programs: straight-line inner loop (see kmat_fast_kernel)
-template <typename T, int OP, int L2>
-__global__ __launch_bounds__(256) void kmat_gemv_fast_kernel(T p0, T amp, int64_t n1, int64_t n2, int d,
-                                                             const T* __restrict__ X1,
-                                                             const T* __restrict__ X2,
-                                                             const T* __restrict__ v, int nv,
-                                                             T* __restrict__ partial, int64_t jchunk) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* sx = reinterpret_cast<T*>(smem);  // [GV_JB][d]
-  T* sv = sx + GV_JB * d;              // [GV_JB][GV_NV]
-  const int64_t i = int64_t(blockIdx.x) * GV_ROWS + threadIdx.x;
-  const int64_t j0 = int64_t(blockIdx.y) * jchunk;
-  const int64_t j1 = (j0 + jchunk < n2) ? j0 + jchunk : n2;
-  T xi[TGP_MAX_DIM];
-#pragma unroll
-  for (int t = 0; t < TGP_MAX_DIM; ++t) xi[t] = (t < d && i < n1) ? X1[i * d + t] : T(0);
-  const T p0sq = p0 * p0;
-  T acc[GV_NV];
-#pragma unroll
-  for (int r = 0; r < GV_NV; ++r) acc[r] = 0;
-  for (int64_t jb = j0; jb < j1; jb += GV_JB) {
-    const int cnt = int((j1 - jb < GV_JB) ? (j1 - jb) : GV_JB);
-    __syncthreads();
-    for (int t = threadIdx.x; t < cnt * d; t += 256) sx[t] = X2[jb * d + t];
-    for (int t = threadIdx.x; t < cnt * GV_NV; t += 256) {
-      const int jj = t / GV_NV, r = t % GV_NV;
-      sv[t] = (r < nv) ? v[int64_t(r) * n2 + jb + jj] : T(0);
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int jj = 0; jj < cnt; ++jj) {
-      T r1 = 0, r2 = 0;
-#pragma unroll
-      for (int t = 0; t < TGP_MAX_DIM; ++t) {
-        if (t < d) {
-          const T dx = xi[t] - sx[jj * d + t];
-          r1 += fabs(dx);
-          r2 += dx * dx;
-        }
-      }
-      const T kv = amp * leaf_fast<T, OP, L2>(r1, r2, p0, p0sq);
+      T r1, r2, r3;
+      pair_dist<T, Eval::FAMILY, TGP_MAX_DIM, true>(xi, sx + jj * d, d, r1, r2, r3);
+      const T kv = ev.value(r1, r2, r3);
 #pragma unroll
       for (int r = 0; r < GV_NV; ++r) acc[r] += kv * sv[jj * GV_NV + r];
     }
@@ -916,6 +820,49 @@ static int kfamily(const KProg& kp) {
   return exp_family(kp) ? 1 : 0;
 }
 
+// ---- run-time values to template arguments: f is a generic lambda taking std::integral_constants ----------------
+template <int V> using IC = std::integral_constant<int, V>;
+
+// f(OP, L2) for the leaf and metric of a fast program (fp.op >= 0)
+template <typename F>
+static void with_fast_leaf(const FastProg& fp, F&& f) {
+  auto with_metric = [&](auto op) {
+    if (fp.l2) f(op, IC<1>{});
+    else f(op, IC<0>{});
+  };
+  switch (fp.op) {
+    case TGP_K_EXP: with_metric(IC<TGP_K_EXP>{}); break;
+    case TGP_K_EXPSQ: with_metric(IC<TGP_K_EXPSQ>{}); break;
+    case TGP_K_M32: with_metric(IC<TGP_K_M32>{}); break;
+    default: with_metric(IC<TGP_K_M52>{}); break;
+  }
+}
+
+// f(FAM) for the program's family; entry points without an exp-family instantiation (EXP_FAMILY = false: the
+// gradient and the diagonal) take the general one, FAM = 0, for those programs
+template <bool EXP_FAMILY, typename F>
+static void with_family(const KProg& kp, F&& f) {
+  const int fam = kfamily(kp);
+  if (fam == 2) return f(IC<2>{});
+  if constexpr (EXP_FAMILY) {
+    if (fam == 1) return f(IC<1>{});
+  }
+  f(IC<0>{});
+}
+
+// f(D) with D = d up to MAXD (3 or 4); beyond it D = 0, the dynamic loop, where MAXD = 4, and nothing where MAXD = 3
+// (kmat_fast_kernel has no such form)
+template <int MAXD, typename F>
+static void with_dim(int d, F&& f) {
+  if (d == 1) f(IC<1>{});
+  else if (d == 2) f(IC<2>{});
+  else if (d == 3) f(IC<3>{});
+  else if constexpr (MAXD == 4) {
+    if (d == 4) f(IC<4>{});
+    else f(IC<0>{});
+  }
+}
+
 template <typename T>
 int launch_kmat_cols(tgp_ctx* ctx, hipStream_t st, const KProg& kp, int64_t n1, int64_t n2, int d,
                      const T* X1, const T* X2, const T* diag, T* out, int64_t ld, int64_t rows_out,
@@ -945,29 +892,14 @@ int launch_kmat_cols(tgp_ctx* ctx, hipStream_t st, const KProg& kp, int64_t n1, 
     if (any) {
       dim3 fgrid((unsigned)ftr, (unsigned)fc);
       if (flags & KMAT_LOWER) fgrid = dim3((unsigned)(tri_c * tri_h - tri_c * (tri_c - 1) / 2));
-#define TGP_FAST3(DD, OP, L2)                                                                     \
-  hipLaunchKernelGGL((kmat_fast_kernel<T, DD, OP, L2>), fgrid, dim3(256), 0, st, T(fp.p0),        \
-                     T(fp.amp), n1, n2, X1, X2, diag, out, ld, flags | (ctx->kmat_plain_div != 0 ? KMAT_PLAIN_DIV : 0), (int)tc0,  \
-                     (int)tri_h)
-#define TGP_FAST2(DD, OP)                                                                         \
-  do {                                                                                           \
-    if (fp.l2) TGP_FAST3(DD, OP, 1); else TGP_FAST3(DD, OP, 0);                                   \
-  } while (0)
-#define TGP_FAST1(DD)                                                                             \
-  do {                                                                                           \
-    switch (fp.op) {                                                                             \
-      case TGP_K_EXP: TGP_FAST2(DD, TGP_K_EXP); break;                                            \
-      case TGP_K_EXPSQ: TGP_FAST2(DD, TGP_K_EXPSQ); break;                                        \
-      case TGP_K_M32: TGP_FAST2(DD, TGP_K_M32); break;                                            \
-      default: TGP_FAST2(DD, TGP_K_M52); break;                                                   \
-    }                                                                                            \
-  } while (0)
-      if (d == 1) TGP_FAST1(1);
-      else if (d == 2) TGP_FAST1(2);
-      else TGP_FAST1(3);
-#undef TGP_FAST1
-#undef TGP_FAST2
-#undef TGP_FAST3
+      const int fflags = flags | (ctx->kmat_plain_div != 0 ? KMAT_PLAIN_DIV : 0);
+      with_dim<3>(d, [&](auto dd) {
+        with_fast_leaf(fp, [&](auto op, auto l2) {
+          constexpr int D = decltype(dd)::value, OP = decltype(op)::value, L2 = decltype(l2)::value;
+          hipLaunchKernelGGL((kmat_fast_kernel<T, D, OP, L2>), fgrid, dim3(256), 0, st, T(fp.p0), T(fp.amp), n1, n2, X1,
+                             X2, diag, out, ld, fflags, (int)tc0, (int)tri_h);
+        });
+      });
     } else {
       ftr = ftc = 0;
     }
@@ -978,27 +910,13 @@ int launch_kmat_cols(tgp_ctx* ctx, hipStream_t st, const KProg& kp, int64_t n1, 
   }
   dim3 grid((unsigned)tr, (unsigned)ntc);
   const size_t shmem = 2 * size_t(KT) * d * sizeof(T);
-  const int fam = kfamily(kp);
-#define TGP_KMAT_LAUNCH(DD)                                                                      \
-  do {                                                                                           \
-    if (fam == 2)                                                                                \
-      hipLaunchKernelGGL((kmat_kernel<T, DD, 2>), grid, dim3(256), shmem, st, kp, n1, n2, d, X1, \
-                         X2, diag, out, ld, rows_out, cols_out, flags, (int)tc0, ftr, ftc);      \
-    else if (fam == 1)                                                                           \
-      hipLaunchKernelGGL((kmat_kernel<T, DD, 1>), grid, dim3(256), shmem, st, kp, n1, n2, d, X1, \
-                         X2, diag, out, ld, rows_out, cols_out, flags, (int)tc0, ftr, ftc);      \
-    else                                                                                         \
-      hipLaunchKernelGGL((kmat_kernel<T, DD, 0>), grid, dim3(256), shmem, st, kp, n1, n2, d, X1, \
-                         X2, diag, out, ld, rows_out, cols_out, flags, (int)tc0, ftr, ftc);      \
-  } while (0)
-  switch (d) {
-    case 1: TGP_KMAT_LAUNCH(1); break;
-    case 2: TGP_KMAT_LAUNCH(2); break;
-    case 3: TGP_KMAT_LAUNCH(3); break;
-    case 4: TGP_KMAT_LAUNCH(4); break;
-    default: TGP_KMAT_LAUNCH(0); break;
-  }
-#undef TGP_KMAT_LAUNCH
+  with_dim<4>(d, [&](auto dd) {
+    with_family<true>(kp, [&](auto fam) {
+      constexpr int D = decltype(dd)::value, FAM = decltype(fam)::value;
+      hipLaunchKernelGGL((kmat_kernel<T, D, FAM>), grid, dim3(256), shmem, st, kp, n1, n2, d, X1, X2, diag, out, ld,
+                         rows_out, cols_out, flags, (int)tc0, ftr, ftc);
+    });
+  });
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
@@ -1015,12 +933,12 @@ template <typename T>
 int launch_kdiag(tgp_ctx* ctx, const KProg& kp, int64_t n, int d, const T* X, const T* add, T* out) {
   if (n == 0) return TGP_OK;
   const dim3 grid((unsigned)((n + 255) / 256));
-  if (kfamily(kp) == 2) {
+  if (kfamily(kp) == 2)
     TGP_ARG_CHECK(X != nullptr && d >= 1 && d <= TGP_MAX_DIM, "kdiag: a DOT program needs the points");
-    hipLaunchKernelGGL((kdiag_kernel<T, 2>), grid, dim3(256), 0, ctx->stream, kp, n, d, X, add, out);
-  } else {
-    hipLaunchKernelGGL((kdiag_kernel<T, 0>), grid, dim3(256), 0, ctx->stream, kp, n, d, X, add, out);
-  }
+  with_family<false>(kp, [&](auto fam) {
+    constexpr int FAM = decltype(fam)::value;
+    hipLaunchKernelGGL((kdiag_kernel<T, FAM>), grid, dim3(256), 0, ctx->stream, kp, n, d, X, add, out);
+  });
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
@@ -1047,29 +965,17 @@ int launch_kmat_gemv_multi(tgp_ctx* ctx, const KProg& kp, int64_t n1, int64_t n2
   const size_t shmem = size_t(GV_JB) * (d + GV_NV) * sizeof(T);
   for (int64_t r0 = 0; r0 < nv_total; r0 += GV_NV) {
     const int nv = int(std::min<int64_t>(GV_NV, nv_total - r0));
+    auto launch = [&](auto ev) {
+      hipLaunchKernelGGL((kmat_gemv_kernel<T, decltype(ev)>), dim3((unsigned)rb, (unsigned)nch), dim3(256), shmem,
+                         ctx->stream, ev, n1, n2, d, X1, X2, v + r0 * n2, nv, partial, jchunk);
+    };
     const FastProg fp = fast_prog(kp);
-#define TGP_GV3(OP, L2)                                                                             \
-  hipLaunchKernelGGL((kmat_gemv_fast_kernel<T, OP, L2>), dim3((unsigned)rb, (unsigned)nch), dim3(256), shmem, \
-                     ctx->stream, T(fp.p0), T(fp.amp), n1, n2, d, X1, X2, v + r0 * n2, nv, partial, jchunk)
-#define TGP_GV2(OP)                                                                                 \
-  do {                                                                                             \
-    if (fp.l2) TGP_GV3(OP, 1); else TGP_GV3(OP, 0);                                                 \
-  } while (0)
-    if (fp.op == TGP_K_EXP) TGP_GV2(TGP_K_EXP);
-    else if (fp.op == TGP_K_EXPSQ) TGP_GV2(TGP_K_EXPSQ);
-    else if (fp.op == TGP_K_M32) TGP_GV2(TGP_K_M32);
-    else if (fp.op == TGP_K_M52) TGP_GV2(TGP_K_M52);
-#undef TGP_GV2
-#undef TGP_GV3
-    else if (kfamily(kp) == 2)
-      hipLaunchKernelGGL((kmat_gemv_kernel<T, 2>), dim3((unsigned)rb, (unsigned)nch), dim3(256), shmem,
-                         ctx->stream, kp, n1, n2, d, X1, X2, v + r0 * n2, nv, partial, jchunk);
-    else if (exp_family(kp))
-      hipLaunchKernelGGL((kmat_gemv_kernel<T, 1>), dim3((unsigned)rb, (unsigned)nch), dim3(256), shmem,
-                         ctx->stream, kp, n1, n2, d, X1, X2, v + r0 * n2, nv, partial, jchunk);
+    if (fp.op >= 0)
+      with_fast_leaf(fp, [&](auto op, auto l2) {
+        launch(FastEval<T, decltype(op)::value, decltype(l2)::value>{T(fp.p0), T(fp.amp)});
+      });
     else
-      hipLaunchKernelGGL((kmat_gemv_kernel<T, 0>), dim3((unsigned)rb, (unsigned)nch), dim3(256), shmem,
-                         ctx->stream, kp, n1, n2, d, X1, X2, v + r0 * n2, nv, partial, jchunk);
+      with_family<true>(kp, [&](auto fam) { launch(GeneralEval<T, decltype(fam)::value>{kp, 0, 0}); });
     hipLaunchKernelGGL((reduce_partials_kernel<T>), dim3((unsigned)((n1 + 255) / 256), (unsigned)nv), dim3(256), 0,
                        ctx->stream, n1, (int)nch, nv, partial, out + r0 * n1);
   }
@@ -1083,46 +989,51 @@ int launch_kmat_gemv(tgp_ctx* ctx, const KProg& kp, int64_t n1, int64_t n2, int 
   return launch_kmat_gemv_multi<T>(ctx, kp, n1, n2, d, X1, X2, v, 1, out);
 }
 
+// The gradient launchers' common body: kgrad_tile_kernel over tr x tc tiles, then each of the evaluator's sums over
+// the tiles into out[s] (added to it where the source accumulates).
+template <typename T, typename Eval, typename Src>
+static int run_kgrad(tgp_ctx* ctx, const Eval& ev, const Src& src, int64_t tr, int64_t tc, int64_t n, int d,
+                     const T* X, const T* alpha, double* out) {
+  const int64_t tiles = tr * tc;
+  TGP_TRY(ensure_work(ctx, Eval::NSUM * size_t(tiles) * sizeof(double)));
+  double* partial = static_cast<double*>(ctx->d_work);
+  const size_t shmem = 2 * size_t(KT) * d * sizeof(T);
+  hipLaunchKernelGGL((kgrad_tile_kernel<T, Eval, Src>), dim3((unsigned)tr, (unsigned)tc), dim3(256), shmem,
+                     ctx->stream, ev, src, n, d, X, alpha, partial);
+  for (int s = 0; s < Eval::NSUM; ++s)
+    hipLaunchKernelGGL((sum_partials_kernel<Src::ACCUMULATE>), dim3(1), dim3(1024), 0, ctx->stream, tiles,
+                       partial + s * tiles, out + s);
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
 template <typename T>
 int launch_kgrad(tgp_ctx* ctx, const KProg& kp, int which_op, int which_param, int64_t n, int d,
                  const T* X, const T* alpha, const T* Kinv, int64_t ld, double* out_dev) {
   const int64_t tiles = (n + KT - 1) / KT;
   TGP_ARG_CHECK(tiles <= 65535, "kgrad: too many tiles");
-  TGP_TRY(ensure_work(ctx, size_t(tiles) * tiles * sizeof(double)));
-  double* partial = static_cast<double*>(ctx->d_work);
-  const size_t shmem = 2 * size_t(KT) * d * sizeof(T);
-  if (kfamily(kp) == 2)
-    hipLaunchKernelGGL((kgrad_kernel<T, 2>), dim3((unsigned)tiles, (unsigned)tiles), dim3(256), shmem,
-                       ctx->stream, kp, which_op, which_param, n, d, X, alpha, Kinv, ld, partial);
-  else
-    hipLaunchKernelGGL((kgrad_kernel<T, 0>), dim3((unsigned)tiles, (unsigned)tiles), dim3(256), shmem,
-                       ctx->stream, kp, which_op, which_param, n, d, X, alpha, Kinv, ld, partial);
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles * tiles, partial,
-                     out_dev);
-  TGP_HIP_TRY(hipGetLastError());
-  return TGP_OK;
+  int rc = TGP_OK;
+  with_family<false>(kp, [&](auto fam) {
+    const GeneralEval<T, decltype(fam)::value> ev{kp, which_op, which_param};
+    rc = run_kgrad<T>(ctx, ev, SquareKinv<T>{Kinv, ld}, tiles, tiles, n, d, X, alpha, out_dev);
+  });
+  return rc;
 }
 
 // out_accum[0] += this rank's share of  sum_{i >= j, j in chunk} w_ij (alpha_i alpha_j - Kinv_ij) dK_ij / dtheta  over the
-// chunk of R columns from c0 (Kc: (n_pad, R) row-major); diag_out (or NULL) receives the chunk's K^-1_jj
+// chunk of R columns from c0 (Kc: (n_pad, R) row-major)
 template <typename T>
 int launch_kgrad_cols(tgp_ctx* ctx, const KProg& kp, int which_op, int which_param, int64_t n, int d, const T* X,
                       const T* alpha, const T* Kc, int64_t R, int64_t c0, int64_t nb, int G, int rank,
                       double* out_accum) {
   const int64_t tr = (n + KT - 1) / KT, tc = (std::min<int64_t>(R, n - c0) + KT - 1) / KT;
   TGP_ARG_CHECK(tr <= 65535 && tc >= 1 && tc <= 65535 && c0 % KT == 0, "kgrad_cols: bad chunk");
-  TGP_TRY(ensure_work(ctx, size_t(tr) * tc * sizeof(double)));
-  double* partial = static_cast<double*>(ctx->d_work);
-  const size_t shmem = 2 * size_t(KT) * d * sizeof(T);
-  if (kfamily(kp) == 2)
-    hipLaunchKernelGGL((kgrad_cols_kernel<T, 2>), dim3((unsigned)tr, (unsigned)tc), dim3(256), shmem, ctx->stream,
-                       kp, which_op, which_param, n, d, X, alpha, Kc, R, c0, nb, G, rank, partial);
-  else
-    hipLaunchKernelGGL((kgrad_cols_kernel<T, 0>), dim3((unsigned)tr, (unsigned)tc), dim3(256), shmem, ctx->stream,
-                       kp, which_op, which_param, n, d, X, alpha, Kc, R, c0, nb, G, rank, partial);
-  hipLaunchKernelGGL(add_partials_kernel, dim3(1), dim3(1024), 0, ctx->stream, tr * tc, partial, out_accum);
-  TGP_HIP_TRY(hipGetLastError());
-  return TGP_OK;
+  int rc = TGP_OK;
+  with_family<false>(kp, [&](auto fam) {
+    const GeneralEval<T, decltype(fam)::value> ev{kp, which_op, which_param};
+    rc = run_kgrad<T>(ctx, ev, ChunkKinv<T>{Kc, R, c0, nb, G, rank}, tr, tc, n, d, X, alpha, out_accum);
+  });
+  return rc;
 }
 
 template <typename T>
@@ -1143,27 +1054,12 @@ int launch_kgrad_fast(tgp_ctx* ctx, const KProg& kp, int64_t n, int d, const T* 
   if (fp.op < 0) return 0;
   const int64_t tiles = (n + KT - 1) / KT;
   TGP_ARG_CHECK(tiles <= 65535, "kgrad: too many tiles");
-  TGP_TRY(ensure_work(ctx, 2 * size_t(tiles) * tiles * sizeof(double)));
-  double* partial = static_cast<double*>(ctx->d_work);
-  const size_t shmem = 2 * size_t(KT) * d * sizeof(T);
-  const dim3 grid((unsigned)tiles, (unsigned)tiles);
-#define TGP_KG3(OP, L2)                                                                            \
-  hipLaunchKernelGGL((kgrad_fast_kernel<T, OP, L2>), grid, dim3(256), shmem, ctx->stream, T(fp.p0), \
-                     T(fp.amp), n, d, X, alpha, Kinv, ld, partial)
-#define TGP_KG2(OP)                                                                                \
-  do {                                                                                            \
-    if (fp.l2) TGP_KG3(OP, 1); else TGP_KG3(OP, 0);                                                \
-  } while (0)
-  if (fp.op == TGP_K_EXP) TGP_KG2(TGP_K_EXP);
-  else if (fp.op == TGP_K_EXPSQ) TGP_KG2(TGP_K_EXPSQ);
-  else if (fp.op == TGP_K_M32) TGP_KG2(TGP_K_M32);
-  else TGP_KG2(TGP_K_M52);
-#undef TGP_KG2
-#undef TGP_KG3
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles * tiles, partial, out_dev);
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles * tiles,
-                     partial + tiles * tiles, out_dev + 1);
-  TGP_HIP_TRY(hipGetLastError());
+  int rc = TGP_OK;
+  with_fast_leaf(fp, [&](auto op, auto l2) {
+    const FastEval<T, decltype(op)::value, decltype(l2)::value> ev{T(fp.p0), T(fp.amp)};
+    rc = run_kgrad<T>(ctx, ev, SquareKinv<T>{Kinv, ld}, tiles, tiles, n, d, X, alpha, out_dev);
+  });
+  if (rc != TGP_OK) return rc;
   *leaf = fp.leaf;
   *konst = fp.konst;
   return 1;
