@@ -651,6 +651,24 @@ int tgp_qsep_logprob_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_
                            int32_t J, const double* hvec, const double* Pinf, const double* noise_host,
                            int64_t noise_stride, const double* resid_host, int64_t resid_stride, int32_t* info,
                            double* out, int32_t* nchains);
+/* Value and gradient (as tgp_qsep_grad) of nb models over the handle's series, evaluated together.  Models, noise and
+ * residual as in tgp_qsep_logprob_batch; every member has ndir directions, member b's `dleaves` (nb x ndir x nleaves x 4),
+ * `dh` (nb x ndir x J) and `dPinf` (nb x ndir x J x J) following member b - 1's.  info (nb), out (nb), dout (nb x ndir),
+ * gnoise_host and alpha_host (nb x n each; either may be NULL and its scan is then skipped): per member, each with the
+ * bits of tgp_qsep_grad with that member's model, noise, residual and directions, whatever nb, its position and the
+ * split.  ndir = 0 with both vectors NULL is the value alone.  A non-positive pivot sets that member's info to its 1-based
+ * step and its out, dout and vectors to NaN and touches no other member.  A launch chain (one stream synchronisation)
+ * holds at most 64 members, a direction pass inside it at most 8 directions per member, and the chain's device scratch
+ * stays under 1 GiB: as many members as fit with one direction each, then as many directions per pass as the rest
+ * holds ("Batches of gradients", states the layout).  *nchains and *npasses (may be NULL) report the
+ * chains and the direction passes (summed over the chains) that ran.  A series whose single member with a single
+ * direction exceeds the cap is an argument error.  The handle's resident model, noise, factor and gradient state are
+ * neither read nor changed; it need not be factored.  nb = 0 returns at once. */
+int tgp_qsep_grad_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                        int32_t J, const double* hvec, const double* Pinf, const double* noise_host,
+                        int64_t noise_stride, const double* resid_host, int64_t resid_stride, int32_t ndir,
+                        const double* dleaves, const double* dh, const double* dPinf, int32_t* info, double* out,
+                        double* dout, double* gnoise_host, double* alpha_host, int32_t* nchains, int32_t* npasses);
 
 #ifdef __cplusplus
 }

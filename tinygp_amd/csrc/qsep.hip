@@ -29,7 +29,7 @@
 // and both scan kernels serve one model per blockIdx.y (qs_finish: per block) over the shared t: model mp[blockIdx.y],
 // every array of that member `stride` doubles after its neighbour's.  A single evaluation is the batch of one (grid
 // y = 1, where no stride matters): launch_factor and launch_affine enqueue the chain for both, so a member's result
-// has the bits of its single call.
+// has the bits of its single call.  The gradient's kernels take the same member axis (see "gradient" below).
 #include "tgp_common.h"
 
 #include <algorithm>
@@ -715,11 +715,15 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_fold(int dir, int want_mea
                                                            const double* __restrict__ cbuf,
                                                            const double* __restrict__ wbuf,
                                                            const double* __restrict__ alpha, int64_t n, int64_t lc,
-                                                           int64_t nchunks, double* __restrict__ elem) {
+                                                           int64_t nchunks, double* __restrict__ elem,
+                                                           int64_t work_stride) {
   const Lane L;
   if (L.wave >= nchunks) return;
-  const QModel& m = *mp;
+  const int64_t mem = blockIdx.y;  // member: c, w and alpha as in qs_aff_emit, elements work_stride apart
+  const QModel& m = mp[mem];
   const int J = m.J, r = L.r, c = L.c;
+  cbuf += mem * n, wbuf += mem * n * J, elem += mem * work_stride;
+  if (alpha) alpha += mem * n;
   const double Ph_r = Xh(m, m.P[L.lane], r);
   const double I = (r == c && r < J) ? 1.0 : 0.0;
   double M = I, V = 0.0, Mf = I, Vf = 0.0;
@@ -859,6 +863,10 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_emit(int dir, int want_mea
 // direction) and a per-chunk sum of dc_n / c_n; the solve pass, which needs them, a per-chunk sum of z_n dz_n:
 //   d log p = -1/2 sum dc_n / c_n - sum z_n dz_n.
 // Scan elements are (M, V), `ndir` independent scans interleaved as element * ndir + direction.
+// Batches of models: member blockIdx.z (qs_pred_fold and qs_invdiag_emit, which have no direction: blockIdx.y) with
+// model mp[member] and directions dirs[member * ndir + direction].  Noise, residual, kept prefixes and scan work space
+// lie one stride per member apart (0: shared); c, w, alpha and the noise gradient n (n J) apart as in qs_emit; dc, dw
+// and the per-chunk sums are indexed by member * ndir + direction.  The single call is member 0 of one.
 struct GStep {
   double Phi, cv, dc, w, dw;  // w, dw: by row
 };
@@ -889,13 +897,16 @@ __device__ __forceinline__ GStep gfac_step(const QModel& m, const QDir& d, const
 
 __global__ __launch_bounds__(WAVE * WPB) void qs_gfac_fold(const QModel* __restrict__ mp,
                                                            const QDir* __restrict__ dirs, const double* __restrict__ t,
-                                                           const double* __restrict__ noise, int64_t n, int64_t lc,
-                                                           int64_t nchunks, const double* __restrict__ prefixP,
-                                                           double* __restrict__ elem) {
+                                                           const double* __restrict__ noise, int64_t noise_stride,
+                                                           int64_t n, int64_t lc, int64_t nchunks,
+                                                           const double* __restrict__ prefixP, int64_t keep_stride,
+                                                           double* __restrict__ elem, int64_t work_stride) {
   const Lane L;
   if (L.wave >= nchunks) return;
-  const QModel& m = *mp;
-  const QDir& d = dirs[blockIdx.y];
+  const int64_t mem = blockIdx.z;
+  const QModel& m = mp[mem];
+  const QDir& d = dirs[mem * gridDim.y + blockIdx.y];
+  noise += mem * noise_stride, prefixP += mem * keep_stride, elem += mem * work_stride;
   const int J = m.J, r = L.r, c = L.c;
   const double Pinf = m.P[L.lane], dPinf = d.dP[L.lane];
   double P = prefixP[L.wave * WAVE + L.lane], V = 0.0, M = (r == c && r < J) ? 1.0 : 0.0;
@@ -909,22 +920,25 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_gfac_fold(const QModel* __restr
   e[L.lane] = M, e[WAVE + L.lane] = V;
 }
 
-// dcbuf: ndir x n, dwbuf: ndir x n x J, dsum: ndir x nchunks
+// dcbuf: members x ndir x n, dwbuf: members x ndir x n x J, dsum: members x ndir x nchunks
 __global__ __launch_bounds__(WAVE * WPB) void qs_gfac_emit(const QModel* __restrict__ mp,
                                                            const QDir* __restrict__ dirs, const double* __restrict__ t,
-                                                           const double* __restrict__ noise, int64_t n, int64_t lc,
-                                                           int64_t nchunks, const double* __restrict__ prefixP,
-                                                           const double* __restrict__ prefixD,
+                                                           const double* __restrict__ noise, int64_t noise_stride,
+                                                           int64_t n, int64_t lc, int64_t nchunks,
+                                                           const double* __restrict__ prefixP, int64_t keep_stride,
+                                                           const double* __restrict__ prefixD, int64_t work_stride,
                                                            double* __restrict__ dcbuf, double* __restrict__ dwbuf,
                                                            double* __restrict__ dsum) {
   const Lane L;
   if (L.wave >= nchunks) return;
-  const QModel& m = *mp;
-  const int64_t dir = blockIdx.y;
+  const int64_t mem = blockIdx.z, dir = mem * gridDim.y + blockIdx.y;
+  const QModel& m = mp[mem];
   const QDir& d = dirs[dir];
+  noise += mem * noise_stride, prefixP += mem * keep_stride, prefixD += mem * work_stride;
   const int J = m.J, r = L.r, c = L.c;
   const double Pinf = m.P[L.lane], dPinf = d.dP[L.lane];
-  double P = prefixP[L.wave * WAVE + L.lane], dD = prefixD[(L.wave * gridDim.y + dir) * WAVE + L.lane], acc = 0.0;
+  double P = prefixP[L.wave * WAVE + L.lane], acc = 0.0;
+  double dD = prefixD[(L.wave * gridDim.y + blockIdx.y) * WAVE + L.lane];
   const int64_t n0 = L.wave * lc, n1 = min(n, n0 + lc);
   for (int64_t i = n0; i < n1; ++i) {
     const GStep s = gfac_step(m, d, t, noise, i, Pinf, dPinf, P, dD, r, c);
@@ -956,21 +970,24 @@ __device__ __forceinline__ double gsol_step(const QModel& m, const QDir& d, doub
   return z * dz;
 }
 
-// fold (prefixS only) or emit (prefixT too) of the solve's tangent; prefixS: the primal scan's chunk states (column 0)
+// fold (prefixS only) or emit (prefixT too) of the solve's tangent; prefixS: the primal scan's chunk states (column 0).
+// elem and prefixT share the scan's work space, hence its stride.
 __global__ __launch_bounds__(WAVE * WPB) void qs_gsol(const QModel* __restrict__ mp, const QDir* __restrict__ dirs,
                                                       const double* __restrict__ t, const double* __restrict__ cbuf,
                                                       const double* __restrict__ wbuf, const double* __restrict__ dcbuf,
                                                       const double* __restrict__ dwbuf, const double* __restrict__ y,
-                                                      int64_t n, int64_t lc, int64_t nchunks,
-                                                      const double* __restrict__ prefixS,
+                                                      int64_t y_stride, int64_t n, int64_t lc, int64_t nchunks,
+                                                      const double* __restrict__ prefixS, int64_t keep_stride,
                                                       const double* __restrict__ prefixT, double* __restrict__ elem,
-                                                      double* __restrict__ dsum) {
+                                                      int64_t work_stride, double* __restrict__ dsum) {
   const Lane L;
   if (L.wave >= nchunks) return;
-  const QModel& m = *mp;
-  const int64_t dir = blockIdx.y, slot = L.wave * gridDim.y + dir;
+  const int64_t mem = blockIdx.z, dir = mem * gridDim.y + blockIdx.y, slot = L.wave * gridDim.y + blockIdx.y;
+  const QModel& m = mp[mem];
   const QDir& d = dirs[dir];
   const int J = m.J, r = L.r, c = L.c;
+  cbuf += mem * n, wbuf += mem * n * J, y += mem * y_stride, prefixS += mem * keep_stride;
+  if (prefixT) prefixT += mem * work_stride; else elem += mem * work_stride;
   const double h_r = r < J ? m.h[r] : 0.0;
   double s = prefixS[L.wave * WAVE + r * 8], ds = prefixT ? prefixT[slot * WAVE + L.lane] : 0.0;
   double M = (r == c && r < J) ? 1.0 : 0.0, acc = 0.0, o;
@@ -993,17 +1010,21 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_gsol(const QModel* __restrict__
 // ---- gradient with respect to the noise: 1/2 (alpha_n^2 - (K^-1)_nn) -------------------------------------------------
 // (K^-1)_nn = (1 + u^T O_{n+1} u) / c_n, u = A_{n+1} w_n, with O the backward recurrence of the prediction (qs_pred_*,
 // dir 1, variance part): this is its emit pass with N outputs instead of test points.
-__global__ __launch_bounds__(WAVE * WPB) void qs_invdiag_emit(const QModel* __restrict__ mp,
+// (4 waves per SIMD asked for: the member's model pointer costs SGPRs that spill into VGPR lanes, 127 -> 135 without it)
+__global__ __launch_bounds__(WAVE * WPB) __attribute__((amdgpu_waves_per_eu(4, 4))) void qs_invdiag_emit(
+                                                              const QModel* __restrict__ mp,
                                                               const double* __restrict__ t,
                                                               const double* __restrict__ cbuf,
                                                               const double* __restrict__ wbuf,
                                                               const double* __restrict__ alpha, int64_t n, int64_t lc,
                                                               int64_t nchunks, const double* __restrict__ prefix,
-                                                              double* __restrict__ out) {
+                                                              int64_t work_stride, double* __restrict__ out) {
   const Lane L;
   if (L.wave >= nchunks) return;
-  const QModel& m = *mp;
+  const int64_t mem = blockIdx.y;
+  const QModel& m = mp[mem];
   const int J = m.J, r = L.r, c = L.c;
+  cbuf += mem * n, wbuf += mem * n * J, alpha += mem * n, prefix += mem * work_stride, out += mem * n;
   double X = prefix[L.wave * 2 * WAVE + L.lane];
   const Chunk ch(true, L.wave, nchunks, lc, n);
   for (int64_t j = 0, len = ch.len(); j < len; ++j) {
@@ -1050,6 +1071,14 @@ __global__ __launch_bounds__(WAVE) void qs_finish(const double* __restrict__ a, 
     out[0] = sa, out[1] = sb;
     if (first_bad) *first_bad = mb;
   }
+}
+
+// member blockIdx.y: dst[i] = src[i], i < len, the members' rows src_stride and dst_stride doubles apart (the chunk
+// prefixes a scan leaves in its work space, set aside before the next scan writes there)
+__global__ void qs_keep_rows(const double* __restrict__ src, int64_t src_stride, double* __restrict__ dst,
+                             int64_t dst_stride, int64_t len) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, mem = blockIdx.y;
+  if (i < len) dst[mem * dst_stride + i] = src[mem * src_stride + i];
 }
 
 inline int64_t blocks_for(int64_t waves) { return (waves + WPB - 1) / WPB; }
@@ -1335,7 +1364,7 @@ int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const 
   TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanPred>(nc, 1)));
   for (int dir = 0; dir < 2; ++dir) {
     qs_pred_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
-                                                        n, q->lc, nc, q->work);
+                                                        n, q->lc, nc, q->work, 0);
     double* prefix = nullptr;
     TGP_TRY(run_scan<ScanPred>(q->model, st, nc, 1, q->work, &prefix));
     qs_pred_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
@@ -1350,10 +1379,80 @@ int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const 
   return TGP_OK;
 }
 
-// Directions are processed in batches of at most GRAD_MAX_BATCH (the grid's y extent) and of at most GRAD_SCRATCH_BYTES
+// Directions are processed in passes of at most GRAD_MAX_BATCH (the grid's y extent) and of at most GRAD_SCRATCH_BYTES
 // of dc, dw scratch (n (1 + J) doubles per direction), whatever the number of parameters.
 constexpr int64_t GRAD_MAX_BATCH = 8;
 constexpr int64_t GRAD_SCRATCH_BYTES = int64_t(1) << 30;
+constexpr int64_t DIR_DOUBLES = sizeof(QDir) / sizeof(double);
+static_assert(sizeof(QDir) % sizeof(double) == 0, "directions are laid out in a buffer of doubles");
+
+// directions [d0, d0 + nd) of one model's host tangents (dleaves: ndir x nl x 4, dh: ndir x J, dPinf: ndir x J x J)
+void pack_dirs(QDir* out, int64_t d0, int64_t nd, int64_t nl, int64_t J, const double* dleaves, const double* dh,
+               const double* dPinf) {
+  for (int64_t b = 0; b < nd; ++b) {
+    QDir x{};
+    const int64_t d = d0 + b;
+    for (int64_t l = 0; l < nl; ++l)
+      for (int p = 0; p < 4; ++p) x.dpar[l][p] = dleaves[(d * nl + l) * 4 + p];
+    for (int64_t r = 0; r < J; ++r) {
+      x.dh[r] = dh[d * J + r];
+      for (int64_t c = 0; c < J; ++c) x.dP[r * QJ + c] = dPinf[(d * J + r) * J + c];
+    }
+    out[b] = x;
+  }
+}
+
+// the derivative along one direction from its two sums; one function, so that single and batched calls round alike
+__attribute__((noinline)) double grad_value(const double* sums) { return -0.5 * sums[0] - sums[1]; }
+
+// One direction pass for `members` models x nd directions (grid z x y), after their factors and forward solves: the
+// factor's tangent (qs_gfac_fold, the congruence scan, qs_gfac_emit), the solve's (qs_gsol, the affine scan, qs_gsol)
+// and one qs_finish block per (member, direction), which leaves (sum dc / c, sum z dz) at res[2 (member nd + direction)].
+// dirs: members x nd; keep: per member the chunks' incoming filtered covariances, then solve states (nchunks x WAVE
+// each); tan: dc | dw (members nd n (1 + J)); red: the per-chunk sums (2 members nd nchunks).  Member b: its noise,
+// residual, keep and work space one stride after member b - 1's, its c and w as in qs_emit.
+int launch_tangents(tgp_qsep* q, const QModel* models, int64_t members, const QDir* dirs, int64_t nd,
+                    const double* noise, int64_t noise_stride, const double* cbuf, const double* wbuf,
+                    const double* resid, int64_t resid_stride, const double* keep, int64_t keep_stride, double* work,
+                    int64_t work_stride, double* tan, double* red, double* res) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks, md = members * nd;
+  const dim3 grid(unsigned(blocks_for(nc)), unsigned(nd), unsigned(members));
+  const double *prefixP = keep, *prefixS = keep + nc * WAVE;
+  double *dcb = tan, *dwb = tan + md * n, *dsum = red, *dsum2 = red + md * nc;
+  double* prefix = nullptr;
+  qs_gfac_fold<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, noise, noise_stride, n, q->lc, nc, prefixP,
+                                            keep_stride, work, work_stride);
+  TGP_TRY(run_scan<ScanCong>(models, st, nc, nd, work, &prefix, members, work_stride));
+  qs_gfac_emit<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, noise, noise_stride, n, q->lc, nc, prefixP,
+                                            keep_stride, prefix, work_stride, dcb, dwb, dsum);
+  qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, cbuf, wbuf, dcb, dwb, resid, resid_stride, n, q->lc, nc,
+                                       prefixS, keep_stride, nullptr, work, work_stride, nullptr);
+  TGP_TRY(run_scan<ScanAffine>(models, st, nc, nd, work, &prefix, members, work_stride));
+  qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, cbuf, wbuf, dcb, dwb, resid, resid_stride, n, q->lc, nc,
+                                       prefixS, keep_stride, prefix, nullptr, work_stride, dsum2);
+  // block b: (member, direction) b's two sums (dsum2 lies md nc doubles after dsum, like its rows)
+  qs_finish<<<unsigned(md), WAVE, 0, st>>>(dsum, nc, dsum2, nc, nullptr, res, nullptr, nc, 0, 2);
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
+// The noise gradient 1/2 (alpha^2 - diag K^-1) of `members` models (grid y) from their factors and alpha: the variance
+// half of qs_pred_fold from the end, the prediction's scan, qs_invdiag_emit.  c, alpha and out n, w n J doubles per
+// member, the work space work_stride.
+int launch_invdiag(tgp_qsep* q, const QModel* models, int64_t members, const double* cbuf, const double* wbuf,
+                   const double* alpha, double* work, int64_t work_stride, double* out) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks;
+  const dim3 grid(unsigned(blocks_for(nc)), unsigned(members));
+  qs_pred_fold<<<grid, WAVE * WPB, 0, st>>>(1, 0, 1, models, q->t, cbuf, wbuf, nullptr, n, q->lc, nc, work,
+                                            work_stride);
+  double* prefix = nullptr;
+  TGP_TRY(run_scan<ScanPred>(models, st, nc, 1, work, &prefix, members, work_stride));
+  qs_invdiag_emit<<<grid, WAVE * WPB, 0, st>>>(models, q->t, cbuf, wbuf, alpha, n, q->lc, nc, prefix, work_stride, out);
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
 
 // After factor() and the forward solve of the residual (q->io: r, q->io2: z; gkeep: both scans' chunk prefixes):
 // the derivative of the log-likelihood along each of ndir directions, -1/2 sum dc/c - sum z dz.
@@ -1367,49 +1466,24 @@ int grad_directions(tgp_qsep* q, int32_t ndir, const double* dleaves, const doub
                 (long long)GRAD_SCRATCH_BYTES);
   const int64_t batch =
       std::min<int64_t>({int64_t(ndir), GRAD_MAX_BATCH, GRAD_SCRATCH_BYTES / (per_dir * int64_t(sizeof(double)))});
-  constexpr int64_t DIR_DOUBLES = sizeof(QDir) / sizeof(double);
   TGP_TRY(grow(&q->gdir, &q->gdir_elems, batch * DIR_DOUBLES));
   TGP_TRY(grow(&q->gtan, &q->gtan_elems, batch * per_dir));
   TGP_TRY(grow(&q->gred, &q->gred_elems, batch * (2 * nc + 2)));
   TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanCong>(nc, batch)));
-  const double *prefixP = q->gkeep, *prefixS = q->gkeep + nc * WAVE;
   const QDir* dirs = reinterpret_cast<const QDir*>(q->gdir);
   std::vector<QDir> hd(size_t(batch), QDir{});
   std::vector<double> sums(size_t(2 * batch));
   for (int64_t d0 = 0; d0 < ndir; d0 += batch) {
     const int64_t nb = std::min<int64_t>(batch, ndir - d0);
-    for (int64_t b = 0; b < nb; ++b) {
-      QDir x{};
-      const int64_t d = d0 + b;
-      for (int64_t l = 0; l < nl; ++l)
-        for (int p = 0; p < 4; ++p) x.dpar[l][p] = dleaves[(d * nl + l) * 4 + p];
-      for (int64_t r = 0; r < J; ++r) {
-        x.dh[r] = dh[d * J + r];
-        for (int64_t c = 0; c < J; ++c) x.dP[r * QJ + c] = dPinf[(d * J + r) * J + c];
-      }
-      hd[size_t(b)] = x;
-    }
+    pack_dirs(hd.data(), d0, nb, nl, J, dleaves, dh, dPinf);
     TGP_HIP_TRY(hipMemcpyAsync(q->gdir, hd.data(), size_t(nb) * sizeof(QDir), hipMemcpyHostToDevice, st));
-    const dim3 grid(unsigned(blocks_for(nc)), unsigned(nb));
-    double *dcb = q->gtan, *dwb = q->gtan + nb * n, *dsum = q->gred, *dsum2 = q->gred + nb * nc;
     double* res = q->gred + 2 * nb * nc;
-    double* prefix = nullptr;
-    qs_gfac_fold<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->noise, n, q->lc, nc, prefixP, q->work);
-    TGP_TRY(run_scan<ScanCong>(q->model, st, nc, nb, q->work, &prefix));
-    qs_gfac_emit<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->noise, n, q->lc, nc, prefixP, prefix, dcb, dwb,
-                                              dsum);
-    qs_gsol<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->c, q->w, dcb, dwb, q->io, n, q->lc, nc, prefixS,
-                                         nullptr, q->work, nullptr);
-    TGP_TRY(run_scan<ScanAffine>(q->model, st, nc, nb, q->work, &prefix));
-    qs_gsol<<<grid, WAVE * WPB, 0, st>>>(q->model, dirs, q->t, q->c, q->w, dcb, dwb, q->io, n, q->lc, nc, prefixS,
-                                         prefix, nullptr, dsum2);
-    // block b: direction b's two sums (dsum2 lies nb nc doubles after dsum, like its rows)
-    qs_finish<<<unsigned(nb), WAVE, 0, st>>>(dsum, nc, dsum2, nc, nullptr, res, nullptr, nc, 0, 2);
-    TGP_HIP_TRY(hipGetLastError());
+    TGP_TRY(launch_tangents(q, q->model, 1, dirs, nb, q->noise, 0, q->c, q->w, q->io, 0, q->gkeep, 0, q->work, 0,
+                            q->gtan, q->gred, res));
     // the host vectors are reused by the next batch: wait for this one
     TGP_HIP_TRY(hipMemcpyAsync(sums.data(), res, size_t(2 * nb) * sizeof(double), hipMemcpyDeviceToHost, st));
     TGP_HIP_TRY(hipStreamSynchronize(st));
-    for (int64_t b = 0; b < nb; ++b) dout[d0 + b] = -0.5 * sums[size_t(2 * b)] - sums[size_t(2 * b + 1)];
+    for (int64_t b = 0; b < nb; ++b) dout[d0 + b] = grad_value(&sums[size_t(2 * b)]);
   }
   return TGP_OK;
 }
@@ -1424,13 +1498,7 @@ int grad_vectors(tgp_qsep* q, double* gnoise_host, double* alpha_host) {
   if (gnoise_host) {
     TGP_TRY(grow(&q->gout, &q->gout_elems, n));
     TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanPred>(nc, 1)));
-    qs_pred_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(1, 0, 1, q->model, q->t, q->c, q->w, nullptr, n, q->lc, nc,
-                                                        q->work);
-    double* prefix = nullptr;
-    TGP_TRY(run_scan<ScanPred>(q->model, st, nc, 1, q->work, &prefix));
-    qs_invdiag_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(q->model, q->t, q->c, q->w, q->io, n, q->lc, nc, prefix,
-                                                           q->gout);
-    TGP_HIP_TRY(hipGetLastError());
+    TGP_TRY(launch_invdiag(q, q->model, 1, q->c, q->w, q->io, q->work, 0, q->gout));
     TGP_HIP_TRY(hipMemcpyAsync(gnoise_host, q->gout, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   TGP_HIP_TRY(hipStreamSynchronize(st));
@@ -1510,6 +1578,148 @@ int batch_chain(tgp_qsep* q, const BatchLayout& lay, int64_t cap, int64_t nb, co
     memcpy(&first_bad, &got[size_t(3 * b + 2)], sizeof(first_bad));
     info[b] = first_bad == INT64_MAX ? 0 : int32_t(first_bad + 1);
     out[b] = info[b] ? NAN : logprob_value(got[size_t(3 * b + 1)], got[size_t(3 * b)], n);
+  }
+  return TGP_OK;
+}
+
+// ---- batches of gradients ---------------------------------------------------------------------------------------------
+// Value and gradient of up to BATCH_MAX_MEMBERS models in one launch chain, in the same batch buffer under the same
+// cap.  With P directions per member, D of them per pass, S the sum of the scan's level sizes, in doubles:
+//   fixed                 BATCH_MAX_MEMBERS models | BATCH_MAX_MEMBERS x GRAD_MAX_BATCH directions (one pass's) |
+//                         the noise, if shared (n) | the residual, if shared (n)
+//   per member            noise, if its own (n) | residual, if its own (n) | c (n) | w (n J) | z (n) | both primal scans'
+//                         chunk prefixes (2 x 64 nchunks) | scan work space (256 S; 384 S with the vectors: the
+//                         prediction scan's) | per-chunk sums of log c and z^2 (2 nchunks) | bad-pivot slots (nchunks) |
+//                         results (3 + 2 P) | with the vectors: alpha (n) | noise gradient (n)
+//   per member and direction of a pass
+//                         dc, dw (n (1 + J)) | scan work space (192 S) | per-chunk sums (2 nchunks)
+// The split (grad_split): as many members as fit with one direction each, then as many directions per pass as the rest
+// holds.  A function of (n, J, P, B, own or shared noise and residual, vectors or not) alone.
+struct GradLayout {
+  int64_t fixed, per_member, per_dir, work, twork;  // doubles; twork: the tangent scans' work space per direction
+  int64_t members, dirs;                            // per chain, per pass; members == 0: one member does not fit
+};
+
+GradLayout grad_split(int64_t n, int64_t nc, int64_t J, int64_t P, int64_t B, bool own_noise, bool own_resid,
+                      bool vectors) {
+  GradLayout l;
+  // the larger need of the scans that share it, as in batch_layout; the prediction scan joins them with the vectors
+  l.work = std::max(scan_work<ScanRiccati>(nc, 1), scan_work<ScanAffine>(nc, 1));
+  if (vectors) l.work = std::max(l.work, scan_work<ScanPred>(nc, 1));
+  l.twork = scan_work<ScanCong>(nc, 1);
+  l.fixed = BATCH_MAX_MEMBERS * (MODEL_DOUBLES + GRAD_MAX_BATCH * DIR_DOUBLES) + (own_noise ? 0 : n) + (own_resid ? 0 : n);
+  l.per_member = (own_noise ? n : 0) + (own_resid ? n : 0) + n * (2 + J) + 2 * nc * WAVE + l.work + 3 * nc + 3 + 2 * P +
+                 (vectors ? 2 * n : 0);
+  l.per_dir = n * (1 + J) + l.twork + 2 * nc;
+  const int64_t budget = BATCH_SCRATCH_BYTES / int64_t(sizeof(double)) - l.fixed;
+  const int64_t one = l.per_member + (P > 0 ? l.per_dir : 0);
+  l.members = budget < one ? 0 : std::min<int64_t>({B, BATCH_MAX_MEMBERS, budget / one});
+  l.dirs = 0;
+  if (l.members > 0 && P > 0)
+    l.dirs = std::min<int64_t>({P, GRAD_MAX_BATCH, (budget - l.members * l.per_member) / (l.members * l.per_dir)});
+  return l;
+}
+
+struct GradBatchArgs {
+  int64_t nl, J, ndir;
+  const double *noise, *resid;  // host; this chain's first member's when per member
+  int64_t noise_stride, resid_stride;
+  const double *dleaves, *dh, *dPinf;  // host, this chain's first member's
+  int32_t* info;
+  double *out, *dout, *gnoise, *alpha;  // host, this chain's first member's; the last two may be null
+};
+
+// one launch chain: members [0, nb) of the arrays given; shared noise / residual are on the device already.  One stream
+// synchronisation, at the end.
+int grad_batch_chain(tgp_qsep* q, const GradLayout& lay, int64_t nb, const QModel* models_host, const GradBatchArgs& a,
+                     int32_t* passes) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks, J = a.J, P = a.ndir, cap = lay.members, D = lay.dirs;
+  const int64_t W = lay.work, TW = D * lay.twork, KS = 2 * nc * WAVE;
+  const bool vectors = a.gnoise || a.alpha;
+  // the buffer is carved for `cap` members and D directions, whatever this chain holds
+  QModel* models = reinterpret_cast<QModel*>(q->bat);
+  double* p = q->bat + BATCH_MAX_MEMBERS * MODEL_DOUBLES;
+  QDir* dirs = reinterpret_cast<QDir*>(p);
+  p += BATCH_MAX_MEMBERS * GRAD_MAX_BATCH * DIR_DOUBLES;
+  auto take = [&](int64_t shared, int64_t stride) {
+    double* r = p;
+    p += stride ? cap * stride : shared;
+    return r;
+  };
+  double* noise = take(n, a.noise_stride);
+  double* resid = take(n, a.resid_stride);
+  double* cbuf = take(0, n);
+  double* wbuf = take(0, n * J);
+  double* z = take(0, n);
+  double* keep = take(0, KS);
+  double* work = take(0, W);
+  double* red = take(0, 2 * nc);
+  int64_t* bad = reinterpret_cast<int64_t*>(take(0, nc));
+  double* res = take(0, 3);
+  double* dres = take(0, 2 * P);
+  double* alpha = take(0, vectors ? n : 0);
+  double* gnoise = take(0, vectors ? n : 0);
+  double* tan = take(0, D * n * (1 + J));
+  double* twork = take(0, TW);
+  double* tred = take(0, D * 2 * nc);
+  TGP_HIP_TRY(hipMemcpyAsync(models, models_host, size_t(nb) * sizeof(QModel), hipMemcpyHostToDevice, st));
+  if (a.noise_stride)
+    TGP_HIP_TRY(hipMemcpyAsync(noise, a.noise, size_t(nb * n) * sizeof(double), hipMemcpyHostToDevice, st));
+  if (a.resid_stride)
+    TGP_HIP_TRY(hipMemcpyAsync(resid, a.resid, size_t(nb * n) * sizeof(double), hipMemcpyHostToDevice, st));
+  // the primal part, each scan's chunk prefixes set aside
+  const dim3 kgrid(unsigned(ceil_div(nc * WAVE, 256)), unsigned(nb));
+  double* prefix = nullptr;
+  TGP_TRY(launch_factor(q, models, nb, noise, a.noise_stride, work, W, cbuf, wbuf, red, 2 * nc, bad, &prefix));
+  qs_keep_rows<<<kgrid, 256, 0, st>>>(prefix, W, keep, KS, nc * WAVE);
+  TGP_TRY(launch_affine(q, TGP_QS_FWD, models, nb, cbuf, wbuf, 1, resid, a.resid_stride, work, W, z, red + nc, 2 * nc,
+                        &prefix));
+  qs_keep_rows<<<kgrid, 256, 0, st>>>(prefix, W, keep + nc * WAVE, KS, nc * WAVE);
+  // per member: (sum log c, sum z^2, first bad pivot), the third an int64 in a double's slot
+  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(red, nc, red + nc, nc, bad, res, reinterpret_cast<int64_t*>(res) + 2,
+                                           2 * nc, nc, 3);
+  TGP_HIP_TRY(hipGetLastError());
+  // direction passes: pass k's host directions (member-major) stay alive until the synchronisation below, its results
+  // land after those of the passes before it (2 nb d0 doubles)
+  std::vector<QDir> hd(size_t(nb * P));
+  for (int64_t d0 = 0; d0 < P; d0 += D, ++*passes) {
+    const int64_t nd = std::min<int64_t>(D, P - d0);
+    QDir* h = hd.data() + nb * d0;
+    for (int64_t b = 0; b < nb; ++b)
+      pack_dirs(h + b * nd, d0, nd, a.nl, J, a.dleaves + b * P * a.nl * 4, a.dh + b * P * J, a.dPinf + b * P * J * J);
+    TGP_HIP_TRY(hipMemcpyAsync(dirs, h, size_t(nb * nd) * sizeof(QDir), hipMemcpyHostToDevice, st));
+    TGP_TRY(launch_tangents(q, models, nb, dirs, nd, noise, a.noise_stride, cbuf, wbuf, resid, a.resid_stride, keep, KS,
+                            twork, TW, tan, tred, dres + 2 * nb * d0));
+  }
+  if (vectors) {
+    TGP_TRY(launch_affine(q, TGP_QS_BWD, models, nb, cbuf, wbuf, 1, z, n, work, W, alpha, nullptr, 0, &prefix));
+    if (a.alpha)
+      TGP_HIP_TRY(hipMemcpyAsync(a.alpha, alpha, size_t(nb * n) * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (a.gnoise) {
+      TGP_TRY(launch_invdiag(q, models, nb, cbuf, wbuf, alpha, work, W, gnoise));
+      TGP_HIP_TRY(hipMemcpyAsync(a.gnoise, gnoise, size_t(nb * n) * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+  }
+  std::vector<double> got(size_t(3 * nb)), dgot(size_t(2 * nb * P));
+  TGP_HIP_TRY(hipMemcpyAsync(got.data(), res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (P > 0) TGP_HIP_TRY(hipMemcpyAsync(dgot.data(), dres, dgot.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t b = 0; b < nb; ++b) {
+    int64_t first_bad;
+    memcpy(&first_bad, &got[size_t(3 * b + 2)], sizeof(first_bad));
+    a.info[b] = first_bad == INT64_MAX ? 0 : int32_t(first_bad + 1);
+    const bool failed = a.info[b] != 0;  // c and w are not a factor of anything: what ran on them is overwritten
+    a.out[b] = failed ? NAN : logprob_value(got[size_t(3 * b + 1)], got[size_t(3 * b)], n);
+    for (int64_t d0 = 0; d0 < P; d0 += D) {
+      const int64_t nd = std::min<int64_t>(D, P - d0);
+      for (int64_t d = 0; d < nd; ++d)
+        a.dout[b * P + d0 + d] = failed ? NAN : grad_value(&dgot[size_t(2 * (nb * d0 + b * nd + d))]);
+    }
+    for (int64_t i = 0; failed && i < n; ++i) {
+      if (a.gnoise) a.gnoise[b * n + i] = NAN;
+      if (a.alpha) a.alpha[b * n + i] = NAN;
+    }
   }
   return TGP_OK;
 }
@@ -1696,6 +1906,69 @@ int tgp_qsep_logprob_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_
                         resid_host + b0 * resid_stride, resid_stride, info + b0, out + b0));
   }
   if (nchains) *nchains = chains;
+  return TGP_OK;
+}
+
+int tgp_qsep_grad_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                        int32_t J, const double* hvec, const double* Pinf, const double* noise_host,
+                        int64_t noise_stride, const double* resid_host, int64_t resid_stride, int32_t ndir,
+                        const double* dleaves, const double* dh, const double* dPinf, int32_t* info, double* out,
+                        double* dout, double* gnoise_host, double* alpha_host, int32_t* nchains, int32_t* npasses) {
+  QS_GUARD(q);
+  TGP_ARG_CHECK(nb >= 0, "negative number of models (%d)", nb);
+  TGP_ARG_CHECK(ndir >= 0, "negative number of directions (%d)", ndir);
+  if (nchains) *nchains = 0;
+  if (npasses) *npasses = 0;
+  if (nb == 0) return TGP_OK;
+  const int64_t n = q->n, nc = q->nchunks;
+  TGP_ARG_CHECK(leaves && state_map && hvec && Pinf, "null model array");
+  TGP_ARG_CHECK(noise_host && resid_host && info && out, "null argument");
+  TGP_ARG_CHECK(ndir == 0 || (dleaves && dh && dPinf && dout), "null direction array");
+  TGP_ARG_CHECK(noise_stride == 0 || noise_stride == n, "the noise stride must be 0 (shared) or n (got %lld)",
+                (long long)noise_stride);
+  TGP_ARG_CHECK(resid_stride == 0 || resid_stride == n, "the residual stride must be 0 (shared) or n (got %lld)",
+                (long long)resid_stride);
+  std::vector<QModel> models(size_t(nb), QModel{});
+  for (int64_t b = 0; b < nb; ++b)
+    TGP_TRY(pack_model(&models[size_t(b)], leaves + b * nleaves * 5, nleaves, state_map, J, hvec + b * J,
+                       Pinf + b * J * J));
+  const bool vectors = gnoise_host || alpha_host;
+  const GradLayout lay = grad_split(n, nc, J, ndir, nb, noise_stride != 0, resid_stride != 0, vectors);
+  TGP_ARG_CHECK(lay.members > 0,
+                "the gradient batch's scratch for one model and one direction (%lld + %lld doubles, %lld shared) "
+                "exceeds its cap of %lld bytes",
+                (long long)lay.per_member, (long long)lay.per_dir, (long long)lay.fixed,
+                (long long)BATCH_SCRATCH_BYTES);
+  const int64_t cap = lay.members;
+  TGP_TRY(grow(&q->bat, &q->bat_elems, lay.fixed + cap * (lay.per_member + lay.dirs * lay.per_dir)));
+  hipStream_t st = q->ctx->stream;
+  double* shared = q->bat + BATCH_MAX_MEMBERS * (MODEL_DOUBLES + GRAD_MAX_BATCH * DIR_DOUBLES);
+  if (!noise_stride) {
+    TGP_HIP_TRY(hipMemcpyAsync(shared, noise_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+    shared += n;
+  } else {
+    shared += cap * n;
+  }
+  if (!resid_stride)
+    TGP_HIP_TRY(hipMemcpyAsync(shared, resid_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+  int32_t chains = 0, passes = 0;
+  const int64_t P = ndir;
+  for (int64_t b0 = 0; b0 < nb; b0 += cap, ++chains) {
+    const int64_t cnt = std::min<int64_t>(cap, nb - b0);
+    GradBatchArgs a;
+    a.nl = nleaves, a.J = J, a.ndir = P;
+    a.noise = noise_host + b0 * noise_stride, a.noise_stride = noise_stride;
+    a.resid = resid_host + b0 * resid_stride, a.resid_stride = resid_stride;
+    a.dleaves = P ? dleaves + b0 * P * nleaves * 4 : nullptr;
+    a.dh = P ? dh + b0 * P * J : nullptr;
+    a.dPinf = P ? dPinf + b0 * P * J * J : nullptr;
+    a.info = info + b0, a.out = out + b0, a.dout = P ? dout + b0 * P : nullptr;
+    a.gnoise = gnoise_host ? gnoise_host + b0 * n : nullptr;
+    a.alpha = alpha_host ? alpha_host + b0 * n : nullptr;
+    TGP_TRY(grad_batch_chain(q, lay, cnt, models.data() + b0, a, &passes));
+  }
+  if (nchains) *nchains = chains;
+  if (npasses) *npasses = passes;
   return TGP_OK;
 }
 

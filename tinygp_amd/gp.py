@@ -163,7 +163,25 @@ class GaussianProcess:
                                       "are evaluated by QuasisepSolver (a kernels.quasisep kernel on sorted 1-D "
                                       "inputs)")
         kernels = list(kernels)
-        nb, n = len(kernels), self.num_data
+        return fused(kernels, *self._batch_inputs(y, len(kernels), diags, means))
+
+    def log_probability_and_grad_batch(self, y, kernels, *, diags=None, means=None):
+        """:meth:`log_probability_and_grad` of ``y`` under B models that share this GP's coordinates, evaluated
+        together: ``(values (B,), grads)`` with ``grads = {"kernel": (B, P), "noise_diag": (B, N), "mean": (B, N),
+        "transform": None}``.  Arguments as in :meth:`log_probability_batch`; row b equals
+        ``GaussianProcess(kernels[b], X, diag=diags[b], mean=means[b]).log_probability_and_grad(y)`` to the bit.
+        Needs a solver with ``value_and_grad_batch`` (:class:`tinygp_amd.solvers.QuasisepSolver`)."""
+        fused = getattr(self.solver, "value_and_grad_batch", None)
+        if fused is None:
+            raise NotImplementedError(f"{type(self.solver).__name__} has no value_and_grad_batch: batches of gradients "
+                                      "are evaluated by QuasisepSolver (a kernels.quasisep kernel on sorted 1-D "
+                                      "inputs)")
+        kernels = list(kernels)
+        return fused(kernels, *self._batch_inputs(y, len(kernels), diags, means))
+
+    def _batch_inputs(self, y, nb, diags, means):
+        """``(resid, noise)`` of a batch of nb models: the arguments of the solver's batch methods."""
+        n = self.num_data
 
         def per_member(a, what):  # (B,) -> (B, N) of this GP's dtype, (B, N) kept
             a = np.asarray(a)
@@ -179,7 +197,7 @@ class GaussianProcess:
             if resid.shape != (nb, n):
                 raise ValueError(f"y must broadcast against the means of shape ({nb}, {n})")
         noise = None if diags is None else per_member(diags, "diags")
-        return fused(kernels, resid, noise)
+        return resid, noise
 
     def log_probability_and_grad(self, y):
         """``(log_probability, grads)``; see :meth:`solvers.DirectSolver.log_probability_and_grad`.

@@ -33,7 +33,8 @@ from tinygp_amd.kernels import base
 from tinygp_amd.kernels.distance import L1Distance
 
 __all__ = ["Quasisep", "Sum", "Product", "Scale", "Celerite", "SHO", "Exp", "Matern32", "Matern52", "Cosine",
-           "MAX_STATE", "MAX_LEAVES", "SSMTangent", "leaf_phi", "leaf_dphi", "model_dphi", "pack_batch"]
+           "MAX_STATE", "MAX_LEAVES", "SSMTangent", "leaf_phi", "leaf_dphi", "model_dphi", "pack_batch",
+           "pack_batch_tangents"]
 
 MAX_STATE = 8   # TGP_QSEP_MAX_J of include/tgp_hip.h
 MAX_LEAVES = 8  # TGP_QSEP_MAX_LEAVES
@@ -103,6 +104,36 @@ def pack_batch(kernels):
     stack = lambda field: np.ascontiguousarray(  # noqa: E731
         np.stack([np.asarray(getattr(s, field), dtype=np.float64) for s in ssms]))
     return stack("leaves"), smap, stack("h"), stack("Pinf")
+
+
+def pack_batch_tangents(kernels):
+    """The parameter tangents of B kernels for ``tgp_qsep_grad_batch``: ``(dleaves (B, P, L, 4), dh (B, P, J), dPinf
+    (B, P, J, J), undefined (B, P) bool)`` from each member's ``_ssm_tangents()``, float64 and contiguous.  A tangent
+    with a non-finite entry (the quality of a critically damped ``SHO``) is zeroed and flagged in ``undefined``, as
+    ``QuasisepSolver.value_and_grad`` does for one model.  Every member must have the first one's number of parameters;
+    a mismatch raises ``ValueError`` naming the member.  The structure itself is checked by :func:`pack_batch`."""
+    kernels = list(kernels)
+    if not kernels:
+        raise ValueError("pack_batch_tangents needs at least one kernel")
+    for i, k in enumerate(kernels):
+        if not isinstance(k, Quasisep):
+            raise TypeError(f"kernel {i} of the batch is no kernels.quasisep.Quasisep kernel ({type(k).__name__})")
+    tangents = [k._ssm_tangents() for k in kernels]
+    nb, npar = len(kernels), len(tangents[0])
+    for i, ts in enumerate(tangents):
+        if len(ts) != npar:
+            raise ValueError(f"kernel {i} of the batch has {len(ts)} parameters, kernel 0 has {npar}")
+    ssm = kernels[0]._lower_ssm()
+    L, J = len(ssm.leaves), ssm.J
+    dleaves, dh, dP = np.zeros((nb, npar, L, 4)), np.zeros((nb, npar, J)), np.zeros((nb, npar, J, J))
+    undefined = np.zeros((nb, npar), dtype=bool)
+    for b, ts in enumerate(tangents):
+        for i, t in enumerate(ts):
+            if np.all(np.isfinite(t.dleaves)) and np.all(np.isfinite(t.dh)) and np.all(np.isfinite(t.dPinf)):
+                dleaves[b, i], dh[b, i], dP[b, i] = t.dleaves, t.dh, t.dPinf
+            else:
+                undefined[b, i] = True
+    return dleaves, dh, dP, undefined
 
 
 class Quasisep(base.Kernel):

@@ -7,7 +7,8 @@ factorisation, both triangular solves and ``L @ z`` are chunked reduce-then-scan
 ``csrc/qsep.hip``, and so are the conditional mean and variance at M test points (``predict_mean_var``; O(N + M),
 nothing of size N x M), the same for every term of a sum at once (``predict_terms``; also at the data themselves),
 the gradient of the log-probability (``value_and_grad``; O(N) per parameter) and the log-probabilities of many
-hyper-parameter sets over the one series in one launch chain (``log_probability_batch``).  Nothing
+hyper-parameter sets over the one series in one launch chain (``log_probability_batch``; with their gradients:
+``value_and_grad_batch``).  Nothing
 of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
 reference); the full conditional covariance and conditioning on another kernel keep the reference's dense route.
 
@@ -350,6 +351,64 @@ class QuasisepSolver(Solver):
         return self.dtype.type(v), {"kernel": [float(g) for g in kgrad],
                                     "noise_diag": gnoise.astype(self.dtype, copy=False),
                                     "mean": alpha.astype(self.dtype, copy=False), "transform": None}
+
+    def value_and_grad_batch(self, kernels, resid, noise=None, *, vectors: bool = True, return_info: bool = False):
+        """:meth:`value_and_grad` of B models over this solver's coordinates, evaluated together on the device
+        (``tgp_qsep_grad_batch``: one model per grid layer of the gradient's kernels): the starts of an optimiser, a
+        population of HMC chains, many stars observed at one cadence (one residual per member).
+
+        ``kernels``, ``resid`` and ``noise`` as in :meth:`log_probability_batch`; every member must have the same
+        number of parameters (:func:`tinygp_amd.kernels.quasisep.pack_batch_tangents`).  Returns ``(values (B,),
+        grads)`` with ``grads = {"kernel": (B, P), "noise_diag": (B, N), "mean": (B, N), "transform": None}``; row b
+        has the bits of :meth:`value_and_grad` of a solver built with that member's kernel and noise.  With
+        ``vectors=False`` the two (B, N) entries are ``None`` and their scans are skipped.  A failed or non-finite
+        member gives ``-inf`` and NaN gradients, an undefined derivative (the quality of a critically damped ``SHO``)
+        NaN.  With ``return_info`` also the B ``info`` values.  fp32 inputs are computed in fp64 and returned as fp32
+        (the ``"kernel"`` rows stay float64, as the floats of :meth:`value_and_grad` do).  The solver's own kernel and
+        factor are neither used nor changed."""
+        from tinygp_amd.kernels.quasisep import pack_batch, pack_batch_tangents
+
+        kernels = list(kernels)
+        nb = len(kernels)
+        if nb == 0:
+            npar = len(self.kernel.parameters())
+            vec = (lambda: np.empty((0, self.n), dtype=self.dtype)) if vectors else (lambda: None)
+            out = np.empty(0, dtype=self.dtype), {"kernel": np.empty((0, npar)),
+                                                  "noise_diag": vec(), "mean": vec(), "transform": None}
+            return out + (np.empty(0, dtype=np.int32),) if return_info else out
+        leaves, smap, h, P = pack_batch(kernels)
+        dleaves, dh, dP, undefined = pack_batch_tangents(kernels)
+        ndir = dh.shape[1]
+
+        def rows(a, what):  # (N,) -> shared, (B, N) -> one per member
+            a = np.asarray(a)
+            if a.shape == (self.n,):
+                return _f64(a), 0
+            if a.shape == (nb, self.n):
+                return _f64(a), self.n
+            raise ValueError(f"{what} must have shape ({self.n},) or ({nb}, {self.n}); got {a.shape}")
+
+        r, r_stride = rows(resid, "resid")
+        d, d_stride = (self._noise, 0) if noise is None else rows(noise, "noise")
+        info, out, kgrad = np.zeros(nb, dtype=np.int32), np.empty(nb), np.zeros((nb, ndir))
+        gnoise, alpha = (np.empty((nb, self.n)), np.empty((nb, self.n))) if vectors else (None, None)
+        _ffi.check(_ffi.lib().tgp_qsep_grad_batch(self._handle, nb, _ffi.ptr(leaves), leaves.shape[1], _ffi.ptr(smap),
+                                                  h.shape[1], _ffi.ptr(h), _ffi.ptr(P), _ffi.ptr(d), d_stride,
+                                                  _ffi.ptr(r), r_stride, ndir, _ffi.ptr(dleaves), _ffi.ptr(dh),
+                                                  _ffi.ptr(dP), _ffi.ptr(info), _ffi.ptr(out), _ffi.ptr(kgrad),
+                                                  _ffi.ptr(gnoise), _ffi.ptr(alpha), None, None),
+                   "tgp_qsep_grad_batch")
+        kgrad[undefined] = np.nan
+        failed = (info != 0) | ~np.isfinite(out)
+        out[failed] = -np.inf
+        kgrad[failed] = np.nan
+        if vectors:
+            gnoise[failed] = np.nan
+            alpha[failed] = np.nan
+        cast = lambda a: None if a is None else a.astype(self.dtype, copy=False)  # noqa: E731
+        result = cast(out), {"kernel": kgrad, "noise_diag": cast(gnoise), "mean": cast(alpha),
+                             "transform": None}
+        return result + (info,) if return_info else result
 
     def _grad_call(self, resid, dleaves, dh, dP, vectors: bool = True):
         """One ``tgp_qsep_grad``: the value, the derivatives along the given directions (``dleaves`` (P, L, 4), ``dh``
