@@ -669,6 +669,28 @@ int tgp_qsep_grad_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_t n
                         int64_t noise_stride, const double* resid_host, int64_t resid_stride, int32_t ndir,
                         const double* dleaves, const double* dh, const double* dPinf, int32_t* info, double* out,
                         double* dout, double* gnoise_host, double* alpha_host, int32_t* nchains, int32_t* npasses);
+/* A set of nseries series, each on sorted coordinates of its own: series b is [offsets[b], offsets[b + 1]) of t_concat
+ * (offsets: nseries + 1 values from 0, strictly increasing -- every series holds at least one point).  The handle keeps
+ * the concatenated t and a table of every series' extent (its slice, length, chunk length, chunk count and scan levels;
+ * the chunk length is tgp_qsep_create's function of the series' own length) resident on the device. */
+typedef struct tgp_qsep_series tgp_qsep_series;
+int tgp_qsep_series_create(tgp_ctx* ctx, int32_t nseries, const int64_t* offsets, const double* t_concat,
+                           tgp_qsep_series** out);
+int tgp_qsep_series_destroy(tgp_qsep_series* set);
+/* The log-probability (as tgp_qsep_factor_logprob) of every series of the set under a model of its own, evaluated
+ * together: one series per grid row of every kernel.  The models are stacked per member exactly as
+ * tgp_qsep_logprob_batch takes them; noise_concat and resid_concat are laid out as t_concat.  info (nseries), out
+ * (nseries): per series; a non-positive pivot sets that series' info to its 1-based step within the series and its out
+ * to NaN and touches no other series.  A series' result has the bits of tgp_qsep_factor_logprob on a handle created on
+ * that series alone, whatever nseries, its position, the other series' lengths and the split.  A launch chain (one
+ * upload each of the models, the noise and the residual, one download, one stream synchronisation) holds at most 64
+ * series and at most 1 GiB of device scratch, the sum of what its own members need; chains are filled in the order
+ * given ("Batches of series", states the layout and the rule), and *nchains (may be NULL) reports how
+ * many ran.  The table is re-cut and uploaded when J differs from the previous call's.  A series that exceeds the cap
+ * alone is an argument error, raised before anything is allocated. */
+int tgp_qsep_series_logprob(tgp_qsep_series* set, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                            int32_t J, const double* hvec, const double* Pinf, const double* noise_concat,
+                            const double* resid_concat, int32_t* info, double* out, int32_t* nchains);
 
 #ifdef __cplusplus
 }

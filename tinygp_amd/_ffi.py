@@ -167,6 +167,9 @@ SIGNATURES = {
     "tgp_qsep_logprob_batch": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _pi32],
     "tgp_qsep_grad_batch": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp, _pi32, _pi32],
+    "tgp_qsep_series_create": [_vp, _i32, _vp, _vp, _pvp],
+    "tgp_qsep_series_destroy": [_vp],
+    "tgp_qsep_series_logprob": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _pi32],
 }
 
 

@@ -30,6 +30,8 @@
 // every array of that member `stride` doubles after its neighbour's.  A single evaluation is the batch of one (grid
 // y = 1, where no stride matters): launch_factor and launch_affine enqueue the chain for both, so a member's result
 // has the bits of its single call.  The gradient's kernels take the same member axis (see "gradient" below).
+// Sets of series: the same kernels, instantiated over an extent policy ("extents" below), serve members that each have
+// a series of their own -- their own slice of t, length, chunk length, chunk count and scan depth -- from a device table.
 #include "tgp_common.h"
 
 #include <algorithm>
@@ -282,16 +284,63 @@ struct Lane {
   }
 };
 
+// ---- extents: what a kernel of the fused log-probability knows of the member it serves ------------------------------
+// The kernels are instantiated over a policy that resolves member blockIdx.y to a Member: the steps it covers and where
+// its arrays start, as offsets from the pointers the kernel was given.
+//   UniformExtent   every member covers the same n steps in chunks of lc; its arrays lie a stride after its neighbour's
+//                   (batches of models over one series, and the single call: the batch of one)
+//   TableExtent     every member has an extent of its own, one QExtent of a device table (sets of series): its slice of
+//                   the concatenated t, noise, residual, c, w and z, its own n, lc, chunk count and scan levels.  Inside a
+//                   member every index is local, so step 0 is the one that absorbs the stationary prior.  The grid is
+//                   sized for the largest member; the waves beyond a member's own count exit at once.
+// The scans (UniformLevel / TableLevel) and qs_finish (UniformSums / TableSums) resolve their members the same way.
+constexpr int MAXLEV = 4;  // scan levels a series of the table may have (64^4 chunks)
+
+struct QExtent {
+  int64_t off;              // of its slice in the concatenated arrays (w: J times that)
+  int64_t n, lc, nchunks;
+  int64_t lev[MAXLEV + 1];  // its scan's level sizes, continued with 1 beyond its own depth
+  int64_t work, chunks;     // offsets of its scan work space and of its per-chunk sums and bad-pivot slots
+};
+
+struct Member {
+  int64_t n, lc, nchunks;
+  int64_t t, noise, y, fac;     // its coordinates, noise, right-hand side, c (w: J times fac)
+  int64_t work, pre, sums, bad; // its scan work space, chunk prefixes, per-chunk sums, bad-pivot slots
+};
+
+struct UniformExtent {
+  int64_t n, lc, nchunks, noise_stride, y_stride, work_stride, red_stride;
+  // eblocks: unused, the prefix pointer a kernel gets is member 0's already
+  __device__ __forceinline__ Member operator()(int64_t mem, int64_t eblocks = 0) const {
+    return {n, lc, nchunks, 0, mem * noise_stride, mem * y_stride, mem * n, mem * work_stride, mem * work_stride,
+            mem * red_stride, mem * nchunks};
+  }
+};
+
+struct TableExtent {
+  const QExtent* tab;
+  // eblocks: lane-blocks of level-0 elements per chunk, which precede the chunk prefixes in the member's work space
+  // (one right-hand side per member: y lies where the noise does)
+  __device__ __forceinline__ Member operator()(int64_t mem, int64_t eblocks = 0) const {
+    const QExtent& x = tab[mem];
+    return {x.n, x.lc, x.nchunks, x.off, x.off, x.off, x.off, x.work, x.work + x.nchunks * eblocks * WAVE, x.chunks,
+            x.chunks};
+  }
+};
+
 // ---- factor, phase 1: fold each chunk into one filtering element (A, C, J) ----------------------------------
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_fold(const QModel* __restrict__ mp, const double* __restrict__ t,
-                                                      const double* __restrict__ noise, int64_t noise_stride,
-                                                      int64_t n, int64_t lc, int64_t nchunks,
-                                                      double* __restrict__ elem, int64_t work_stride) {
+                                                      const double* __restrict__ noise, E ext,
+                                                      double* __restrict__ elem) {
   const Lane L;
-  if (L.wave >= nchunks) return;
   const int64_t mem = blockIdx.y;
+  const Member M = ext(mem);
+  if (L.wave >= M.nchunks) return;
   const QModel& m = mp[mem];
-  noise += mem * noise_stride, elem += mem * work_stride;
+  t += M.t, noise += M.noise, elem += M.work;
+  const int64_t n = M.n, lc = M.lc;
   const int J = m.J, r = L.r, c = L.c;
   const double P = m.P[L.lane];
   double A = (r == c && r < J) ? 1.0 : 0.0, C = 0.0, Jm = 0.0;
@@ -421,23 +470,67 @@ __device__ __forceinline__ void store_blocks(double* p, const double* v, int lan
   for (int k = 0; k < NB; ++k) p[k * WAVE + lane] = v[k];
 }
 
-// One level of a scan: `width` independent scans over `count` elements each, interleaved as element * width + scan;
-// one wavefront per group of GROUP elements of one scan.  Member blockIdx.y: model mp[blockIdx.y], its in, out and
-// prefixes work_stride doubles after its neighbour's.  qs_scan_reduce folds each group into one element of the next
-// level; qs_scan_down writes the state before every element of a group from the state before the group (prefix_in:
-// one per group; nullptr: the top level, which starts from 0).
+// Work layout of a scan over level sizes sz[]: level 0's elements (where the fold put them), then per level the
+// prefixes and the next level's elements.  *el, *pre: where level l's elements and prefixes start.
 template <class S>
+__host__ __device__ inline void level_offsets(const int64_t* sz, int l, int64_t width, int64_t* el, int64_t* pre) {
+  constexpr int64_t esz = S::ESZ * WAVE, psz = S::PSZ * WAVE;
+  int64_t e = 0, cur = sz[0] * width * esz;
+  for (int k = 0; k < l; ++k) {
+    cur += sz[k] * width * psz;
+    e = cur;
+    cur += sz[k + 1] * width * esz;
+  }
+  *el = e, *pre = cur;
+}
+
+// One level of one member's scan: its elements and groups, and where they lie from the pointers the kernel was given
+// (reduce: in, out; down: in, pre_in, pre_out)
+struct Level {
+  int64_t count, ngroups, in, out, pre_in, pre_out;
+};
+
+struct UniformLevel {  // the pointers are member 0's, member b's work_stride doubles after member b - 1's
+  int64_t count, ngroups, work_stride;
+  template <class S>
+  __device__ __forceinline__ Level at(int64_t mem, int64_t width) const {
+    const int64_t o = mem * work_stride;
+    return {count, ngroups, o, o, o, o};
+  }
+};
+
+struct TableLevel {  // level `level` of every member's own scan; the pointers are the base of the work space
+  const QExtent* tab;
+  int32_t level;
+  template <class S>
+  __device__ __forceinline__ Level at(int64_t mem, int64_t width) const {
+    const QExtent& x = tab[mem];
+    int64_t el, pre, el_up, pre_up;
+    level_offsets<S>(x.lev, level, width, &el, &pre);
+    level_offsets<S>(x.lev, level + 1, width, &el_up, &pre_up);
+    return {x.lev[level], x.lev[level + 1], x.work + el, x.work + el_up, x.work + pre_up, x.work + pre};
+  }
+};
+
+// One level of a scan: `width` independent scans over `count` elements each, interleaved as element * width + scan;
+// one wavefront per group of GROUP elements of one scan.  Member blockIdx.y: model mp[blockIdx.y], its level from the
+// policy E.  qs_scan_reduce folds each group into one element of the next level; qs_scan_down writes the state before
+// every element of a group from the state before the group (prefix_in: one per group; nullptr: the top level, which
+// starts from 0).  A member of a table whose own scan is shallower than the launch has one element per upper level:
+// the reduce copies it, the top-level down pass stores the zero state, and its level-0 prefixes start from the same
+// +0.0 as when its own top level is the launch's.
+template <class S, class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_scan_reduce(const QModel* __restrict__ mp,
-                                                             const double* __restrict__ in, int64_t count,
-                                                             int64_t width, double* __restrict__ out, int64_t ngroups,
-                                                             int64_t work_stride) {
+                                                             const double* __restrict__ in, int64_t width,
+                                                             double* __restrict__ out, E lev) {
   const Lane L;
-  if (L.wave >= ngroups * width) return;
   const int64_t mem = blockIdx.y;
+  const Level V = lev.template at<S>(mem, width);
+  if (L.wave >= V.ngroups * width) return;
   const int J = mp[mem].J;
-  in += mem * work_stride, out += mem * work_stride;
+  in += V.in, out += V.out;
   const int64_t g = L.wave / width, d = L.wave % width;
-  const int64_t b = g * GROUP, e = min(count, b + GROUP);
+  const int64_t b = g * GROUP, e = min(V.count, b + GROUP);
   double a[S::ESZ], x[S::ESZ];
   load_blocks<S::ESZ>(a, in + (b * width + d) * S::ESZ * WAVE, L.lane);
   for (int64_t i = b + 1; i < e; ++i) {
@@ -447,23 +540,23 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_scan_reduce(const QModel* __res
   store_blocks<S::ESZ>(out + L.wave * S::ESZ * WAVE, a, L.lane);
 }
 
-template <class S>
+template <class S, class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_scan_down(const QModel* __restrict__ mp,
-                                                           const double* __restrict__ elem, int64_t count,
-                                                           int64_t width, const double* __restrict__ prefix_in,
-                                                           double* __restrict__ prefix_out, int64_t ngroups,
-                                                           int64_t work_stride) {
+                                                           const double* __restrict__ elem, int64_t width,
+                                                           const double* __restrict__ prefix_in,
+                                                           double* __restrict__ prefix_out, E lev) {
   const Lane L;
-  if (L.wave >= ngroups * width) return;
   const int64_t mem = blockIdx.y;
+  const Level V = lev.template at<S>(mem, width);
+  if (L.wave >= V.ngroups * width) return;
   const int J = mp[mem].J;
-  elem += mem * work_stride, prefix_out += mem * work_stride;
+  elem += V.in, prefix_out += V.pre_out;
   const int64_t g = L.wave / width, d = L.wave % width;
-  const int64_t b = g * GROUP, e = min(count, b + GROUP);
+  const int64_t b = g * GROUP, e = min(V.count, b + GROUP);
   double p[S::PSZ], x[S::ESZ];
 #pragma unroll
   for (int k = 0; k < S::PSZ; ++k) p[k] = 0.0;
-  if (prefix_in) load_blocks<S::PSZ>(p, prefix_in + mem * work_stride + L.wave * S::PSZ * WAVE, L.lane);
+  if (prefix_in) load_blocks<S::PSZ>(p, prefix_in + V.pre_in + L.wave * S::PSZ * WAVE, L.lane);
   for (int64_t i = b; i < e; ++i) {
     store_blocks<S::PSZ>(prefix_out + (i * width + d) * S::PSZ * WAVE, p, L.lane);
     load_blocks<S::ESZ>(x, elem + (i * width + d) * S::ESZ * WAVE, L.lane);
@@ -472,21 +565,22 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_scan_down(const QModel* __restr
 }
 
 // ---- factor, phase 3: the sequential recursion from each chunk's incoming filtered covariance ------------------
-// member blockIdx.y: c at cbuf + y n, w at wbuf + y n J, its bad-pivot slots at bad + y nchunks
+// member blockIdx.y (uniform: c at cbuf + y n, w at wbuf + y n J, its bad-pivot slots at bad + y nchunks)
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_emit(const QModel* __restrict__ mp, const double* __restrict__ t,
-                                                      const double* __restrict__ noise, int64_t noise_stride,
-                                                      int64_t n, int64_t lc, int64_t nchunks,
-                                                      const double* __restrict__ prefix, int64_t work_stride,
-                                                      double* __restrict__ cbuf, double* __restrict__ wbuf,
-                                                      double* __restrict__ logsum, int64_t red_stride,
+                                                      const double* __restrict__ noise, E ext,
+                                                      const double* __restrict__ prefix, double* __restrict__ cbuf,
+                                                      double* __restrict__ wbuf, double* __restrict__ logsum,
                                                       int64_t* __restrict__ bad) {
   const Lane L;
-  if (L.wave >= nchunks) return;
   const int64_t mem = blockIdx.y;
+  const Member M = ext(mem, ScanRiccati::ESZ);
+  if (L.wave >= M.nchunks) return;
   const QModel& m = mp[mem];
   const int J = m.J, r = L.r, c = L.c;
-  noise += mem * noise_stride, prefix += mem * work_stride, cbuf += mem * n, wbuf += mem * n * J;
-  logsum += mem * red_stride, bad += mem * nchunks;
+  t += M.t, noise += M.noise, prefix += M.pre, cbuf += M.fac, wbuf += M.fac * J;
+  logsum += M.sums, bad += M.bad;
+  const int64_t n = M.n, lc = M.lc;
   const double Pinf = m.P[L.lane];
   double P = prefix[L.wave * WAVE + L.lane];
   double acc = 0.0;
@@ -566,17 +660,19 @@ struct Chunk {
   __device__ int64_t step(int64_t j) const { return back ? n1 - 1 - j : n0 + j; }
 };
 
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_aff_fold(int op, const QModel* __restrict__ mp,
                                                           const double* __restrict__ t, const double* __restrict__ cbuf,
-                                                          const double* __restrict__ wbuf, int64_t n, int64_t lc,
-                                                          int64_t nchunks, int64_t nrhs, int64_t ncg,
-                                                          const double* __restrict__ y, int64_t y_stride,
-                                                          double* __restrict__ elem, int64_t work_stride) {
+                                                          const double* __restrict__ wbuf, E ext, int64_t nrhs,
+                                                          int64_t ncg, const double* __restrict__ y,
+                                                          double* __restrict__ elem) {
   const Lane L;
-  if (L.wave >= nchunks * ncg) return;
   const int64_t mem = blockIdx.y;
+  const Member mx = ext(mem);
+  if (L.wave >= mx.nchunks * ncg) return;
   const QModel& m = mp[mem];
-  cbuf += mem * n, wbuf += mem * n * m.J, y += mem * y_stride, elem += mem * work_stride;
+  t += mx.t, cbuf += mx.fac, wbuf += mx.fac * m.J, y += mx.y, elem += mx.work;
+  const int64_t n = mx.n, lc = mx.lc, nchunks = mx.nchunks;
   const int r = L.r, c = L.c;
   const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
   double M = (r == c && r < m.J) ? 1.0 : 0.0, V = 0.0, o;
@@ -592,19 +688,20 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_fold(int op, const QModel* 
   e[L.lane] = M, e[WAVE + L.lane] = V;
 }
 
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_aff_emit(int op, const QModel* __restrict__ mp,
                                                           const double* __restrict__ t, const double* __restrict__ cbuf,
-                                                          const double* __restrict__ wbuf, int64_t n, int64_t lc,
-                                                          int64_t nchunks, int64_t nrhs, int64_t ncg,
-                                                          const double* __restrict__ prefix, int64_t work_stride,
-                                                          const double* __restrict__ y, int64_t y_stride,
-                                                          double* __restrict__ out, double* __restrict__ sumsq,
-                                                          int64_t red_stride) {
+                                                          const double* __restrict__ wbuf, E ext, int64_t nrhs,
+                                                          int64_t ncg, const double* __restrict__ prefix,
+                                                          const double* __restrict__ y, double* __restrict__ out,
+                                                          double* __restrict__ sumsq) {
   const Lane L;
-  if (L.wave >= nchunks * ncg) return;
   const int64_t mem = blockIdx.y;
+  const Member mx = ext(mem, ScanAffine::ESZ * ncg);
+  if (L.wave >= mx.nchunks * ncg) return;
   const QModel& m = mp[mem];
-  cbuf += mem * n, wbuf += mem * n * m.J, prefix += mem * work_stride, y += mem * y_stride, out += mem * n * nrhs;
+  t += mx.t, cbuf += mx.fac, wbuf += mx.fac * m.J, prefix += mx.pre, y += mx.y, out += mx.fac * nrhs;
+  const int64_t n = mx.n, lc = mx.lc, nchunks = mx.nchunks;
   const int r = L.r, c = L.c;
   const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
   double X = prefix[L.wave * WAVE + L.lane], o = 0.0, acc = 0.0;
@@ -622,7 +719,7 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_emit(int op, const QModel* 
   if (sumsq) {  // fixed-order sum over the 8 columns of row 0
     double s = 0.0;
     for (int q = 0; q < 8; ++q) s += sh(acc, q);
-    if (L.lane == 0) sumsq[mem * red_stride + L.wave] = s;
+    if (L.lane == 0) sumsq[mx.sums + L.wave] = s;
   }
 }
 
@@ -1043,18 +1140,37 @@ __global__ __launch_bounds__(WAVE * WPB) __attribute__((amdgpu_waves_per_eu(4, 4
   }
 }
 
-// one wavefront per block: fixed-order sums of a[0..na) and b[0..nb), minimum of bad[0..na).  Block x reads a and b
-// x in_stride doubles, bad x bad_stride slots further on and writes out and first_bad x out_stride slots further on.
-__global__ __launch_bounds__(WAVE) void qs_finish(const double* __restrict__ a, int64_t na,
-                                                  const double* __restrict__ b, int64_t nb,
+// What qs_finish sums for member `mem`: a[0..na), b[0..nb) and the minimum of bad[0..na), as offsets from its pointers
+struct Sums {
+  int64_t na, nb, a, b, bad;
+};
+struct UniformSums {  // member x reads a and b x in_stride doubles, bad x bad_stride slots further on
+  int64_t na, nb, in_stride, bad_stride;
+  __device__ __forceinline__ Sums operator()(int64_t mem) const {
+    return {na, nb, mem * in_stride, mem * in_stride, mem * bad_stride};
+  }
+};
+struct TableSums {  // a, b and bad: the per-chunk arrays of all members, each member's part where its extent says
+  const QExtent* tab;
+  __device__ __forceinline__ Sums operator()(int64_t mem) const {
+    const QExtent& x = tab[mem];
+    return {x.nchunks, x.nchunks, x.chunks, x.chunks, x.chunks};
+  }
+};
+
+// one wavefront per block: fixed-order sums and the first bad pivot of member blockIdx.x, which writes out and first_bad
+// x out_stride slots further on
+template <class E>
+__global__ __launch_bounds__(WAVE) void qs_finish(const double* __restrict__ a, const double* __restrict__ b,
                                                   const int64_t* __restrict__ bad, double* __restrict__ out,
-                                                  int64_t* __restrict__ first_bad, int64_t in_stride,
-                                                  int64_t bad_stride, int64_t out_stride) {
+                                                  int64_t* __restrict__ first_bad, E sums, int64_t out_stride) {
   const int lane = threadIdx.x;
   const int64_t mem = blockIdx.x;
-  a += mem * in_stride, out += mem * out_stride;
-  if (b) b += mem * in_stride;
-  if (bad) bad += mem * bad_stride;
+  const Sums U = sums(mem);
+  const int64_t na = U.na, nb = U.nb;
+  a += U.a, out += mem * out_stride;
+  if (b) b += U.b;
+  if (bad) bad += U.bad;
   if (first_bad) first_bad += mem * out_stride;
   double sa = 0.0, sb = 0.0;
   int64_t mb = INT64_MAX;
@@ -1118,6 +1234,21 @@ struct tgp_qsep {
   int64_t bat_elems = 0;
 };
 
+// A set of series, each on coordinates of its own: the concatenated t and the extent table stay resident
+struct tgp_qsep_series {
+  tgp_ctx* ctx = nullptr;
+  int64_t nseries = 0;
+  std::vector<int64_t> offsets;  // nseries + 1: series b is [offsets[b], offsets[b + 1]) of the concatenated arrays
+  std::vector<QExtent> ext;      // the table's host copy; series_split fills the offsets inside a chain
+  std::vector<int64_t> chain0;   // the split for table_J: every chain's first member, then nseries
+  int32_t table_J = 0;           // the state dimension the resident table's chains were cut for (0: none yet)
+  int64_t buf_need = 0;          // what the largest of those chains needs, in doubles
+  double* t = nullptr;
+  QExtent* tab = nullptr;
+  double* buf = nullptr;         // the models and every array of one launch chain (the capped scratch)
+  int64_t buf_elems = 0;
+};
+
 namespace {
 
 using tgp::set_error;
@@ -1147,33 +1278,51 @@ std::vector<int64_t> level_sizes(int64_t count) {
 template <class S>
 int run_scan(const QModel* models, hipStream_t st, int64_t count, int64_t width, double* elem0, double** prefix0,
              int64_t members = 1, int64_t work_stride = 0) {
-  constexpr int64_t esz = S::ESZ * WAVE, psz = S::PSZ * WAVE;
   const std::vector<int64_t> sz = level_sizes(count);
   std::vector<double*> el(sz.size()), pre(sz.size());
-  el[0] = elem0;
-  double* cur = elem0 + count * width * esz;
   for (size_t l = 0; l < sz.size(); ++l) {
-    if (l) {
-      el[l] = cur;
-      cur += sz[l] * width * esz;
-    }
-    pre[l] = cur;
-    cur += sz[l] * width * psz;
+    int64_t e, p;
+    level_offsets<S>(sz.data(), int(l), width, &e, &p);
+    el[l] = elem0 + e, pre[l] = elem0 + p;
   }
   for (size_t l = 0; l + 1 < sz.size(); ++l) {
     const int64_t g = sz[l + 1];
-    qs_scan_reduce<S><<<dim3(unsigned(blocks_for(g * width)), unsigned(members)), WAVE * WPB, 0, st>>>(
-        models, el[l], sz[l], width, el[l + 1], g, work_stride);
+    qs_scan_reduce<S, UniformLevel><<<dim3(unsigned(blocks_for(g * width)), unsigned(members)), WAVE * WPB, 0, st>>>(
+        models, el[l], width, el[l + 1], UniformLevel{sz[l], g, work_stride});
   }
   for (size_t l = sz.size(); l-- > 0;) {
     const int64_t g = l + 1 < sz.size() ? sz[l + 1] : 1;
     const double* pin = l + 1 < sz.size() ? pre[l + 1] : nullptr;
-    qs_scan_down<S><<<dim3(unsigned(blocks_for(g * width)), unsigned(members)), WAVE * WPB, 0, st>>>(
-        models, el[l], sz[l], width, pin, pre[l], g, work_stride);
+    qs_scan_down<S, UniformLevel><<<dim3(unsigned(blocks_for(g * width)), unsigned(members)), WAVE * WPB, 0, st>>>(
+        models, el[l], width, pin, pre[l], UniformLevel{sz[l], g, work_stride});
   }
   TGP_HIP_TRY(hipGetLastError());
   *prefix0 = pre[0];
   return TGP_OK;
+}
+
+// The same over the members of an extent table, each with a scan of its own: the levels of the deepest member are
+// launched (top[l]: the largest level-l size, `depth` levels), every grid sized for the largest member.  One scan per
+// member (width 1); the level-0 prefixes land in each member's work space, where TableExtent looks for them.
+template <class S>
+int run_scan_table(const QModel* models, hipStream_t st, const QExtent* tab, int64_t members, const int64_t* top,
+                   int depth, double* work) {
+  for (int l = 0; l + 1 < depth; ++l)
+    qs_scan_reduce<S, TableLevel><<<dim3(unsigned(blocks_for(top[l + 1])), unsigned(members)), WAVE * WPB, 0, st>>>(
+        models, work, 1, work, TableLevel{tab, l});
+  for (int l = depth; l-- > 0;)
+    qs_scan_down<S, TableLevel><<<dim3(unsigned(blocks_for(top[l + 1])), unsigned(members)), WAVE * WPB, 0, st>>>(
+        models, work, 1, l + 1 < depth ? work : nullptr, work, TableLevel{tab, l});
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
+// chunk length: about 4096 chunks, 16..256 steps each (a function of n only: results depend neither on the device nor
+// on what else a launch serves)
+int64_t chunk_length(int64_t n) {
+  int64_t lc = 16;
+  while (lc < 256 && lc * 4096 < n) lc *= 2;
+  return lc;
 }
 
 template <class S>
@@ -1228,10 +1377,10 @@ int launch_factor(tgp_qsep* q, const QModel* models, int64_t members, const doub
   hipStream_t st = q->ctx->stream;
   const int64_t n = q->n, nc = q->nchunks;
   const dim3 grid(unsigned(blocks_for(nc)), unsigned(members));
-  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, noise_stride, n, q->lc, nc, work, work_stride);
+  const UniformExtent ext{n, q->lc, nc, noise_stride, 0, work_stride, red_stride};
+  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, ext, work);
   TGP_TRY(run_scan<ScanRiccati>(models, st, nc, 1, work, prefix, members, work_stride));
-  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, noise_stride, n, q->lc, nc, *prefix, work_stride, cbuf,
-                                       wbuf, logsum, red_stride, bad);
+  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, ext, *prefix, cbuf, wbuf, logsum, bad);
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
@@ -1246,11 +1395,10 @@ int launch_affine(tgp_qsep* q, int op, const QModel* models, int64_t members, co
   hipStream_t st = q->ctx->stream;
   const int64_t n = q->n, nc = q->nchunks, ncg = ceil_div(nrhs, 8);
   const dim3 grid(unsigned(blocks_for(nc * ncg)), unsigned(members));
-  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(op, models, q->t, cbuf, wbuf, n, q->lc, nc, nrhs, ncg, y, y_stride, work,
-                                           work_stride);
+  const UniformExtent ext{n, q->lc, nc, 0, y_stride, work_stride, red_stride};
+  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(op, models, q->t, cbuf, wbuf, ext, nrhs, ncg, y, work);
   TGP_TRY(run_scan<ScanAffine>(models, st, nc, ncg, work, prefix, members, work_stride));
-  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(op, models, q->t, cbuf, wbuf, n, q->lc, nc, nrhs, ncg, *prefix, work_stride,
-                                           y, y_stride, out, sumsq, red_stride);
+  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(op, models, q->t, cbuf, wbuf, ext, nrhs, ncg, *prefix, y, out, sumsq);
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
@@ -1266,7 +1414,7 @@ int factor(tgp_qsep* q, const double* noise_host, double* keep = nullptr) {
   TGP_TRY(launch_factor(q, q->model, 1, q->noise, 0, q->work, 0, q->c, q->w, q->red, 0, q->bad, &prefix));
   if (keep)
     TGP_HIP_TRY(hipMemcpyAsync(keep, prefix, size_t(nc) * WAVE * sizeof(double), hipMemcpyDeviceToDevice, st));
-  qs_finish<<<1, WAVE, 0, st>>>(q->red, nc, nullptr, 0, q->bad, q->red + 2 * nc, q->bad + nc, 0, 0, 0);
+  qs_finish<<<1, WAVE, 0, st>>>(q->red, nullptr, q->bad, q->red + 2 * nc, q->bad + nc, UniformSums{nc, 0, 0, 0}, 0);
   TGP_HIP_TRY(hipGetLastError());
   double sums[2];
   int64_t bad = 0;
@@ -1291,7 +1439,8 @@ int affine(tgp_qsep* q, int op, int64_t nrhs, const double* y, double* out, doub
   if (keep)
     TGP_HIP_TRY(hipMemcpyAsync(keep, prefix, size_t(nc * ncg) * WAVE * sizeof(double), hipMemcpyDeviceToDevice, st));
   if (sumsq) {
-    qs_finish<<<1, WAVE, 0, st>>>(q->red, nc * ncg, nullptr, 0, nullptr, q->red + 2 * nc * ncg, nullptr, 0, 0, 0);
+    qs_finish<<<1, WAVE, 0, st>>>(q->red, nullptr, nullptr, q->red + 2 * nc * ncg, nullptr,
+                                  UniformSums{nc * ncg, 0, 0, 0}, 0);
     TGP_HIP_TRY(hipMemcpyAsync(sumsq, q->red + 2 * nc * ncg, sizeof(double), hipMemcpyDeviceToHost, st));
   }
   TGP_HIP_TRY(hipGetLastError());
@@ -1432,7 +1581,7 @@ int launch_tangents(tgp_qsep* q, const QModel* models, int64_t members, const QD
   qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, cbuf, wbuf, dcb, dwb, resid, resid_stride, n, q->lc, nc,
                                        prefixS, keep_stride, prefix, nullptr, work_stride, dsum2);
   // block b: (member, direction) b's two sums (dsum2 lies md nc doubles after dsum, like its rows)
-  qs_finish<<<unsigned(md), WAVE, 0, st>>>(dsum, nc, dsum2, nc, nullptr, res, nullptr, nc, 0, 2);
+  qs_finish<<<unsigned(md), WAVE, 0, st>>>(dsum, dsum2, nullptr, res, nullptr, UniformSums{nc, nc, nc, 0}, 2);
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
@@ -1510,6 +1659,15 @@ __attribute__((noinline)) double logprob_value(double zz, double logdet, int64_t
   return -0.5 * zz - 0.5 * logdet - 0.5 * double(n) * kLog2Pi;
 }
 
+// what qs_finish leaves per member of a batch -- (sum log c, sum z^2, first bad pivot), the third an int64 in a double's
+// slot -- as that member's info and value
+void member_value(const double* got, int64_t n, int32_t* info, double* out) {
+  int64_t first_bad;
+  memcpy(&first_bad, &got[2], sizeof(first_bad));
+  *info = first_bad == INT64_MAX ? 0 : int32_t(first_bad + 1);
+  *out = *info ? NAN : logprob_value(got[1], got[0], n);
+}
+
 // ---- batches of models over the one series -----------------------------------------------------------------------------
 // A launch chain evaluates up to BATCH_MAX_MEMBERS models, and as many as keep the handle's batch buffer at or under
 // BATCH_SCRATCH_BYTES.  The buffer, in doubles:
@@ -1567,18 +1725,120 @@ int batch_chain(tgp_qsep* q, const BatchLayout& lay, int64_t cap, int64_t nb, co
   TGP_TRY(launch_affine(q, TGP_QS_FWD, models, nb, cbuf, wbuf, 1, resid, resid_stride, work, W, z, red + nc, 2 * nc,
                         &prefix));
   // per member: (sum log c, sum z^2, first bad pivot), the third an int64 in a double's slot
-  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(red, nc, red + nc, nc, bad, res, reinterpret_cast<int64_t*>(res) + 2,
-                                           2 * nc, nc, 3);
+  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(red, red + nc, bad, res, reinterpret_cast<int64_t*>(res) + 2,
+                                           UniformSums{nc, nc, 2 * nc, nc}, 3);
   TGP_HIP_TRY(hipGetLastError());
   std::vector<double> got(size_t(3 * nb));
   TGP_HIP_TRY(hipMemcpyAsync(got.data(), res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   TGP_HIP_TRY(hipStreamSynchronize(st));
-  for (int64_t b = 0; b < nb; ++b) {
-    int64_t first_bad;
-    memcpy(&first_bad, &got[size_t(3 * b + 2)], sizeof(first_bad));
-    info[b] = first_bad == INT64_MAX ? 0 : int32_t(first_bad + 1);
-    out[b] = info[b] ? NAN : logprob_value(got[size_t(3 * b + 1)], got[size_t(3 * b)], n);
+  for (int64_t b = 0; b < nb; ++b) member_value(&got[size_t(3 * b)], n, &info[b], &out[b]);
+  return TGP_OK;
+}
+
+// ---- sets of series -------------------------------------------------------------------------------------------------------
+// B series, each on its own coordinates, in launch chains of up to BATCH_MAX_MEMBERS members under the same
+// BATCH_SCRATCH_BYTES.  A chain's buffer holds what its own members need and no more, in doubles:
+//   fixed        BATCH_MAX_MEMBERS models
+//   by array     noise | residual | c | z (sum N_b each) | w (J sum N_b) | scan work space (sum W_b) | per-chunk sums of
+//                log c | of z^2 | bad-pivot slots (sum nchunks_b each) | results (3 per member)
+// with W_b = 256 x (the sizes of MAXLEV scan levels of series b, 1 beyond its own depth): the Riccati scan's 4
+// lane-blocks per element and level, the larger need of the chain's two scans.  Series b therefore needs
+//   need_b = N_b (4 + J) + W_b + 3 nchunks_b + 3.
+// The split (series_split): chains are filled in the order given; a chain ends at BATCH_MAX_MEMBERS members or before
+// the member whose need would take it past the cap.  A function of (N_0 .. N_{B-1}, J) alone.
+constexpr int64_t SERIES_BLOCKS = std::max(ScanRiccati::ESZ + ScanRiccati::PSZ, ScanAffine::ESZ + ScanAffine::PSZ);
+
+int64_t series_work(const QExtent& x) {
+  int64_t s = 0;
+  for (int l = 0; l < MAXLEV; ++l) s += x.lev[l];
+  return s * SERIES_BLOCKS * WAVE;
+}
+
+int64_t series_need(const QExtent& x, int64_t J) { return x.n * (4 + J) + series_work(x) + 3 * x.nchunks + 3; }
+
+// cuts the set into chains for state dimension J and makes the resident table say where each member lies in its chain
+int series_split(tgp_qsep_series* s, int32_t J) {
+  if (s->table_J == J) return TGP_OK;
+  const int64_t budget = BATCH_SCRATCH_BYTES / int64_t(sizeof(double)) - BATCH_MAX_MEMBERS * MODEL_DOUBLES;
+  for (int64_t b = 0; b < s->nseries; ++b)
+    TGP_ARG_CHECK(series_need(s->ext[size_t(b)], J) <= budget,
+                  "series %lld (n = %lld) needs %lld doubles of scratch and exceeds its cap of %lld bytes", (long long)b,
+                  (long long)s->ext[size_t(b)].n, (long long)series_need(s->ext[size_t(b)], J),
+                  (long long)BATCH_SCRATCH_BYTES);
+  s->table_J = 0;
+  s->chain0.assign(1, 0);
+  int64_t used = 0, count = 0, largest = 0, off = 0, work = 0, chunks = 0;
+  for (int64_t b = 0; b < s->nseries; ++b) {
+    QExtent& x = s->ext[size_t(b)];
+    const int64_t need = series_need(x, J);
+    if (count == BATCH_MAX_MEMBERS || used + need > budget) {
+      s->chain0.push_back(b);
+      used = count = off = work = chunks = 0;
+    }
+    x.off = off, x.work = work, x.chunks = chunks;
+    off += x.n, work += series_work(x), chunks += x.nchunks;
+    used += need, ++count;
+    largest = std::max(largest, used);
   }
+  s->chain0.push_back(s->nseries);
+  s->buf_need = BATCH_MAX_MEMBERS * MODEL_DOUBLES + largest;
+  hipStream_t st = s->ctx->stream;
+  TGP_HIP_TRY(hipMemcpyAsync(s->tab, s->ext.data(), s->ext.size() * sizeof(QExtent), hipMemcpyHostToDevice, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  s->table_J = J;
+  return TGP_OK;
+}
+
+// one launch chain: members [b0, b0 + nb) of the set; the host arrays are the concatenated ones
+int series_chain(tgp_qsep_series* s, int64_t b0, int64_t nb, const QModel* models_host, int64_t J,
+                 const double* noise_host, const double* resid_host, int32_t* info, double* out) {
+  hipStream_t st = s->ctx->stream;
+  const QExtent* mine = &s->ext[size_t(b0)];
+  int64_t N = 0, W = 0, C = 0, top[MAXLEV + 1] = {};
+  for (int64_t b = 0; b < nb; ++b) {
+    N += mine[b].n, W += series_work(mine[b]), C += mine[b].nchunks;
+    for (int l = 0; l <= MAXLEV; ++l) top[l] = std::max(top[l], mine[b].lev[l]);
+  }
+  int depth = 1;  // the deepest member's: the level sizes grow with the chunk count
+  while (top[depth - 1] > GROUP) ++depth;
+  QModel* models = reinterpret_cast<QModel*>(s->buf);
+  double* p = s->buf + BATCH_MAX_MEMBERS * MODEL_DOUBLES;
+  auto take = [&](int64_t len) {
+    double* r = p;
+    p += len;
+    return r;
+  };
+  double* noise = take(N);
+  double* resid = take(N);
+  double* cbuf = take(N);
+  double* wbuf = take(N * J);
+  double* z = take(N);
+  double* work = take(W);
+  double* logsum = take(C);
+  double* sumsq = take(C);
+  int64_t* bad = reinterpret_cast<int64_t*>(take(C));
+  double* res = take(3 * nb);
+  const int64_t at = s->offsets[size_t(b0)];
+  const double* t = s->t + at;
+  const QExtent* tab = s->tab + b0;
+  const TableExtent ext{tab};
+  TGP_HIP_TRY(hipMemcpyAsync(models, models_host, size_t(nb) * sizeof(QModel), hipMemcpyHostToDevice, st));
+  TGP_HIP_TRY(hipMemcpyAsync(noise, noise_host + at, size_t(N) * sizeof(double), hipMemcpyHostToDevice, st));
+  TGP_HIP_TRY(hipMemcpyAsync(resid, resid_host + at, size_t(N) * sizeof(double), hipMemcpyHostToDevice, st));
+  const dim3 grid(unsigned(blocks_for(top[0])), unsigned(nb));
+  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, t, noise, ext, work);
+  TGP_TRY(run_scan_table<ScanRiccati>(models, st, tab, nb, top, depth, work));
+  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, t, noise, ext, work, cbuf, wbuf, logsum, bad);
+  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, t, cbuf, wbuf, ext, 1, 1, resid, work);
+  TGP_TRY(run_scan_table<ScanAffine>(models, st, tab, nb, top, depth, work));
+  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, t, cbuf, wbuf, ext, 1, 1, work, resid, z, sumsq);
+  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(logsum, sumsq, bad, res, reinterpret_cast<int64_t*>(res) + 2, TableSums{tab},
+                                           3);
+  TGP_HIP_TRY(hipGetLastError());
+  std::vector<double> got(size_t(3 * nb));
+  TGP_HIP_TRY(hipMemcpyAsync(got.data(), res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t b = 0; b < nb; ++b) member_value(&got[size_t(3 * b)], mine[b].n, &info[b], &out[b]);
   return TGP_OK;
 }
 
@@ -1677,8 +1937,8 @@ int grad_batch_chain(tgp_qsep* q, const GradLayout& lay, int64_t nb, const QMode
                         &prefix));
   qs_keep_rows<<<kgrid, 256, 0, st>>>(prefix, W, keep + nc * WAVE, KS, nc * WAVE);
   // per member: (sum log c, sum z^2, first bad pivot), the third an int64 in a double's slot
-  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(red, nc, red + nc, nc, bad, res, reinterpret_cast<int64_t*>(res) + 2,
-                                           2 * nc, nc, 3);
+  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(red, red + nc, bad, res, reinterpret_cast<int64_t*>(res) + 2,
+                                           UniformSums{nc, nc, 2 * nc, nc}, 3);
   TGP_HIP_TRY(hipGetLastError());
   // direction passes: pass k's host directions (member-major) stay alive until the synchronisation below, its results
   // land after those of the passes before it (2 nb d0 doubles)
@@ -1762,11 +2022,8 @@ int tgp_qsep_create(tgp_ctx* ctx, int64_t n, const double* t_host, tgp_qsep** ou
   tgp_qsep* q = new tgp_qsep();
   q->ctx = ctx;
   q->n = n;
-  // chunk length: about 4096 chunks, 16..256 steps each (a function of n only: results do not depend on the device)
-  int64_t lc = 16;
-  while (lc < 256 && lc * 4096 < n) lc *= 2;
-  q->lc = lc;
-  q->nchunks = ceil_div(n, lc);
+  q->lc = chunk_length(n);
+  q->nchunks = ceil_div(n, q->lc);
   auto fail = [&](int code) { tgp_qsep_destroy(q); return code; };
 #define Q_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) {                \
     set_error("%s failed: %s", #expr, hipGetErrorString(_e));                          \
@@ -1969,6 +2226,85 @@ int tgp_qsep_grad_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_t n
   }
   if (nchains) *nchains = chains;
   if (npasses) *npasses = passes;
+  return TGP_OK;
+}
+
+int tgp_qsep_series_create(tgp_ctx* ctx, int32_t nseries, const int64_t* offsets, const double* t_concat,
+                           tgp_qsep_series** out) {
+  TGP_ARG_CHECK(ctx != nullptr, "null context");
+  std::unique_lock<std::recursive_mutex> lock(ctx->mu);
+  TGP_HIP_TRY(hipSetDevice(ctx->device));
+  TGP_ARG_CHECK(out != nullptr && offsets != nullptr && t_concat != nullptr, "null argument");
+  TGP_ARG_CHECK(nseries >= 1, "need at least one series (nseries = %d)", nseries);
+  TGP_ARG_CHECK(offsets[0] == 0, "the offsets start at 0 (got %lld)", (long long)offsets[0]);
+  for (int32_t b = 0; b < nseries; ++b) {
+    TGP_ARG_CHECK(offsets[b + 1] >= offsets[b], "the offsets must not decrease (series %d: %lld after %lld)", b,
+                  (long long)offsets[b + 1], (long long)offsets[b]);
+    TGP_ARG_CHECK(offsets[b + 1] > offsets[b], "series %d is empty: every series needs at least one data point", b);
+  }
+  std::vector<QExtent> ext(size_t(nseries), QExtent{});
+  for (int32_t b = 0; b < nseries; ++b) {
+    QExtent& x = ext[size_t(b)];
+    x.n = offsets[b + 1] - offsets[b];
+    x.lc = chunk_length(x.n);  // the single call's rule: a member's chunks are those of its own solver
+    x.nchunks = ceil_div(x.n, x.lc);
+    x.lev[0] = x.nchunks;
+    for (int l = 0; l < MAXLEV; ++l) x.lev[l + 1] = ceil_div(x.lev[l], GROUP);
+    TGP_ARG_CHECK(x.lev[MAXLEV - 1] <= GROUP, "series %d (n = %lld) needs more than %d scan levels", b,
+                  (long long)x.n, MAXLEV);
+  }
+  tgp_qsep_series* s = new tgp_qsep_series();
+  s->ctx = ctx;
+  s->nseries = nseries;
+  s->offsets.assign(offsets, offsets + nseries + 1);
+  s->ext = std::move(ext);
+  auto fail = [&](int code) { tgp_qsep_series_destroy(s); return code; };
+#define Q_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) {                \
+    set_error("%s failed: %s", #expr, hipGetErrorString(_e));                          \
+    return fail(_e == hipErrorOutOfMemory ? TGP_E_NOMEM : TGP_E_HIP); } } while (0)
+  const size_t total = size_t(offsets[nseries]);
+  Q_TRY(hipMalloc(&s->t, total * sizeof(double)));
+  Q_TRY(hipMalloc(&s->tab, size_t(nseries) * sizeof(QExtent)));
+  Q_TRY(hipMemcpyAsync(s->t, t_concat, total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  Q_TRY(hipStreamSynchronize(ctx->stream));
+#undef Q_TRY
+  *out = s;
+  return TGP_OK;
+}
+
+int tgp_qsep_series_destroy(tgp_qsep_series* s) {
+  if (!s) return TGP_OK;
+  if (s->ctx) {
+    hipSetDevice(s->ctx->device);
+    hipStreamSynchronize(s->ctx->stream);
+  }
+  void* bufs[] = {s->t, s->tab, s->buf};
+  for (void* b : bufs)
+    if (b) hipFree(b);
+  delete s;
+  return TGP_OK;
+}
+
+int tgp_qsep_series_logprob(tgp_qsep_series* s, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                            int32_t J, const double* hvec, const double* Pinf, const double* noise_concat,
+                            const double* resid_concat, int32_t* info, double* out, int32_t* nchains) {
+  QS_GUARD(s);
+  if (nchains) *nchains = 0;
+  TGP_ARG_CHECK(leaves && state_map && hvec && Pinf, "null model array");
+  TGP_ARG_CHECK(noise_concat && resid_concat && info && out, "null argument");
+  const int64_t nb = s->nseries;
+  std::vector<QModel> models(size_t(nb), QModel{});
+  for (int64_t b = 0; b < nb; ++b)
+    TGP_TRY(pack_model(&models[size_t(b)], leaves + b * nleaves * 5, nleaves, state_map, J, hvec + b * J,
+                       Pinf + b * J * J));
+  TGP_TRY(series_split(s, J));
+  TGP_TRY(grow(&s->buf, &s->buf_elems, s->buf_need));
+  const size_t chains = s->chain0.size() - 1;
+  for (size_t k = 0; k < chains; ++k) {
+    const int64_t b0 = s->chain0[k], cnt = s->chain0[k + 1] - b0;
+    TGP_TRY(series_chain(s, b0, cnt, models.data() + b0, J, noise_concat, resid_concat, info + b0, out + b0));
+  }
+  if (nchains) *nchains = int32_t(chains);
   return TGP_OK;
 }
 

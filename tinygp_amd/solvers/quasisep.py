@@ -8,7 +8,8 @@ factorisation, both triangular solves and ``L @ z`` are chunked reduce-then-scan
 nothing of size N x M), the same for every term of a sum at once (``predict_terms``; also at the data themselves),
 the gradient of the log-probability (``value_and_grad``; O(N) per parameter) and the log-probabilities of many
 hyper-parameter sets over the one series in one launch chain (``log_probability_batch``; with their gradients:
-``value_and_grad_batch``).  Nothing
+``value_and_grad_batch``).  :class:`QuasisepSeriesSet` evaluates many series, each on coordinates of its own, in one
+launch chain (``tgp_qsep_series_logprob``).  Nothing
 of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
 reference); the full conditional covariance and conditioning on another kernel keep the reference's dense route.
 
@@ -30,7 +31,7 @@ from tinygp_amd import _device, _ffi
 from tinygp_amd.noise import Diagonal, Noise
 from tinygp_amd.solvers.solver import Solver
 
-__all__ = ["QuasisepSolver"]
+__all__ = ["QuasisepSolver", "QuasisepSeriesSet"]
 
 
 def _check_sorted(t):
@@ -439,3 +440,139 @@ class QuasisepSolver(Solver):
             self.close()
         except Exception:
             pass
+
+
+def check_series(Xs, assume_sorted: bool = False):
+    """The coordinates of a set of series as float64 vectors: each (N_b,) or (N_b, 1) with N_b >= 1 and, unless
+    ``assume_sorted``, sorted; a ``ValueError`` names the member that is not."""
+    from tinygp_amd.kernels.quasisep import _coords
+
+    ts = []
+    for b, X in enumerate(Xs):
+        try:
+            t = _coords(X)
+        except ValueError as e:
+            raise ValueError(f"series {b}: {e}") from e
+        if t.shape[0] == 0:
+            raise ValueError(f"series {b} is empty: every series needs at least one data point")
+        if not assume_sorted and np.any(np.diff(t) < 0):
+            raise ValueError(f"series {b}: input coordinates must be sorted in order to use the QuasisepSeriesSet")
+        ts.append(_f64(t))
+    if not ts:
+        raise ValueError("a set of series needs at least one series")
+    return ts
+
+
+def pack_series(lengths, kernels, ys, diags, means=None):
+    """The host arrays of ``tgp_qsep_series_logprob`` for series of the given lengths: ``(leaves, state_map, h, Pinf,
+    noise, resid)``, the models stacked as by :func:`tinygp_amd.kernels.quasisep.pack_batch` (one shared kernel is
+    lowered once and repeated), noise and residual concatenated.  A wrong count or length raises ``ValueError`` naming
+    the member."""
+    from tinygp_amd.kernels.quasisep import Quasisep, pack_batch
+
+    lengths = np.asarray(lengths, dtype=np.int64)
+    nb = len(lengths)
+    offsets = np.concatenate([[0], np.cumsum(lengths)])
+    if isinstance(kernels, Quasisep):
+        leaves, smap, h, P = pack_batch([kernels])
+        leaves, h, P = (np.ascontiguousarray(np.repeat(a, nb, axis=0)) for a in (leaves, h, P))
+    else:
+        kernels = list(kernels)
+        if len(kernels) != nb:
+            raise ValueError(f"kernels must be one kernel or one per series ({nb}); got {len(kernels)}")
+        leaves, smap, h, P = pack_batch(kernels)
+
+    def concat(values, what, scalars_ok):
+        values = list(values)
+        if len(values) != nb:
+            raise ValueError(f"{what} must hold one entry per series ({nb}); got {len(values)}")
+        out = np.empty(offsets[-1])
+        for b, v in enumerate(values):
+            v = np.asarray(v)
+            if v.ndim == 2 and v.shape[1] == 1:
+                v = v[:, 0]
+            if not (v.shape == (lengths[b],) or (scalars_ok and v.shape == ())):
+                raise ValueError(f"{what}[{b}] must have shape ({lengths[b]},)" + (" or be a scalar" if scalars_ok else "")
+                                 + f" for series {b}; got {v.shape}")
+            out[offsets[b]:offsets[b + 1]] = v
+        return out
+
+    resid = concat(ys, "ys", False)
+    if means is not None:
+        resid -= concat(means, "means", True)
+    return leaves, smap, h, P, concat(diags, "diags", True), resid
+
+
+class QuasisepSeriesSet:
+    """B series on coordinates of their own -- the light curves of a survey, each with its gaps, masks and length --
+    evaluated together on the device: one series per grid row of every kernel (``tgp_qsep_series_logprob``), where a
+    loop over :class:`QuasisepSolver` pays a handle and a launch chain per series and fills the card with none of them.
+
+    Args:
+        Xs: a sequence of B sorted coordinate arrays, each of shape (N_b,) or (N_b, 1) with N_b >= 1; the lengths may
+            differ freely.
+        assume_sorted: skip the host check that every member is sorted.
+        ctx: optional :class:`tinygp_amd._ffi.Ctx`.
+
+    The handle keeps the concatenated coordinates and the table of the series' extents resident; :meth:`close` frees it.
+    """
+
+    def __init__(self, Xs, *, assume_sorted: bool = False, ctx=None):
+        self._handle = None
+        ts = check_series(Xs, assume_sorted)
+        self.lengths = np.array([len(t) for t in ts], dtype=np.int64)
+        self._offsets = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        self._t = np.concatenate(ts)
+        self._ctx = _ffi.default_ctx() if ctx is None else ctx
+        h = C.c_void_p()
+        _ffi.check(_ffi.lib().tgp_qsep_series_create(self._ctx.handle, len(ts), _ffi.ptr(self._offsets),
+                                                     _ffi.ptr(self._t), C.byref(h)), "tgp_qsep_series_create")
+        self._handle = h
+
+    def __len__(self):
+        return len(self.lengths)
+
+    def log_probability(self, kernels, ys, diags, *, means=None, return_info: bool = False):
+        """The log-probabilities of the B series, float64, shape (B,).
+
+        ``kernels``: one :class:`~tinygp_amd.kernels.quasisep.Quasisep` kernel shared by all series, or B of one
+        structure (:func:`tinygp_amd.kernels.quasisep.pack_batch`).  ``ys``: B arrays, (N_b,) each.  ``diags``: B
+        noise diagonals, each (N_b,) or a scalar.  ``means``: ``None``, or B means, each a scalar or (N_b,).  Member b
+        has the bits of ``QuasisepSolver(kernels[b], Xs[b], Diagonal(diags[b])).log_probability(ys[b] - means[b])``
+        on a fresh solver, whatever B, its position and the other members' lengths; a failed or non-finite member
+        gives ``-inf`` and touches no other.  With ``return_info`` also the B ``info`` values (0, or the 1-based step
+        of the first non-positive pivot within that series)."""
+        if self._handle is None:
+            raise ValueError("this QuasisepSeriesSet has been closed")
+        leaves, smap, h, P, noise, resid = pack_series(self.lengths, kernels, ys, diags, means)
+        nb = len(self)
+        info, out = np.zeros(nb, dtype=np.int32), np.empty(nb)
+        _ffi.check(_ffi.lib().tgp_qsep_series_logprob(self._handle, _ffi.ptr(leaves), leaves.shape[1], _ffi.ptr(smap),
+                                                      h.shape[1], _ffi.ptr(h), _ffi.ptr(P), _ffi.ptr(noise),
+                                                      _ffi.ptr(resid), _ffi.ptr(info), _ffi.ptr(out), None),
+                   "tgp_qsep_series_logprob")
+        out[(info != 0) | ~np.isfinite(out)] = -np.inf
+        return (out, info) if return_info else out
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            _ffi.lib().tgp_qsep_series_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def log_probability_series(kernels, Xs, ys, *, diags, means=None):
+    """The log-probabilities of B series, each on coordinates of its own, under quasiseparable GPs: builds a
+    :class:`QuasisepSeriesSet` on ``Xs``, evaluates it and closes it.  Member b equals
+    ``GaussianProcess(kernels[b], Xs[b], diag=diags[b], mean=means[b]).log_probability(ys[b])`` for float64 inputs.
+    Arguments as in :meth:`QuasisepSeriesSet.log_probability`; keep the set yourself to evaluate it more than once."""
+    series = QuasisepSeriesSet(Xs)
+    try:
+        return series.log_probability(kernels, ys, diags, means=means)
+    finally:
+        series.close()
