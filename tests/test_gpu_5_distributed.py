@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import _cases
+import _dense_grad_np as dg
 from oracle import tinygp_np as o
 
 pytestmark = pytest.mark.gpu
@@ -262,6 +263,35 @@ def test_gradient_on_the_block_column_path_hip(pg, n, nb, chunk):
     np.testing.assert_allclose(got, want_g, rtol=2e-6, atol=2e-6 * scale)
     np.testing.assert_allclose(g["noise_diag"], want_noise, rtol=1e-6, atol=1e-6 * np.abs(want_noise).max())
     np.testing.assert_allclose(g["mean"], want_alpha, rtol=1e-7, atol=1e-7 * np.abs(want_alpha).max())
+    s.ops.close()
+
+
+@pytest.mark.parametrize("name,n,nb,chunk", dg.BLOCK_COLUMN_CASES, ids=lambda v: str(v))
+def test_gradient_on_the_block_column_path_with_every_tile_weighted_hip(pg, name, n, nb, chunk):
+    """The same route on the box inputs of tests/_dense_grad_np.py, where every 128 x 128 tile of every chunk of K^-1
+    enters every parameter's sum with at least 100 bars of weight (asserted on the reference), against the exact
+    reference (LAPACK's K^-1, analytic dK/dtheta) at the same bars: N = 1 100 in block columns of 256 and chunks of
+    384 (a chunk boundary inside a block column, a ragged last chunk), N = 2 176 in block columns and chunks of 512
+    (17 tiles: a last block column of one tile)."""
+    from tinygp_amd import kernels
+    from tinygp_amd.distributed import BlockCyclicCholesky
+
+    X, diag, y = dg.inputs(n, dg.PROGRAMS[name][0])
+    ref = dg.reference(name, n)
+    kern = dg.kernel(name, kernels)
+    s = BlockCyclicCholesky(kern, X, diag, nb=nb, dist=pg)
+    s.GRAD_CHUNK = chunk
+    ll, g = s.log_probability_and_grad(y)
+    assert s.info == 0 and np.isfinite(ll)
+    flat = np.array(g["kernel"])  # 2 per op of the postfix program; a leaf's parameters are its p0, p1
+    slots: list = []
+    kern._slots(slots)
+    assert len(flat) == 2 * len(slots)
+    got = [flat[2 * i + q] for i, pair in enumerate(slots) for q in (0, 1) if pair[q] is not None]
+    assert len(got) == dg.N_KERNEL[name]
+    worst = dg.errors(ref, ll, got, g["noise_diag"], g["mean"])
+    print(f"{name} N={n} nb={nb} chunk={chunk}: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()) + " of the bar")
+    dg.check(ref, ll, got, g["noise_diag"], g["mean"])
     s.ops.close()
 
 
