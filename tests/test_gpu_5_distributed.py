@@ -123,6 +123,42 @@ def test_block_cyclic_bad_pivot_and_determinism(pg):
     assert np.all(np.isnan(s.condition_mean(y, X[:4])))
 
 
+@pytest.mark.parametrize("half", [0, 1], ids=["up_to_the_second_block", "past_it"])
+@pytest.mark.parametrize("nb", [128, 512])
+def test_block_cyclic_pivot_position_at_block_edges(pg, nb, half):
+    """The block-column driver's pivot_off: a bad noise entry (tests/_dense_failure.py: every earlier pivot >= 0.5,
+    this one < -7, so info = p + 1 whatever the rounding) in the first and last column of a block column, one past it,
+    two blocks in, and in the last real row of a ragged N -- and a solver built behind the failures on the same
+    process group returns the bits of one built before them.  (Two cases per width: every solver here brings up a
+    context and a communicator of its own, most of a second each.)"""
+    import _dense_failure as df
+    from tinygp_amd import kernels
+    from tinygp_amd.distributed import BlockCyclicCholesky
+
+    n = df.DIST_N
+    assert n % nb
+    X, y = df.inputs(n)
+    xt = np.linspace(X[0], X[-1], 11)
+
+    def good():
+        s = BlockCyclicCholesky(df.kernel(kernels), X, np.full(n, df.DIAG), nb=nb, dist=pg)
+        out = np.asarray(s.log_probability(y)), s.condition_mean(y, xt)
+        assert s.info == 0 and np.isfinite(out[0]) and np.all(np.isfinite(out[1]))
+        s.ops.close()
+        return out
+
+    before = good()
+    for p in df.dist_positions(nb)[3 * half:3 * half + 3]:
+        s = BlockCyclicCholesky(df.kernel(kernels), X, df.bad_noise(n, p), nb=nb, dist=pg)
+        assert s.log_probability(y) == -np.inf
+        assert s.info == p + 1, (p, s.info)
+        assert np.all(np.isnan(s.condition_mean(y, xt)))
+        s.ops.close()
+    after = good()
+    np.testing.assert_array_equal(after[0], before[0])
+    np.testing.assert_array_equal(after[1], before[1])
+
+
 def test_block_cyclic_matches_single_gpu_driver_n16384(pg):
     """Same inputs through both drivers: the block-column path (nb = 1024, RCCL self-broadcast)
     and the single-GPU fused path agree to 1e-10 relative at BASELINE config 2's size."""
