@@ -167,6 +167,14 @@ int tgp_ctx_sync(tgp_ctx* ctx);
  *                       deadline has passed at once
  *   "kmat_plain_div"    1: the straight-line assembly kernel takes r / l, r^2 / l^2 by the division sequence instead
  *                       of the bit-identical reciprocal + FMA form (kmat.hip, UDiv) -- the tests' switch
+ *   "gemm_role"         role tgp_gemm_nt launches its product with (default 1: the in-panel update, 64 x 64 tiles up to k = 256;
+ *                       0: the trailing update on 128 x 128 tiles; 4: 64 x 64 tiles at any k; 3 / 5: 64 x 64 tiles without the
+ *                       first 128 x 128 diagonal block) -- a switch for tests and measurements.  With role 0, two more:
+ *                       "gemm_reserve" (0): workgroup slots that launch leaves free, as potrf's "chain_reserve" does for a
+ *                       trailing update -- the grid is then smaller than the tile count and a workgroup walks several tiles;
+ *                       "gemm_prefix_cols" (0): the first so many columns of a lower square update with k >= 128 (a multiple
+ *                       of 128, fewer than n) are its write-through, counted prefix; nothing polls the counter, the call
+ *                       joins the stream and "gemm_prefix_count" (read-only) then holds the prefix tiles that launch counted
  *   "chain_reserve"     workgroup slots (of two per CU) that a trailing update running beside a panel
  *                       chain leaves to the chain's kernels (default 96; 0: the update fills the chip)
  *   "reserve_max_tiles" ... when the update has at most this many 128x128 tiles (default 1200)

@@ -85,6 +85,46 @@ def gemm_nt(A, B, Cm, alpha, beta, lower=False):
         ctx.free(dA), ctx.free(dB), ctx.free(dC)
 
 
+def gemm_nt_ld(A, B, C0, m, n, k, mode, lower, options=None, repeat=1, read=()):
+    """tgp_gemm_nt on column-major buffers with their own leading dimensions: A (lda, k), B (ldb, k), C0 (ldc, n), of which the
+    call uses the first m / n / m rows.  mode 0: C -= A B^T, 1: C = A B^T.  `options` hold for the call and are restored.
+    The call is made `repeat` times, each on a fresh upload of C0; returns one (C, values, error) per call: the WHOLE (ldc, n)
+    buffer, padding rows included, the context options named in `read` behind the call, and the ValueError of a rejected
+    argument (None otherwise)."""
+    ctx = _ffi.default_ctx()
+    dt = C0.dtype
+    lda, ldb, ldc = A.shape[0], B.shape[0], C0.shape[0]
+    assert A.shape[1] == k and B.shape[1] == k and C0.shape[1] == n and lda >= m and ldb >= n and ldc >= m
+    alpha, beta = ((-1.0, 1.0), (1.0, 0.0))[mode]
+    flat = _f(C0, dt).ravel(order="K")
+    old, dev, out = {}, [], []
+    try:
+        for key, v in (options or {}).items():
+            old[key] = ctx.set_option(key, v)
+        dev.append(ctx.upload(_f(A, dt).ravel(order="K")))
+        dev.append(ctx.upload(_f(B, dt).ravel(order="K")))
+        dev.append(ctx.upload(flat))
+        dA, dB, dC = dev
+        for rep in range(repeat):
+            if rep:
+                _ffi.check(_ffi.lib().tgp_memcpy_h2d(ctx.handle, C.c_void_p(dC), flat.ctypes.data_as(C.c_void_p), flat.nbytes),
+                           "tgp_memcpy_h2d")
+            err = None
+            try:
+                _ffi.check(_ffi.lib().tgp_gemm_nt(ctx.handle, _ffi.dtype_code(dt), m, n, k, alpha, C.c_void_p(dA), lda,
+                                                  C.c_void_p(dB), ldb, beta, C.c_void_p(dC), ldc, int(lower)), "tgp_gemm_nt")
+            except ValueError as e:
+                err = e
+            got = ctx.download(dC, (n, ldc), dt).T
+            out.append((got, {key: ctx.get_option(key) for key in read}, err))
+    finally:
+        for p in dev:
+            ctx.free(p)
+        for key, v in old.items():
+            ctx.set_option(key, v)
+    return out
+
+
 def ubench(dtype):
     ctx = _ffi.default_ctx()
     out = C.c_double()

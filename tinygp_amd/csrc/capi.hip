@@ -272,6 +272,7 @@ int tgp_ctx_destroy(tgp_ctx* ctx) {
   if (ctx->d_dinv) hipFree(ctx->d_dinv);
   if (ctx->d_work) hipFree(ctx->d_work);
   if (ctx->d_gemm_ws) hipFree(ctx->d_gemm_ws);
+  if (ctx->d_gemm_prefix_count) hipFree(ctx->d_gemm_prefix_count);
   if (ctx->panel_stream) hipStreamDestroy(ctx->panel_stream);
   if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -325,6 +326,9 @@ static int64_t* option_slot(tgp_ctx* ctx, const char* key) {
   if (!strcmp(key, "nb_first")) return &ctx->nb_first;
   if (!strcmp(key, "split_tail")) return &ctx->split_tail;
   if (!strcmp(key, "gemm_role")) return &ctx->gemm_role;
+  if (!strcmp(key, "gemm_reserve")) return &ctx->gemm_reserve;
+  if (!strcmp(key, "gemm_prefix_cols")) return &ctx->gemm_prefix_cols;
+  if (!strcmp(key, "gemm_prefix_count")) return &ctx->gemm_prefix_count;  // (read: prefix tiles counted by the last such call)
   if (!strcmp(key, "host_join")) return &ctx->host_join;
   if (!strcmp(key, "late_join")) return &ctx->late_join;
   if (!strcmp(key, "chain_reduce")) return &ctx->chain_reduce;
@@ -536,11 +540,31 @@ int tgp_gemm_nt(tgp_ctx* ctx, int dtype, int64_t m, int64_t n, int64_t k, double
     set_error("gemm_nt: (alpha, beta) must be (-1, 1) or (1, 0)");
     return TGP_E_UNSUPPORTED;
   }
-  return dispatch(dtype, [&](auto tag) {
+  // test hooks (role 0 only): the reserve and the prefix that potrf alone sets otherwise; launch_gemm_nt consumes the hints
+  // and judges what a prefix may be
+  const bool counted = ctx->gemm_role == 0 && ctx->gemm_prefix_cols > 0;
+  if (ctx->gemm_role == 0) ctx->reserve_hint = ctx->gemm_reserve;
+  if (counted) {
+    if (!ctx->d_gemm_prefix_count) TGP_HIP_TRY(hipMalloc(&ctx->d_gemm_prefix_count, sizeof(int32_t)));
+    TGP_HIP_TRY(hipMemsetAsync(ctx->d_gemm_prefix_count, 0, sizeof(int32_t), ctx->stream));
+    ctx->prefix_hint_cols = ctx->gemm_prefix_cols;
+    ctx->prefix_hint_counter = ctx->d_gemm_prefix_count;
+  }
+  const int rc = dispatch(dtype, [&](auto tag) {
     using T = decltype(tag);
     return launch_gemm_nt<T>(ctx, ctx->stream, m, n, k, (const T*)A, lda, (const T*)B, ldb, (T*)C,
                              ldc, lower, mode, (int)ctx->gemm_role);
   });
+  ctx->reserve_hint = 0;  // (an argument error leaves the launcher before it has consumed them)
+  ctx->prefix_hint_cols = 0;
+  ctx->prefix_hint_counter = nullptr;
+  if (counted && rc == TGP_OK) {  // nothing polls the counter: it is read behind the whole launch
+    int32_t done = 0;
+    TGP_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    TGP_HIP_TRY(hipMemcpy(&done, ctx->d_gemm_prefix_count, sizeof(int32_t), hipMemcpyDeviceToHost));
+    ctx->gemm_prefix_count = done;
+  }
+  return rc;
 }
 
 int tgp_sum_log_diag(tgp_ctx* ctx, int dtype, int64_t n, const void* L, int64_t ld, double* out) {

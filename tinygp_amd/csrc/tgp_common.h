@@ -128,6 +128,12 @@ struct tgp_ctx {
   int64_t nb_first = 0;    // width of the FIRST panel, whose chain nothing hides (0: nb_outer)
   int64_t split_tail = 0;  // trailing update: the last, partly filled round of tiles is split along k (gemm.hip)
   int64_t gemm_role = 1;     // role tgp_gemm_nt launches with (measurement hook: 4 = the 64x64-tile kernel at any k)
+  // tests and measurements (capi.hip, tgp_gemm_nt with gemm_role 0): workgroup slots that launch leaves free (the persistent
+  // loop), and the columns of a counted write-through prefix; the count of the last such call is read as "gemm_prefix_count"
+  int64_t gemm_reserve = 0;
+  int64_t gemm_prefix_cols = 0;
+  int64_t gemm_prefix_count = 0;
+  int32_t* d_gemm_prefix_count = nullptr;  // allocated on first use
   int64_t late_join = 1;       // fused evaluation: ONE host join per evaluation, `info` read with the scalars (0: round 5's two)
   // fused evaluation: sum z^2 and sum log L_ii are left by the chain's fsolve tasks (chol.hip, ChainArgs::red) -- no reduction
   // launch behind the factorisation (0: the two kernels of util.hip)
