@@ -694,11 +694,32 @@ int tgp_qsep_series_destroy(tgp_qsep_series* set);
  * upload each of the models, the noise and the residual, one download, one stream synchronisation) holds at most 64
  * series and at most 1 GiB of device scratch, the sum of what its own members need; chains are filled in the order
  * given ("Batches of series", states the layout and the rule), and *nchains (may be NULL) reports how
- * many ran.  The table is re-cut and uploaded when J differs from the previous call's.  A series that exceeds the cap
- * alone is an argument error, raised before anything is allocated. */
+ * many ran.  The table is re-cut and uploaded when what it was cut for (the call, J) differs from the previous
+ * call's.  A series that exceeds the cap alone is an argument error, raised before anything is allocated. */
 int tgp_qsep_series_logprob(tgp_qsep_series* set, const double* leaves, int32_t nleaves, const int32_t* state_map,
                             int32_t J, const double* hvec, const double* Pinf, const double* noise_concat,
                             const double* resid_concat, int32_t* info, double* out, int32_t* nchains);
+/* Value and gradient (as tgp_qsep_grad) of every series of the set under a model of its own, evaluated together.
+ * Models, noise_concat and resid_concat as in tgp_qsep_series_logprob; directions stacked per member as
+ * tgp_qsep_grad_batch takes them, every member with ndir of them.  info (nseries), out (nseries), dout (nseries x ndir),
+ * gnoise_concat and alpha_concat (laid out as t_concat; either may be NULL and its scan is then skipped): per series.
+ * ndir = 0 with both vectors NULL is the value alone.  A series' value, every dout entry, its slice of the noise
+ * gradient and of alpha have the bits of tgp_qsep_grad on a handle created on that series alone, whatever nseries, its
+ * position, the other series' lengths, the split into chains and passes, and which vectors were asked for.  A
+ * non-positive pivot sets that series' info to its 1-based step within the series and all of its outputs to NaN and
+ * changes no other series by a bit.  A launch chain (one stream synchronisation, at its end) holds at most 64 series, a
+ * direction pass inside it at most 8 directions per member, and the chain's device scratch stays under 1 GiB: chains
+ * are filled in the order given while every member fits with one direction, then the chain takes as many directions
+ * per pass as the rest holds ("Batches of series: value and gradient", states the layout and the
+ * rule).  *nchains and *npasses (may be NULL) report the chains and the direction passes (summed over the chains) that
+ * ran.  The resident table is re-cut and uploaded whenever the call (this one or tgp_qsep_series_logprob), J, ndir or
+ * the wish for vectors differs from the previous call's.  Argument errors: null arrays, ndir < 0, and a series that
+ * exceeds the cap alone with one direction, raised before anything is allocated. */
+int tgp_qsep_series_grad(tgp_qsep_series* set, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                         int32_t J, const double* hvec, const double* Pinf, const double* noise_concat,
+                         const double* resid_concat, int32_t ndir, const double* dleaves, const double* dh,
+                         const double* dPinf, int32_t* info, double* out, double* dout, double* gnoise_concat,
+                         double* alpha_concat, int32_t* nchains, int32_t* npasses);
 
 #ifdef __cplusplus
 }

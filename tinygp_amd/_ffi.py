@@ -170,6 +170,8 @@ SIGNATURES = {
     "tgp_qsep_series_create": [_vp, _i32, _vp, _vp, _pvp],
     "tgp_qsep_series_destroy": [_vp],
     "tgp_qsep_series_logprob": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _pi32],
+    "tgp_qsep_series_grad": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _pi32, _pi32],
 }
 
 

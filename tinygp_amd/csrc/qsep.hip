@@ -32,6 +32,7 @@
 // has the bits of its single call.  The gradient's kernels take the same member axis (see "gradient" below).
 // Sets of series: the same kernels, instantiated over an extent policy ("extents" below), serve members that each have
 // a series of their own -- their own slice of t, length, chunk length, chunk count and scan depth -- from a device table.
+// The gradient's kernels take the same two kinds of extent, so a set of series has value and gradient in one launch chain.
 #include "tgp_common.h"
 
 #include <algorithm>
@@ -301,6 +302,8 @@ struct QExtent {
   int64_t n, lc, nchunks;
   int64_t lev[MAXLEV + 1];  // its scan's level sizes, continued with 1 beyond its own depth
   int64_t work, chunks;     // offsets of its scan work space and of its per-chunk sums and bad-pivot slots
+  int64_t keep, twork;      // gradient: offsets of its kept chunk prefixes and, per direction of a pass, of the tangent
+                            // scans' work space (a pass of d directions puts the member d twork doubles in)
 };
 
 struct Member {
@@ -326,6 +329,39 @@ struct TableExtent {
     const QExtent& x = tab[mem];
     return {x.n, x.lc, x.nchunks, x.off, x.off, x.off, x.off, x.work, x.work + x.nchunks * eblocks * WAVE, x.chunks,
             x.chunks};
+  }
+};
+
+// The gradient's kernels resolve their member through a policy of the same two kinds (UniformGExtent / TableGExtent),
+// called with the directions of the pass (nd; 0: a kernel without directions, which works in the primal work space) and
+// the lane-blocks of level-0 elements per chunk and direction that precede the chunk prefixes.
+// Layout of dc, dw and the per-chunk tangent sums, for kernels and host alike: with nd directions in the pass, a
+// member's part starts at nd x (its slice offset) -- GMember::tan for dc (dw: J times that), nd x (its chunk offset),
+// GMember::sums, for the sums -- and its directions lie n (dw: n J; sums: nchunks) apart.  Uniform members have the
+// slice offset member x n, so direction d of member b is row b nd + d of an (members nd) x n array.
+struct GMember {
+  int64_t n, lc, nchunks;
+  int64_t t, noise, y, fac;  // as Member
+  int64_t keep;              // the primal scans' kept chunk prefixes: filtered covariances, then (nchunks x WAVE on) solve states
+  int64_t work, pre;         // the scan work space of this pass and its chunk prefixes
+  int64_t tan, sums;
+};
+
+struct UniformGExtent {  // keep, work space, noise and residual one stride per member apart; the prefix pointer is member 0's
+  int64_t n, lc, nchunks, noise_stride, y_stride, keep_stride, work_stride;
+  __device__ __forceinline__ GMember operator()(int64_t mem, int64_t nd, int64_t eblocks) const {
+    return {n, lc, nchunks, 0, mem * noise_stride, mem * y_stride, mem * n, mem * keep_stride, mem * work_stride,
+            mem * work_stride, nd * mem * n, nd * mem * nchunks};
+  }
+};
+
+struct TableGExtent {  // the pointers are the bases of the chain's arrays
+  const QExtent* tab;
+  __device__ __forceinline__ GMember operator()(int64_t mem, int64_t nd, int64_t eblocks) const {
+    const QExtent& x = tab[mem];
+    const int64_t work = nd ? x.twork * nd : x.work, width = nd ? nd : 1;
+    return {x.n, x.lc, x.nchunks, x.off, x.off, x.off, x.off, x.keep, work, work + x.nchunks * width * eblocks * WAVE,
+            nd * x.off, nd * x.chunks};
   }
 };
 
@@ -502,13 +538,15 @@ struct UniformLevel {  // the pointers are member 0's, member b's work_stride do
 struct TableLevel {  // level `level` of every member's own scan; the pointers are the base of the work space
   const QExtent* tab;
   int32_t level;
+  int32_t tangent;  // the scans of a direction pass: the member's work space lies width x twork in, not at work
   template <class S>
   __device__ __forceinline__ Level at(int64_t mem, int64_t width) const {
     const QExtent& x = tab[mem];
+    const int64_t w = tangent ? x.twork * width : x.work;
     int64_t el, pre, el_up, pre_up;
     level_offsets<S>(x.lev, level, width, &el, &pre);
     level_offsets<S>(x.lev, level + 1, width, &el_up, &pre_up);
-    return {x.lev[level], x.lev[level + 1], x.work + el, x.work + el_up, x.work + pre_up, x.work + pre};
+    return {x.lev[level], x.lev[level + 1], w + el, w + el_up, w + pre_up, w + pre};
   }
 };
 
@@ -807,20 +845,22 @@ __device__ __forceinline__ double lin(int dir, double A, double X, int J, int r,
   return dir == 0 ? mm(A, X, J, r, c) : mm_tn(A, X, J, r, c);
 }
 
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_pred_fold(int dir, int want_mean, int want_var,
                                                            const QModel* __restrict__ mp, const double* __restrict__ t,
                                                            const double* __restrict__ cbuf,
                                                            const double* __restrict__ wbuf,
-                                                           const double* __restrict__ alpha, int64_t n, int64_t lc,
-                                                           int64_t nchunks, double* __restrict__ elem,
-                                                           int64_t work_stride) {
+                                                           const double* __restrict__ alpha, E ext,
+                                                           double* __restrict__ elem) {
   const Lane L;
-  if (L.wave >= nchunks) return;
-  const int64_t mem = blockIdx.y;  // member: c, w and alpha as in qs_aff_emit, elements work_stride apart
+  const int64_t mem = blockIdx.y;  // member: c, w and alpha as in qs_aff_emit, elements in its (primal) work space
+  const GMember G = ext(mem, 0, 0);
+  if (L.wave >= G.nchunks) return;
+  const int64_t n = G.n, lc = G.lc, nchunks = G.nchunks;
   const QModel& m = mp[mem];
   const int J = m.J, r = L.r, c = L.c;
-  cbuf += mem * n, wbuf += mem * n * J, elem += mem * work_stride;
-  if (alpha) alpha += mem * n;
+  t += G.t, cbuf += G.fac, wbuf += G.fac * J, elem += G.work;
+  if (alpha) alpha += G.fac;
   const double Ph_r = Xh(m, m.P[L.lane], r);
   const double I = (r == c && r < J) ? 1.0 : 0.0;
   double M = I, V = 0.0, Mf = I, Vf = 0.0;
@@ -960,10 +1000,11 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_pred_emit(int dir, int want_mea
 // direction) and a per-chunk sum of dc_n / c_n; the solve pass, which needs them, a per-chunk sum of z_n dz_n:
 //   d log p = -1/2 sum dc_n / c_n - sum z_n dz_n.
 // Scan elements are (M, V), `ndir` independent scans interleaved as element * ndir + direction.
-// Batches of models: member blockIdx.z (qs_pred_fold and qs_invdiag_emit, which have no direction: blockIdx.y) with
-// model mp[member] and directions dirs[member * ndir + direction].  Noise, residual, kept prefixes and scan work space
-// lie one stride per member apart (0: shared); c, w, alpha and the noise gradient n (n J) apart as in qs_emit; dc, dw
-// and the per-chunk sums are indexed by member * ndir + direction.  The single call is member 0 of one.
+// Batches of models and sets of series: member blockIdx.z (qs_pred_fold and qs_invdiag_emit, which have no direction:
+// blockIdx.y) with model mp[member] and directions dirs[member * ndir + direction]; where the member's arrays lie is
+// the gradient extent policy's answer ("extents" above, which also states the layout of dc, dw and the per-chunk sums).
+// Uniform: noise, residual, kept prefixes and scan work space lie one stride per member apart (0: shared); c, w, alpha
+// and the noise gradient n (n J) apart as in qs_emit.  The single call is member 0 of one.
 struct GStep {
   double Phi, cv, dc, w, dw;  // w, dw: by row
 };
@@ -992,18 +1033,21 @@ __device__ __forceinline__ GStep gfac_step(const QModel& m, const QDir& d, const
   return s;
 }
 
+// keep: the base of the kept prefixes (GMember::keep)
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_gfac_fold(const QModel* __restrict__ mp,
                                                            const QDir* __restrict__ dirs, const double* __restrict__ t,
-                                                           const double* __restrict__ noise, int64_t noise_stride,
-                                                           int64_t n, int64_t lc, int64_t nchunks,
-                                                           const double* __restrict__ prefixP, int64_t keep_stride,
-                                                           double* __restrict__ elem, int64_t work_stride) {
+                                                           const double* __restrict__ noise, E ext,
+                                                           const double* __restrict__ keep, double* __restrict__ elem) {
   const Lane L;
-  if (L.wave >= nchunks) return;
   const int64_t mem = blockIdx.z;
+  const GMember G = ext(mem, gridDim.y, 0);
+  if (L.wave >= G.nchunks) return;
+  const int64_t n = G.n, lc = G.lc;
   const QModel& m = mp[mem];
   const QDir& d = dirs[mem * gridDim.y + blockIdx.y];
-  noise += mem * noise_stride, prefixP += mem * keep_stride, elem += mem * work_stride;
+  const double* prefixP = keep + G.keep;
+  t += G.t, noise += G.noise, elem += G.work;
   const int J = m.J, r = L.r, c = L.c;
   const double Pinf = m.P[L.lane], dPinf = d.dP[L.lane];
   double P = prefixP[L.wave * WAVE + L.lane], V = 0.0, M = (r == c && r < J) ? 1.0 : 0.0;
@@ -1017,21 +1061,25 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_gfac_fold(const QModel* __restr
   e[L.lane] = M, e[WAVE + L.lane] = V;
 }
 
-// dcbuf: members x ndir x n, dwbuf: members x ndir x n x J, dsum: members x ndir x nchunks
+// dcbuf, dwbuf, dsum: laid out as "extents" states (uniform: members x ndir x n, x n x J, x nchunks)
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_gfac_emit(const QModel* __restrict__ mp,
                                                            const QDir* __restrict__ dirs, const double* __restrict__ t,
-                                                           const double* __restrict__ noise, int64_t noise_stride,
-                                                           int64_t n, int64_t lc, int64_t nchunks,
-                                                           const double* __restrict__ prefixP, int64_t keep_stride,
-                                                           const double* __restrict__ prefixD, int64_t work_stride,
+                                                           const double* __restrict__ noise, E ext,
+                                                           const double* __restrict__ keep,
+                                                           const double* __restrict__ prefixD,
                                                            double* __restrict__ dcbuf, double* __restrict__ dwbuf,
                                                            double* __restrict__ dsum) {
   const Lane L;
-  if (L.wave >= nchunks) return;
-  const int64_t mem = blockIdx.z, dir = mem * gridDim.y + blockIdx.y;
+  const int64_t mem = blockIdx.z;
+  const GMember G = ext(mem, gridDim.y, ScanCong::ESZ);
+  if (L.wave >= G.nchunks) return;
+  const int64_t n = G.n, lc = G.lc;
   const QModel& m = mp[mem];
-  const QDir& d = dirs[dir];
-  noise += mem * noise_stride, prefixP += mem * keep_stride, prefixD += mem * work_stride;
+  const QDir& d = dirs[mem * gridDim.y + blockIdx.y];
+  const double* prefixP = keep + G.keep;
+  t += G.t, noise += G.noise, prefixD += G.pre;
+  const int64_t row = G.tan + blockIdx.y * n;  // of this direction's dc (dw: J times that)
   const int J = m.J, r = L.r, c = L.c;
   const double Pinf = m.P[L.lane], dPinf = d.dP[L.lane];
   double P = prefixP[L.wave * WAVE + L.lane], acc = 0.0;
@@ -1039,11 +1087,11 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_gfac_emit(const QModel* __restr
   const int64_t n0 = L.wave * lc, n1 = min(n, n0 + lc);
   for (int64_t i = n0; i < n1; ++i) {
     const GStep s = gfac_step(m, d, t, noise, i, Pinf, dPinf, P, dD, r, c);
-    if (L.lane == 0) dcbuf[dir * n + i] = s.dc;
-    if (c == 0 && r < J) dwbuf[(dir * n + i) * J + r] = s.dw;
+    if (L.lane == 0) dcbuf[row + i] = s.dc;
+    if (c == 0 && r < J) dwbuf[(row + i) * J + r] = s.dw;
     acc += s.dc / s.cv;
   }
-  if (L.lane == 0) dsum[dir * nchunks + L.wave] = acc;
+  if (L.lane == 0) dsum[G.sums + blockIdx.y * G.nchunks + L.wave] = acc;
 }
 
 // one step of L^-1 y (one column) and of its tangent; s, ds: the state by row, in and out; returns z dz
@@ -1067,24 +1115,28 @@ __device__ __forceinline__ double gsol_step(const QModel& m, const QDir& d, doub
   return z * dz;
 }
 
-// fold (prefixS only) or emit (prefixT too) of the solve's tangent; prefixS: the primal scan's chunk states (column 0).
-// elem and prefixT share the scan's work space, hence its stride.
+// fold (elem) or emit (prefixT) of the solve's tangent; the primal scan's chunk states (column 0) come from the kept
+// prefixes.  elem and prefixT lie in the scan's work space.
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_gsol(const QModel* __restrict__ mp, const QDir* __restrict__ dirs,
                                                       const double* __restrict__ t, const double* __restrict__ cbuf,
                                                       const double* __restrict__ wbuf, const double* __restrict__ dcbuf,
                                                       const double* __restrict__ dwbuf, const double* __restrict__ y,
-                                                      int64_t y_stride, int64_t n, int64_t lc, int64_t nchunks,
-                                                      const double* __restrict__ prefixS, int64_t keep_stride,
+                                                      E ext, const double* __restrict__ keep,
                                                       const double* __restrict__ prefixT, double* __restrict__ elem,
-                                                      int64_t work_stride, double* __restrict__ dsum) {
+                                                      double* __restrict__ dsum) {
   const Lane L;
-  if (L.wave >= nchunks) return;
-  const int64_t mem = blockIdx.z, dir = mem * gridDim.y + blockIdx.y, slot = L.wave * gridDim.y + blockIdx.y;
+  const int64_t mem = blockIdx.z;
+  const GMember G = ext(mem, gridDim.y, ScanAffine::ESZ);
+  if (L.wave >= G.nchunks) return;
+  const int64_t n = G.n, lc = G.lc, slot = L.wave * gridDim.y + blockIdx.y;
   const QModel& m = mp[mem];
-  const QDir& d = dirs[dir];
+  const QDir& d = dirs[mem * gridDim.y + blockIdx.y];
   const int J = m.J, r = L.r, c = L.c;
-  cbuf += mem * n, wbuf += mem * n * J, y += mem * y_stride, prefixS += mem * keep_stride;
-  if (prefixT) prefixT += mem * work_stride; else elem += mem * work_stride;
+  const double* prefixS = keep + G.keep + G.nchunks * WAVE;
+  t += G.t, cbuf += G.fac, wbuf += G.fac * J, y += G.y;
+  if (prefixT) prefixT += G.pre; else elem += G.work;
+  const int64_t row = G.tan + blockIdx.y * n;  // of this direction's dc (dw: J times that)
   const double h_r = r < J ? m.h[r] : 0.0;
   double s = prefixS[L.wave * WAVE + r * 8], ds = prefixT ? prefixT[slot * WAVE + L.lane] : 0.0;
   double M = (r == c && r < J) ? 1.0 : 0.0, acc = 0.0, o;
@@ -1092,13 +1144,13 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_gsol(const QModel* __restrict__
   for (int64_t i = n0; i < n1; ++i) {
     double Phi, dPhi;
     phi_entry_d(m, d, dt_at(t, i), r, c, &Phi, &dPhi);
-    const double w = r < J ? wbuf[i * J + r] : 0.0, dw = r < J ? dwbuf[(dir * n + i) * J + r] : 0.0;
+    const double w = r < J ? wbuf[i * J + r] : 0.0, dw = r < J ? dwbuf[(row + i) * J + r] : 0.0;
     const double cv = cbuf[i];
-    acc += gsol_step(m, d, Phi, dPhi, w, dw, cv, dcbuf[dir * n + i], y[i], s, ds, r);
+    acc += gsol_step(m, d, Phi, dPhi, w, dw, cv, dcbuf[row + i], y[i], s, ds, r);
     if (!prefixT) M = step_apply(TGP_QS_FWD, m, StepData{Phi, w, sqrt(cv), h_r}, M, 0.0, &o, r, c);
   }
   if (prefixT) {
-    if (L.lane == 0) dsum[dir * nchunks + L.wave] = acc;
+    if (L.lane == 0) dsum[G.sums + blockIdx.y * G.nchunks + L.wave] = acc;
   } else {
     elem[slot * 2 * WAVE + L.lane] = M, elem[slot * 2 * WAVE + WAVE + L.lane] = ds;
   }
@@ -1108,20 +1160,23 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_gsol(const QModel* __restrict__
 // (K^-1)_nn = (1 + u^T O_{n+1} u) / c_n, u = A_{n+1} w_n, with O the backward recurrence of the prediction (qs_pred_*,
 // dir 1, variance part): this is its emit pass with N outputs instead of test points.
 // (4 waves per SIMD asked for: the member's model pointer costs SGPRs that spill into VGPR lanes, 127 -> 135 without it)
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) __attribute__((amdgpu_waves_per_eu(4, 4))) void qs_invdiag_emit(
                                                               const QModel* __restrict__ mp,
                                                               const double* __restrict__ t,
                                                               const double* __restrict__ cbuf,
                                                               const double* __restrict__ wbuf,
-                                                              const double* __restrict__ alpha, int64_t n, int64_t lc,
-                                                              int64_t nchunks, const double* __restrict__ prefix,
-                                                              int64_t work_stride, double* __restrict__ out) {
+                                                              const double* __restrict__ alpha, E ext,
+                                                              const double* __restrict__ prefix,
+                                                              double* __restrict__ out) {
   const Lane L;
-  if (L.wave >= nchunks) return;
   const int64_t mem = blockIdx.y;
+  const GMember G = ext(mem, 0, ScanPred::ESZ);
+  if (L.wave >= G.nchunks) return;
+  const int64_t n = G.n, lc = G.lc, nchunks = G.nchunks;
   const QModel& m = mp[mem];
   const int J = m.J, r = L.r, c = L.c;
-  cbuf += mem * n, wbuf += mem * n * J, alpha += mem * n, prefix += mem * work_stride, out += mem * n;
+  t += G.t, cbuf += G.fac, wbuf += G.fac * J, alpha += G.fac, prefix += G.pre, out += G.fac;
   double X = prefix[L.wave * 2 * WAVE + L.lane];
   const Chunk ch(true, L.wave, nchunks, lc, n);
   for (int64_t j = 0, len = ch.len(); j < len; ++j) {
@@ -1150,11 +1205,15 @@ struct UniformSums {  // member x reads a and b x in_stride doubles, bad x bad_s
     return {na, nb, mem * in_stride, mem * in_stride, mem * bad_stride};
   }
 };
-struct TableSums {  // a, b and bad: the per-chunk arrays of all members, each member's part where its extent says
+// a, b and bad: the per-chunk arrays of all members, each member's part where its extent says.  With nd directions per
+// member, block x serves direction x % nd of member x / nd (the layout "extents" states); the values have nd = 1.
+struct TableSums {
   const QExtent* tab;
-  __device__ __forceinline__ Sums operator()(int64_t mem) const {
-    const QExtent& x = tab[mem];
-    return {x.nchunks, x.nchunks, x.chunks, x.chunks, x.chunks};
+  int64_t nd;
+  __device__ __forceinline__ Sums operator()(int64_t blk) const {
+    const QExtent& x = tab[blk / nd];
+    const int64_t o = nd * x.chunks + (blk % nd) * x.nchunks;
+    return {x.nchunks, x.nchunks, o, o, o};
   }
 };
 
@@ -1195,6 +1254,16 @@ __global__ void qs_keep_rows(const double* __restrict__ src, int64_t src_stride,
                              int64_t dst_stride, int64_t len) {
   const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, mem = blockIdx.y;
   if (i < len) dst[mem * dst_stride + i] = src[mem * src_stride + i];
+}
+
+// the same for the members of an extent table: member blockIdx.y's chunk prefixes of a width-1 scan with `eblocks`
+// lane-blocks per element, from its work space to slot `which` (0: filtered covariances, 1: solve states) of its keep
+__global__ void qs_keep_table(const QExtent* __restrict__ tab, const double* __restrict__ work, int64_t eblocks,
+                              double* __restrict__ keep, int64_t which) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  const QExtent& x = tab[blockIdx.y];
+  const int64_t len = x.nchunks * WAVE;
+  if (i < len) keep[x.keep + which * len + i] = work[x.work + x.nchunks * eblocks * WAVE + i];
 }
 
 inline int64_t blocks_for(int64_t waves) { return (waves + WPB - 1) / WPB; }
@@ -1240,8 +1309,14 @@ struct tgp_qsep_series {
   int64_t nseries = 0;
   std::vector<int64_t> offsets;  // nseries + 1: series b is [offsets[b], offsets[b + 1]) of the concatenated arrays
   std::vector<QExtent> ext;      // the table's host copy; series_split fills the offsets inside a chain
-  std::vector<int64_t> chain0;   // the split for table_J: every chain's first member, then nseries
-  int32_t table_J = 0;           // the state dimension the resident table's chains were cut for (0: none yet)
+  std::vector<int64_t> chain0;   // the split the table was cut for: every chain's first member, then nseries
+  std::vector<int64_t> chain_d;  // gradient: every chain's directions per pass
+  // what the resident table's chains were cut for: the call (0: none yet, 1: value, 2: value and gradient), the state
+  // dimension, the directions per member and whether the vectors were wanted (the last two: gradient only)
+  struct Cut {
+    int32_t call = 0, J = 0, P = 0, vectors = 0;
+    bool operator==(const Cut& o) const { return call == o.call && J == o.J && P == o.P && vectors == o.vectors; }
+  } cut;
   int64_t buf_need = 0;          // what the largest of those chains needs, in doubles
   double* t = nullptr;
   QExtent* tab = nullptr;
@@ -1302,17 +1377,20 @@ int run_scan(const QModel* models, hipStream_t st, int64_t count, int64_t width,
 }
 
 // The same over the members of an extent table, each with a scan of its own: the levels of the deepest member are
-// launched (top[l]: the largest level-l size, `depth` levels), every grid sized for the largest member.  One scan per
-// member (width 1); the level-0 prefixes land in each member's work space, where TableExtent looks for them.
+// launched (top[l]: the largest level-l size, `depth` levels), every grid sized for the largest member.  The level-0
+// prefixes land in each member's work space, where TableExtent / TableGExtent look for them.  width 0: one scan per
+// member in its primal work space; width >= 1: the scans of a direction pass, `width` per member, in its tangent one.
 template <class S>
 int run_scan_table(const QModel* models, hipStream_t st, const QExtent* tab, int64_t members, const int64_t* top,
-                   int depth, double* work) {
+                   int depth, double* work, int64_t width = 0) {
+  const int32_t tangent = width > 0;
+  const int64_t w = tangent ? width : 1;
   for (int l = 0; l + 1 < depth; ++l)
-    qs_scan_reduce<S, TableLevel><<<dim3(unsigned(blocks_for(top[l + 1])), unsigned(members)), WAVE * WPB, 0, st>>>(
-        models, work, 1, work, TableLevel{tab, l});
+    qs_scan_reduce<S, TableLevel><<<dim3(unsigned(blocks_for(top[l + 1] * w)), unsigned(members)), WAVE * WPB, 0, st>>>(
+        models, work, w, work, TableLevel{tab, l, tangent});
   for (int l = depth; l-- > 0;)
-    qs_scan_down<S, TableLevel><<<dim3(unsigned(blocks_for(top[l + 1])), unsigned(members)), WAVE * WPB, 0, st>>>(
-        models, work, 1, l + 1 < depth ? work : nullptr, work, TableLevel{tab, l});
+    qs_scan_down<S, TableLevel><<<dim3(unsigned(blocks_for(top[l + 1] * w)), unsigned(members)), WAVE * WPB, 0, st>>>(
+        models, work, w, l + 1 < depth ? work : nullptr, work, TableLevel{tab, l, tangent});
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
@@ -1513,7 +1591,7 @@ int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const 
   TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanPred>(nc, 1)));
   for (int dir = 0; dir < 2; ++dir) {
     qs_pred_fold<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
-                                                        n, q->lc, nc, q->work, 0);
+                                                        UniformGExtent{n, q->lc, nc, 0, 0, 0, 0}, q->work);
     double* prefix = nullptr;
     TGP_TRY(run_scan<ScanPred>(q->model, st, nc, 1, q->work, &prefix));
     qs_pred_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
@@ -1567,19 +1645,17 @@ int launch_tangents(tgp_qsep* q, const QModel* models, int64_t members, const QD
   hipStream_t st = q->ctx->stream;
   const int64_t n = q->n, nc = q->nchunks, md = members * nd;
   const dim3 grid(unsigned(blocks_for(nc)), unsigned(nd), unsigned(members));
-  const double *prefixP = keep, *prefixS = keep + nc * WAVE;
+  const UniformGExtent ext{n, q->lc, nc, noise_stride, resid_stride, keep_stride, work_stride};
   double *dcb = tan, *dwb = tan + md * n, *dsum = red, *dsum2 = red + md * nc;
   double* prefix = nullptr;
-  qs_gfac_fold<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, noise, noise_stride, n, q->lc, nc, prefixP,
-                                            keep_stride, work, work_stride);
+  qs_gfac_fold<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, noise, ext, keep, work);
   TGP_TRY(run_scan<ScanCong>(models, st, nc, nd, work, &prefix, members, work_stride));
-  qs_gfac_emit<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, noise, noise_stride, n, q->lc, nc, prefixP,
-                                            keep_stride, prefix, work_stride, dcb, dwb, dsum);
-  qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, cbuf, wbuf, dcb, dwb, resid, resid_stride, n, q->lc, nc,
-                                       prefixS, keep_stride, nullptr, work, work_stride, nullptr);
+  qs_gfac_emit<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, noise, ext, keep, prefix, dcb, dwb, dsum);
+  qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, cbuf, wbuf, dcb, dwb, resid, ext, keep, nullptr, work,
+                                       nullptr);
   TGP_TRY(run_scan<ScanAffine>(models, st, nc, nd, work, &prefix, members, work_stride));
-  qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, cbuf, wbuf, dcb, dwb, resid, resid_stride, n, q->lc, nc,
-                                       prefixS, keep_stride, prefix, nullptr, work_stride, dsum2);
+  qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, cbuf, wbuf, dcb, dwb, resid, ext, keep, prefix, nullptr,
+                                       dsum2);
   // block b: (member, direction) b's two sums (dsum2 lies md nc doubles after dsum, like its rows)
   qs_finish<<<unsigned(md), WAVE, 0, st>>>(dsum, dsum2, nullptr, res, nullptr, UniformSums{nc, nc, nc, 0}, 2);
   TGP_HIP_TRY(hipGetLastError());
@@ -1594,11 +1670,11 @@ int launch_invdiag(tgp_qsep* q, const QModel* models, int64_t members, const dou
   hipStream_t st = q->ctx->stream;
   const int64_t n = q->n, nc = q->nchunks;
   const dim3 grid(unsigned(blocks_for(nc)), unsigned(members));
-  qs_pred_fold<<<grid, WAVE * WPB, 0, st>>>(1, 0, 1, models, q->t, cbuf, wbuf, nullptr, n, q->lc, nc, work,
-                                            work_stride);
+  const UniformGExtent ext{n, q->lc, nc, 0, 0, 0, work_stride};
+  qs_pred_fold<<<grid, WAVE * WPB, 0, st>>>(1, 0, 1, models, q->t, cbuf, wbuf, nullptr, ext, work);
   double* prefix = nullptr;
   TGP_TRY(run_scan<ScanPred>(models, st, nc, 1, work, &prefix, members, work_stride));
-  qs_invdiag_emit<<<grid, WAVE * WPB, 0, st>>>(models, q->t, cbuf, wbuf, alpha, n, q->lc, nc, prefix, work_stride, out);
+  qs_invdiag_emit<<<grid, WAVE * WPB, 0, st>>>(models, q->t, cbuf, wbuf, alpha, ext, prefix, out);
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
@@ -1758,14 +1834,15 @@ int64_t series_need(const QExtent& x, int64_t J) { return x.n * (4 + J) + series
 
 // cuts the set into chains for state dimension J and makes the resident table say where each member lies in its chain
 int series_split(tgp_qsep_series* s, int32_t J) {
-  if (s->table_J == J) return TGP_OK;
+  const tgp_qsep_series::Cut cut{1, J, 0, 0};
+  if (s->cut == cut) return TGP_OK;
   const int64_t budget = BATCH_SCRATCH_BYTES / int64_t(sizeof(double)) - BATCH_MAX_MEMBERS * MODEL_DOUBLES;
   for (int64_t b = 0; b < s->nseries; ++b)
     TGP_ARG_CHECK(series_need(s->ext[size_t(b)], J) <= budget,
                   "series %lld (n = %lld) needs %lld doubles of scratch and exceeds its cap of %lld bytes", (long long)b,
                   (long long)s->ext[size_t(b)].n, (long long)series_need(s->ext[size_t(b)], J),
                   (long long)BATCH_SCRATCH_BYTES);
-  s->table_J = 0;
+  s->cut = {};
   s->chain0.assign(1, 0);
   int64_t used = 0, count = 0, largest = 0, off = 0, work = 0, chunks = 0;
   for (int64_t b = 0; b < s->nseries; ++b) {
@@ -1785,7 +1862,7 @@ int series_split(tgp_qsep_series* s, int32_t J) {
   hipStream_t st = s->ctx->stream;
   TGP_HIP_TRY(hipMemcpyAsync(s->tab, s->ext.data(), s->ext.size() * sizeof(QExtent), hipMemcpyHostToDevice, st));
   TGP_HIP_TRY(hipStreamSynchronize(st));
-  s->table_J = J;
+  s->cut = cut;
   return TGP_OK;
 }
 
@@ -1832,7 +1909,7 @@ int series_chain(tgp_qsep_series* s, int64_t b0, int64_t nb, const QModel* model
   qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, t, cbuf, wbuf, ext, 1, 1, resid, work);
   TGP_TRY(run_scan_table<ScanAffine>(models, st, tab, nb, top, depth, work));
   qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, t, cbuf, wbuf, ext, 1, 1, work, resid, z, sumsq);
-  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(logsum, sumsq, bad, res, reinterpret_cast<int64_t*>(res) + 2, TableSums{tab},
+  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(logsum, sumsq, bad, res, reinterpret_cast<int64_t*>(res) + 2, TableSums{tab, 1},
                                            3);
   TGP_HIP_TRY(hipGetLastError());
   std::vector<double> got(size_t(3 * nb));
@@ -1979,6 +2056,208 @@ int grad_batch_chain(tgp_qsep* q, const GradLayout& lay, int64_t nb, const QMode
     for (int64_t i = 0; failed && i < n; ++i) {
       if (a.gnoise) a.gnoise[b * n + i] = NAN;
       if (a.alpha) a.alpha[b * n + i] = NAN;
+    }
+  }
+  return TGP_OK;
+}
+
+// ---- sets of series: value and gradient --------------------------------------------------------------------------------
+// The set's chains with the gradient's arrays, every array the sum of what the chain's own members need.  With P
+// directions per member, d of them per pass, S4_b the sizes of series b's MAXLEV table levels summed, in doubles:
+//   fixed        BATCH_MAX_MEMBERS models | BATCH_MAX_MEMBERS x GRAD_MAX_BATCH directions (one pass's)
+//   member_b     noise | residual | c | z (N_b each) | w (N_b J) | both primal scans' chunk prefixes (2 x 64 nchunks_b) |
+//                scan work space (256 S4_b; 384 S4_b with the vectors: the prediction scan's) | per-chunk sums of log c |
+//                of z^2 | bad-pivot slots (nchunks_b each) | results (3 + 2 P) | with the vectors: alpha | noise gradient
+//                (N_b each)
+//   dir_b        per direction of a pass: dc, dw (N_b (1 + J)) | scan work space (192 S4_b) | per-chunk sums (2 nchunks_b)
+// The split (series_grad_split): chains are filled in the order given; a chain ends at BATCH_MAX_MEMBERS members or
+// before the member that would take sum (member_b + [P > 0] dir_b) past the cap less the fixed part.  Per chain,
+// d = min(P, GRAD_MAX_BATCH, (cap - fixed - sum member_b) / sum dir_b).  A function of (N_0 .. N_{B-1}, J, P, vectors
+// wanted or not) alone.
+int64_t series_levels(const QExtent& x) {
+  int64_t s = 0;
+  for (int l = 0; l < MAXLEV; ++l) s += x.lev[l];
+  return s;
+}
+int64_t series_grad_work(const QExtent& x, bool vectors) {
+  const int64_t blocks = vectors ? std::max<int64_t>(SERIES_BLOCKS, ScanPred::ESZ + ScanPred::PSZ) : SERIES_BLOCKS;
+  return series_levels(x) * blocks * WAVE;
+}
+int64_t series_grad_twork(const QExtent& x) { return series_levels(x) * (ScanCong::ESZ + ScanCong::PSZ) * WAVE; }
+int64_t series_grad_member(const QExtent& x, int64_t J, int64_t P, bool vectors) {
+  return x.n * (4 + J) + 2 * x.nchunks * WAVE + series_grad_work(x, vectors) + 3 * x.nchunks + 3 + 2 * P +
+         (vectors ? 2 * x.n : 0);
+}
+int64_t series_grad_dir(const QExtent& x, int64_t J) { return x.n * (1 + J) + series_grad_twork(x) + 2 * x.nchunks; }
+
+constexpr int64_t SERIES_GRAD_FIXED = BATCH_MAX_MEMBERS * (MODEL_DOUBLES + GRAD_MAX_BATCH * DIR_DOUBLES);
+
+// cuts the set into chains for (J, P, vectors) and makes the resident table say where each member lies in its chain
+int series_grad_split(tgp_qsep_series* s, int32_t J, int32_t P, bool vectors) {
+  const tgp_qsep_series::Cut cut{2, J, P, int32_t(vectors)};
+  if (s->cut == cut) return TGP_OK;
+  const int64_t budget = BATCH_SCRATCH_BYTES / int64_t(sizeof(double)) - SERIES_GRAD_FIXED;
+  auto one = [&](const QExtent& x) { return series_grad_member(x, J, P, vectors) + (P > 0 ? series_grad_dir(x, J) : 0); };
+  for (int64_t b = 0; b < s->nseries; ++b)
+    TGP_ARG_CHECK(one(s->ext[size_t(b)]) <= budget,
+                  "series %lld (n = %lld) needs %lld doubles of scratch and exceeds its cap of %lld bytes", (long long)b,
+                  (long long)s->ext[size_t(b)].n, (long long)one(s->ext[size_t(b)]), (long long)BATCH_SCRATCH_BYTES);
+  s->cut = {};
+  s->chain0.assign(1, 0);
+  s->chain_d.clear();
+  int64_t used = 0, count = 0, largest = 0, mem = 0, dir = 0, off = 0, work = 0, chunks = 0, twork = 0;
+  auto close = [&]() {  // the chain that ends here: its directions per pass and its need
+    const int64_t d = P > 0 ? std::min<int64_t>({int64_t(P), GRAD_MAX_BATCH, (budget - mem) / dir}) : 0;
+    s->chain_d.push_back(d);
+    largest = std::max(largest, mem + d * dir);
+  };
+  for (int64_t b = 0; b < s->nseries; ++b) {
+    QExtent& x = s->ext[size_t(b)];
+    if (count == BATCH_MAX_MEMBERS || used + one(x) > budget) {
+      close();
+      s->chain0.push_back(b);
+      used = count = mem = dir = off = work = chunks = twork = 0;
+    }
+    x.off = off, x.work = work, x.chunks = chunks, x.keep = 2 * chunks * WAVE, x.twork = twork;
+    off += x.n, work += series_grad_work(x, vectors), chunks += x.nchunks, twork += series_grad_twork(x);
+    mem += series_grad_member(x, J, P, vectors), dir += series_grad_dir(x, J);
+    used += one(x), ++count;
+  }
+  close();
+  s->chain0.push_back(s->nseries);
+  s->buf_need = SERIES_GRAD_FIXED + largest;
+  hipStream_t st = s->ctx->stream;
+  TGP_HIP_TRY(hipMemcpyAsync(s->tab, s->ext.data(), s->ext.size() * sizeof(QExtent), hipMemcpyHostToDevice, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  s->cut = cut;
+  return TGP_OK;
+}
+
+struct SeriesGradArgs {
+  int64_t nl, J, ndir;
+  const double *noise, *resid;         // host, concatenated over the whole set
+  const double *dleaves, *dh, *dPinf;  // host, the set's first member's
+  int32_t* info;
+  double *out, *dout, *gnoise, *alpha;  // host, the set's first member's; the last two may be null
+};
+
+// one launch chain: members [b0, b0 + nb) of the set with D directions per pass.  One stream synchronisation, at the end.
+int series_grad_chain(tgp_qsep_series* s, int64_t b0, int64_t nb, int64_t D, const QModel* models_host,
+                      const SeriesGradArgs& a, int32_t* passes) {
+  hipStream_t st = s->ctx->stream;
+  const QExtent* mine = &s->ext[size_t(b0)];
+  const int64_t J = a.J, P = a.ndir;
+  const bool vectors = a.gnoise || a.alpha;
+  int64_t N = 0, W = 0, TW = 0, C = 0, top[MAXLEV + 1] = {};
+  for (int64_t b = 0; b < nb; ++b) {
+    N += mine[b].n, W += series_grad_work(mine[b], vectors), TW += series_grad_twork(mine[b]), C += mine[b].nchunks;
+    for (int l = 0; l <= MAXLEV; ++l) top[l] = std::max(top[l], mine[b].lev[l]);
+  }
+  int depth = 1;  // the deepest member's: the level sizes grow with the chunk count
+  while (top[depth - 1] > GROUP) ++depth;
+  QModel* models = reinterpret_cast<QModel*>(s->buf);
+  double* p = s->buf + BATCH_MAX_MEMBERS * MODEL_DOUBLES;
+  QDir* dirs = reinterpret_cast<QDir*>(p);
+  p += BATCH_MAX_MEMBERS * GRAD_MAX_BATCH * DIR_DOUBLES;
+  auto take = [&](int64_t len) {
+    double* r = p;
+    p += len;
+    return r;
+  };
+  double* noise = take(N);
+  double* resid = take(N);
+  double* cbuf = take(N);
+  double* wbuf = take(N * J);
+  double* z = take(N);
+  double* keep = take(2 * C * WAVE);
+  double* work = take(W);
+  double* logsum = take(C);
+  double* sumsq = take(C);
+  int64_t* bad = reinterpret_cast<int64_t*>(take(C));
+  double* res = take(3 * nb);
+  double* dres = take(2 * P * nb);
+  double* alpha = take(vectors ? N : 0);
+  double* gnoise = take(vectors ? N : 0);
+  double* tan = take(D * N * (1 + J));
+  double* twork = take(D * TW);
+  double* tred = take(D * 2 * C);
+  const int64_t at = s->offsets[size_t(b0)];
+  const double* t = s->t + at;
+  const QExtent* tab = s->tab + b0;
+  const TableExtent ext{tab};
+  const TableGExtent gext{tab};
+  TGP_HIP_TRY(hipMemcpyAsync(models, models_host, size_t(nb) * sizeof(QModel), hipMemcpyHostToDevice, st));
+  TGP_HIP_TRY(hipMemcpyAsync(noise, a.noise + at, size_t(N) * sizeof(double), hipMemcpyHostToDevice, st));
+  TGP_HIP_TRY(hipMemcpyAsync(resid, a.resid + at, size_t(N) * sizeof(double), hipMemcpyHostToDevice, st));
+  // the primal part, each scan's chunk prefixes set aside
+  const dim3 grid(unsigned(blocks_for(top[0])), unsigned(nb));
+  const dim3 kgrid(unsigned(ceil_div(top[0] * WAVE, 256)), unsigned(nb));
+  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, t, noise, ext, work);
+  TGP_TRY(run_scan_table<ScanRiccati>(models, st, tab, nb, top, depth, work));
+  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, t, noise, ext, work, cbuf, wbuf, logsum, bad);
+  qs_keep_table<<<kgrid, 256, 0, st>>>(tab, work, ScanRiccati::ESZ, keep, 0);
+  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, t, cbuf, wbuf, ext, 1, 1, resid, work);
+  TGP_TRY(run_scan_table<ScanAffine>(models, st, tab, nb, top, depth, work));
+  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, t, cbuf, wbuf, ext, 1, 1, work, resid, z, sumsq);
+  qs_keep_table<<<kgrid, 256, 0, st>>>(tab, work, ScanAffine::ESZ, keep, 1);
+  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(logsum, sumsq, bad, res, reinterpret_cast<int64_t*>(res) + 2,
+                                           TableSums{tab, 1}, 3);
+  TGP_HIP_TRY(hipGetLastError());
+  // direction passes, as in grad_batch_chain: pass k's host directions (member-major) stay alive until the
+  // synchronisation below, its results land after those of the passes before it (2 nb d0 doubles)
+  std::vector<QDir> hd(size_t(nb * P));
+  for (int64_t d0 = 0; d0 < P; d0 += D, ++*passes) {
+    const int64_t nd = std::min<int64_t>(D, P - d0);
+    QDir* h = hd.data() + nb * d0;
+    for (int64_t b = 0; b < nb; ++b)
+      pack_dirs(h + b * nd, d0, nd, a.nl, J, a.dleaves + (b0 + b) * P * a.nl * 4, a.dh + (b0 + b) * P * J,
+                a.dPinf + (b0 + b) * P * J * J);
+    TGP_HIP_TRY(hipMemcpyAsync(dirs, h, size_t(nb * nd) * sizeof(QDir), hipMemcpyHostToDevice, st));
+    const dim3 tgrid(unsigned(blocks_for(top[0])), unsigned(nd), unsigned(nb));
+    double *dcb = tan, *dwb = tan + nd * N, *dsum = tred, *dsum2 = tred + nd * C;
+    qs_gfac_fold<<<tgrid, WAVE * WPB, 0, st>>>(models, dirs, t, noise, gext, keep, twork);
+    TGP_TRY(run_scan_table<ScanCong>(models, st, tab, nb, top, depth, twork, nd));
+    qs_gfac_emit<<<tgrid, WAVE * WPB, 0, st>>>(models, dirs, t, noise, gext, keep, twork, dcb, dwb, dsum);
+    qs_gsol<<<tgrid, WAVE * WPB, 0, st>>>(models, dirs, t, cbuf, wbuf, dcb, dwb, resid, gext, keep, nullptr, twork,
+                                          nullptr);
+    TGP_TRY(run_scan_table<ScanAffine>(models, st, tab, nb, top, depth, twork, nd));
+    qs_gsol<<<tgrid, WAVE * WPB, 0, st>>>(models, dirs, t, cbuf, wbuf, dcb, dwb, resid, gext, keep, twork, nullptr,
+                                          dsum2);
+    // block b nd + d: (member b, direction d)'s two sums
+    qs_finish<<<unsigned(nb * nd), WAVE, 0, st>>>(dsum, dsum2, nullptr, dres + 2 * nb * d0, nullptr, TableSums{tab, nd},
+                                                  2);
+    TGP_HIP_TRY(hipGetLastError());
+  }
+  if (vectors) {
+    qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_BWD, models, t, cbuf, wbuf, ext, 1, 1, z, work);
+    TGP_TRY(run_scan_table<ScanAffine>(models, st, tab, nb, top, depth, work));
+    qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_BWD, models, t, cbuf, wbuf, ext, 1, 1, work, z, alpha, nullptr);
+    if (a.alpha)
+      TGP_HIP_TRY(hipMemcpyAsync(a.alpha + at, alpha, size_t(N) * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (a.gnoise) {
+      qs_pred_fold<<<grid, WAVE * WPB, 0, st>>>(1, 0, 1, models, t, cbuf, wbuf, nullptr, gext, work);
+      TGP_TRY(run_scan_table<ScanPred>(models, st, tab, nb, top, depth, work));
+      qs_invdiag_emit<<<grid, WAVE * WPB, 0, st>>>(models, t, cbuf, wbuf, alpha, gext, work, gnoise);
+      TGP_HIP_TRY(hipMemcpyAsync(a.gnoise + at, gnoise, size_t(N) * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    TGP_HIP_TRY(hipGetLastError());
+  }
+  std::vector<double> got(size_t(3 * nb)), dgot(size_t(2 * nb * P));
+  TGP_HIP_TRY(hipMemcpyAsync(got.data(), res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (P > 0) TGP_HIP_TRY(hipMemcpyAsync(dgot.data(), dres, dgot.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t b = 0; b < nb; ++b) {
+    const int64_t g = b0 + b, n = mine[b].n, lo = s->offsets[size_t(g)];
+    member_value(&got[size_t(3 * b)], n, &a.info[g], &a.out[g]);
+    const bool failed = a.info[g] != 0;  // c and w are not a factor of anything: what ran on them is overwritten
+    for (int64_t d0 = 0; d0 < P; d0 += D) {
+      const int64_t nd = std::min<int64_t>(D, P - d0);
+      for (int64_t d = 0; d < nd; ++d)
+        a.dout[g * P + d0 + d] = failed ? NAN : grad_value(&dgot[size_t(2 * (nb * d0 + b * nd + d))]);
+    }
+    for (int64_t i = 0; failed && i < n; ++i) {
+      if (a.gnoise) a.gnoise[lo + i] = NAN;
+      if (a.alpha) a.alpha[lo + i] = NAN;
     }
   }
   return TGP_OK;
@@ -2305,6 +2584,39 @@ int tgp_qsep_series_logprob(tgp_qsep_series* s, const double* leaves, int32_t nl
     TGP_TRY(series_chain(s, b0, cnt, models.data() + b0, J, noise_concat, resid_concat, info + b0, out + b0));
   }
   if (nchains) *nchains = int32_t(chains);
+  return TGP_OK;
+}
+
+int tgp_qsep_series_grad(tgp_qsep_series* s, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                         int32_t J, const double* hvec, const double* Pinf, const double* noise_concat,
+                         const double* resid_concat, int32_t ndir, const double* dleaves, const double* dh,
+                         const double* dPinf, int32_t* info, double* out, double* dout, double* gnoise_concat,
+                         double* alpha_concat, int32_t* nchains, int32_t* npasses) {
+  QS_GUARD(s);
+  if (nchains) *nchains = 0;
+  if (npasses) *npasses = 0;
+  TGP_ARG_CHECK(ndir >= 0, "negative number of directions (%d)", ndir);
+  TGP_ARG_CHECK(leaves && state_map && hvec && Pinf, "null model array");
+  TGP_ARG_CHECK(noise_concat && resid_concat && info && out, "null argument");
+  TGP_ARG_CHECK(ndir == 0 || (dleaves && dh && dPinf && dout), "null direction array");
+  const int64_t nb = s->nseries;
+  std::vector<QModel> models(size_t(nb), QModel{});
+  for (int64_t b = 0; b < nb; ++b)
+    TGP_TRY(pack_model(&models[size_t(b)], leaves + b * nleaves * 5, nleaves, state_map, J, hvec + b * J,
+                       Pinf + b * J * J));
+  TGP_TRY(series_grad_split(s, J, ndir, gnoise_concat || alpha_concat));
+  TGP_TRY(grow(&s->buf, &s->buf_elems, s->buf_need));
+  const SeriesGradArgs a{nleaves,       J,     ndir, noise_concat, resid_concat,  dleaves,
+                         dh,            dPinf, info, out,          dout,          gnoise_concat,
+                         alpha_concat};
+  const size_t chains = s->chain0.size() - 1;
+  int32_t passes = 0;
+  for (size_t k = 0; k < chains; ++k) {
+    const int64_t b0 = s->chain0[k], cnt = s->chain0[k + 1] - b0;
+    TGP_TRY(series_grad_chain(s, b0, cnt, s->chain_d[k], models.data() + b0, a, &passes));
+  }
+  if (nchains) *nchains = int32_t(chains);
+  if (npasses) *npasses = passes;
   return TGP_OK;
 }
 

@@ -9,7 +9,7 @@ nothing of size N x M), the same for every term of a sum at once (``predict_term
 the gradient of the log-probability (``value_and_grad``; O(N) per parameter) and the log-probabilities of many
 hyper-parameter sets over the one series in one launch chain (``log_probability_batch``; with their gradients:
 ``value_and_grad_batch``).  :class:`QuasisepSeriesSet` evaluates many series, each on coordinates of its own, in one
-launch chain (``tgp_qsep_series_logprob``).  Nothing
+launch chain (``tgp_qsep_series_logprob``; with their gradients: ``tgp_qsep_series_grad``).  Nothing
 of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
 reference); the full conditional covariance and conditioning on another kernel keep the reference's dense route.
 
@@ -503,6 +503,23 @@ def pack_series(lengths, kernels, ys, diags, means=None):
     return leaves, smap, h, P, concat(diags, "diags", True), resid
 
 
+def pack_series_tangents(lengths, kernels):
+    """The parameter tangents of ``tgp_qsep_series_grad`` for series of the given lengths: ``(dleaves (B, P, L, 4), dh
+    (B, P, J), dPinf (B, P, J, J), undefined (B, P) bool)`` as :func:`tinygp_amd.kernels.quasisep.pack_batch_tangents`
+    makes them (a non-finite tangent -- the quality of a critically damped ``SHO`` -- is zeroed and flagged).  One
+    shared kernel is lowered once and repeated, B kernels of one structure are stacked; a member whose parameter count
+    differs raises ``ValueError`` naming it, and so does a wrong number of kernels."""
+    from tinygp_amd.kernels.quasisep import Quasisep, pack_batch_tangents
+
+    nb = len(lengths)
+    if isinstance(kernels, Quasisep):
+        return tuple(np.ascontiguousarray(np.repeat(a, nb, axis=0)) for a in pack_batch_tangents([kernels]))
+    kernels = list(kernels)
+    if len(kernels) != nb:
+        raise ValueError(f"kernels must be one kernel or one per series ({nb}); got {len(kernels)}")
+    return pack_batch_tangents(kernels)
+
+
 class QuasisepSeriesSet:
     """B series on coordinates of their own -- the light curves of a survey, each with its gaps, masks and length --
     evaluated together on the device: one series per grid row of every kernel (``tgp_qsep_series_logprob``), where a
@@ -554,6 +571,41 @@ class QuasisepSeriesSet:
         out[(info != 0) | ~np.isfinite(out)] = -np.inf
         return (out, info) if return_info else out
 
+    def value_and_grad(self, kernels, ys, diags, *, means=None, vectors: bool = True, return_info: bool = False):
+        """Value and gradient of the B series in one launch chain (``tgp_qsep_series_grad``): what a population fit by
+        L-BFGS or HMC needs per step.  Arguments as in :meth:`log_probability`; every member must have the same number
+        of parameters (:func:`pack_series_tangents`).  Returns ``(values (B,), grads)`` with ``grads = {"kernel":
+        (B, P) float64, "noise_diag": list of B arrays (N_b,), "mean": list of B arrays (N_b,), "transform": None}``;
+        with ``vectors=False`` the two lists are ``None`` and their scans are skipped.  Member b has the bits of
+        ``QuasisepSolver(kernels[b], Xs[b], Diagonal(diags[b])).value_and_grad(ys[b] - means[b])`` on a fresh solver,
+        whatever B, its position, the other members' lengths and the split into chains and direction passes.  A failed
+        or non-finite member gives ``-inf`` and NaN gradients and touches no other; an undefined derivative (the
+        quality of a critically damped ``SHO``) is NaN in that entry only.  With ``return_info`` also the B ``info``
+        values."""
+        if self._handle is None:
+            raise ValueError("this QuasisepSeriesSet has been closed")
+        leaves, smap, h, P, noise, resid = pack_series(self.lengths, kernels, ys, diags, means)
+        dleaves, dh, dP, undefined = pack_series_tangents(self.lengths, kernels)
+        nb, ndir, total = len(self), dh.shape[1], int(self._offsets[-1])
+        info, out, kgrad = np.zeros(nb, dtype=np.int32), np.empty(nb), np.zeros((nb, ndir))
+        gnoise, alpha = (np.empty(total), np.empty(total)) if vectors else (None, None)
+        _ffi.check(_ffi.lib().tgp_qsep_series_grad(self._handle, _ffi.ptr(leaves), leaves.shape[1], _ffi.ptr(smap),
+                                                   h.shape[1], _ffi.ptr(h), _ffi.ptr(P), _ffi.ptr(noise),
+                                                   _ffi.ptr(resid), ndir, _ffi.ptr(dleaves), _ffi.ptr(dh), _ffi.ptr(dP),
+                                                   _ffi.ptr(info), _ffi.ptr(out), _ffi.ptr(kgrad), _ffi.ptr(gnoise),
+                                                   _ffi.ptr(alpha), None, None), "tgp_qsep_series_grad")
+        kgrad[undefined] = np.nan
+        failed = (info != 0) | ~np.isfinite(out)
+        out[failed] = -np.inf
+        kgrad[failed] = np.nan
+        split = lambda a: [a[lo:hi] for lo, hi in zip(self._offsets[:-1], self._offsets[1:])]  # noqa: E731
+        gnoise, alpha = (split(gnoise), split(alpha)) if vectors else (None, None)
+        for b in np.flatnonzero(failed) if vectors else ():
+            gnoise[b][:] = np.nan
+            alpha[b][:] = np.nan
+        result = out, {"kernel": kgrad, "noise_diag": gnoise, "mean": alpha, "transform": None}
+        return result + (info,) if return_info else result
+
     def close(self):
         if getattr(self, "_handle", None):
             _ffi.lib().tgp_qsep_series_destroy(self._handle)
@@ -574,5 +626,17 @@ def log_probability_series(kernels, Xs, ys, *, diags, means=None):
     series = QuasisepSeriesSet(Xs)
     try:
         return series.log_probability(kernels, ys, diags, means=means)
+    finally:
+        series.close()
+
+
+def log_probability_and_grad_series(kernels, Xs, ys, *, diags, means=None, vectors: bool = True):
+    """Value and gradient of B series, each on coordinates of its own, under quasiseparable GPs: builds a
+    :class:`QuasisepSeriesSet` on ``Xs``, evaluates it and closes it.  Member b equals ``GaussianProcess(kernels[b],
+    Xs[b], diag=diags[b], mean=means[b]).log_probability_and_grad(ys[b])`` for float64 inputs.  Arguments and result as
+    in :meth:`QuasisepSeriesSet.value_and_grad`; keep the set yourself to evaluate it more than once."""
+    series = QuasisepSeriesSet(Xs)
+    try:
+        return series.value_and_grad(kernels, ys, diags, means=means, vectors=vectors)
     finally:
         series.close()
