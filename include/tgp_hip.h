@@ -632,6 +632,25 @@ int tgp_qsep_predict(tgp_qsep* q, const double* v_host, int32_t v_is_alpha, int6
  * xtest_host == NULL: the test points are the data points themselves (m must equal n); nothing is uploaded or sorted. */
 int tgp_qsep_predict_terms(tgp_qsep* q, const double* v_host, int32_t v_is_alpha, int64_t m, const double* xtest_host,
                            int32_t nterms, const double* g_host, double* mean_host, double* var_host);
+/* Posterior samples by Matheron's rule in O((n + m) J^3) per column, on a factored handle: nrhs draws of the latent
+ * process conditioned on the residual, at the n data points (data_host, n x nrhs) and at m test points (test_host,
+ * m x nrhs; any order, anywhere relative to the data, all finite); either output may be NULL.  xtest_host == NULL: the
+ * data only (m must be 0).  The draw is a function of the standard normals the caller passes: xi_host ((n + m) x J x
+ * nrhs; row p belongs to point p of [data; test points]) drives a prior draw of the state over the merged sorted grid
+ * (np.argsort of the concatenation, stable), x_0 = chol(P) xi, x_g = A(dt) x_{g-1} + chol(sym(P - A P A^T)) xi, f = h^T x,
+ * with chol the unpivoted lower Cholesky that zeroes a column whose pivot is <= 16 * 2^-52 * P[j][j]; eps_host (n x nrhs)
+ * is the noise draw.  Then v = r - f(X) - sqrt(noise) eps, alpha = K^-1 v, data = f(X) + v - noise alpha and
+ * test = f(x) + k(x, X) alpha.  No noise is added to the result.  Columns run in passes of at most 64, and of fewer when
+ * (n + m) (max(J, 2) + 2) doubles per column plus the scans' work space would pass 1 GiB (one column that does is an
+ * argument error); *npasses (may be NULL) is their number.  A column's result has the bits of a call with that column
+ * alone.  After a failed factor both outputs are NaN. */
+int tgp_qsep_sample(tgp_qsep* q, const double* resid_host, int64_t m, const double* xtest_host, int64_t nrhs,
+                    const double* xi_host, const double* eps_host, double* data_host, double* test_host,
+                    int32_t* npasses);
+/* The conditional mean of tgp_qsep_predict for nrhs columns at once: v_host (n x nrhs) holds residuals or, with
+ * v_is_alpha != 0, alpha = K^-1 r; mean_host (m x nrhs).  No variance, and no congruence scan beside the mean's. */
+int tgp_qsep_predict_mean(tgp_qsep* q, int64_t nrhs, const double* v_host, int32_t v_is_alpha, int64_t m,
+                          const double* xtest_host, double* mean_host);
 /* Factor, log-probability (as tgp_qsep_factor_logprob) and its gradient in O(n J^3) per direction.  A direction is the
  * tangent of the model along one parameter: `dleaves` (ndir x nleaves x 4: one tangent per stored leaf parameter, the
  * dependent third parameter of an SHO included), `dh` (ndir x J), `dPinf` (ndir x J x J).  dout (ndir): the directional

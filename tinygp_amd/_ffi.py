@@ -163,6 +163,8 @@ SIGNATURES = {
     "tgp_qsep_factor_data": [_vp, _vp, _vp],
     "tgp_qsep_predict": [_vp, _vp, _i32, _i64, _vp, _vp, _vp],
     "tgp_qsep_predict_terms": [_vp, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp],
+    "tgp_qsep_sample": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _pi32],
+    "tgp_qsep_predict_mean": [_vp, _i64, _vp, _i32, _i64, _vp, _vp],
     "tgp_qsep_grad": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _pi32, _pdbl, _vp, _vp, _vp],
     "tgp_qsep_logprob_batch": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _pi32],
     "tgp_qsep_grad_batch": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp,

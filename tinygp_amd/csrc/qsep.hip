@@ -19,6 +19,8 @@
 // A_n is regenerated from dt_n = t_n - t_{n-1} (dt_0 = 0, A = I) in every kernel instead of being stored.
 // Prediction at test points (qs_pred_*) runs two more scans of the same shape, one per direction, whose elements pair
 // a congruence recurrence X <- M X M^T + V (J x J) with an affine one f <- Mf f + Vf (J-vector); see below.
+// Posterior samples (qs_prior, qs_cm_*, qs_smp_*) are affine scans too: a prior draw of the state over the merged grid of
+// data and test points, and the conditional mean for J x 8 blocks of columns; see "posterior samples" below.
 // Phase 2 is one kernel pair for every recurrence, instantiated over the four element types of "scan policies" below.
 //
 // Layout: one wavefront holds a J x J matrix (or a J x 8 block of right-hand sides) as one entry per lane,
@@ -1195,6 +1197,229 @@ __global__ __launch_bounds__(WAVE * WPB) __attribute__((amdgpu_waves_per_eu(4, 4
   }
 }
 
+// ---- posterior samples: prior states on a merged grid, conditional mean for blocks of columns ------------------------
+// Matheron's rule: with f a joint prior draw at data and test points and eps a draw of the noise,
+//   s(.) = f(.) + k(., X) alpha,   alpha = (K + D)^-1 v,   v = r - f(X) - D^1/2 eps
+// has the posterior's mean and covariance.  The prior draw is the state-space recurrence over the merged sorted grid
+// of G = N + M points (grid point g is point gp[g] of [X; X_test], at coordinate gt[g]; gp == nullptr: the identity),
+//   x_0 = chol(P) xi_0,   x_g = A(dt_g) x_{g-1} + chol(Q(dt_g)) xi_g,   Q(dt) = sym(P - A(dt) P A(dt)^T),   f_g = h^T x_g,
+// an affine recurrence over a J x 8 block of columns (element (A, chol(Q) xi); ScanAffine).  xi is indexed by point,
+// (G x J x nrhs), and f is written by point, so the caller's order needs no pass of its own.  States are not stored.
+// chol is the unpivoted lower Cholesky with a guard: a pivot d <= kCholGuard P[j, j] gives a zero column and leaves the
+// Schur complement as it is.  dt = 0 has A = I and Q = 0 exactly, so a tie gets one value.
+constexpr double kCholGuard = 16 * 0x1p-52;
+
+__device__ __forceinline__ double chol_psd(double S, double Pinf, int J, int r, int c) {
+  double Lm = 0.0;
+  for (int j = 0; j < J; ++j) {
+    const double d = at(S, j, j);
+    const bool ok = d > kCholGuard * at(Pinf, j, j);
+    const double sq = sqrt(ok ? d : 1.0);
+    const double l_r = ok ? (r == j ? sq : at(S, r, j) / sq) : 0.0;  // L[r, j], meaningful for r >= j
+    const double l_c = sh(l_r, c * 8);
+    if (c == j && r >= j) Lm = l_r;
+    if (ok && r > j && c > j) S -= l_r * l_c;
+  }
+  return Lm;
+}
+
+// the element of grid point g: *Phi = A(dt) (0 at the first point, which draws from the stationary prior) and the
+// return value chol(Q) xi, both by lane
+__device__ __forceinline__ double prior_step(const QModel& m, double Pinf, const double* __restrict__ gt, int64_t g,
+                                             double xi, int r, int c, double* Phi) {
+  const int J = m.J;
+  double S = Pinf;
+  *Phi = 0.0;
+  if (g > 0) {
+    *Phi = phi_entry(m, gt[g] - gt[g - 1], r, c);
+    S = symm(Pinf - mm_nt(mm(*Phi, Pinf, J, r, c), *Phi, J, r, c), r, c);
+  }
+  return mm(chol_psd(S, Pinf, J, r, c), xi, J, r, c);
+}
+
+// emit == 0: fold chunk k of column group cg into elem; emit != 0: walk it from its incoming state (prefix) and write
+// f = h^T x to out[point x nrhs + column]
+__global__ __launch_bounds__(WAVE * WPB) void qs_prior(int emit, const QModel* __restrict__ mp,
+                                                       const double* __restrict__ gt, const int64_t* __restrict__ gp,
+                                                       int64_t G, int64_t lc, int64_t nchunks,
+                                                       const double* __restrict__ xi, int64_t nrhs, int64_t ncg,
+                                                       const double* __restrict__ prefix, double* __restrict__ elem,
+                                                       double* __restrict__ out) {
+  const Lane L;
+  if (L.wave >= nchunks * ncg) return;
+  const QModel& m = *mp;
+  const int J = m.J, r = L.r, c = L.c;
+  const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
+  const bool live = r < J && col < nrhs;
+  const double Pinf = m.P[L.lane];
+  double M = (r == c && r < J) ? 1.0 : 0.0, X = emit ? prefix[L.wave * WAVE + L.lane] : 0.0, Phi;
+  const int64_t g0 = k * lc, g1 = min(G, g0 + lc);
+  for (int64_t g = g0; g < g1; ++g) {
+    const int64_t p = gp ? gp[g] : g;
+    const double W = prior_step(m, Pinf, gt, g, live ? xi[(p * J + r) * nrhs + col] : 0.0, r, c, &Phi);
+    X = mm(Phi, X, J, r, c) + W;
+    if (emit) {
+      const double f = hT(m, X, c);
+      if (r == 0 && col < nrhs) out[p * nrhs + col] = f;
+    } else {
+      M = mm(Phi, M, J, r, c);
+    }
+  }
+  if (!emit) {
+    double* e = elem + L.wave * 2 * WAVE;
+    e[L.lane] = M, e[WAVE + L.lane] = X;
+  }
+}
+
+// key of a test point in the sort by value: NaN goes first, where qs_pred_locate puts it (interval -1)
+__host__ __device__ inline double sort_key(double x) { return x != x ? -INFINITY : x; }
+
+// sorted position j holds test point order[j] (sorted by value, ties in the caller's order): its interval as
+// qs_pred_locate finds it and, with a grid to build, its place in the merged grid (after the data of the same value)
+__global__ void qs_smp_locate(const double* __restrict__ t, int64_t n, const double* __restrict__ x,
+                              const int64_t* __restrict__ order, int64_t m, int64_t* __restrict__ sidx,
+                              double* __restrict__ gt, int64_t* __restrict__ gp) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const double xv = x[order[j]];
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (t[mid] <= xv) lo = mid + 1; else hi = mid;
+  }
+  sidx[j] = lo - 1;
+  if (gt) gt[lo + j] = xv, gp[lo + j] = n + order[j];
+}
+
+// data point i goes after the test points below it
+__global__ void qs_smp_place(const double* __restrict__ t, int64_t n, const double* __restrict__ x,
+                             const int64_t* __restrict__ order, int64_t m, double* __restrict__ gt,
+                             int64_t* __restrict__ gp) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double tv = t[i];
+  int64_t lo = 0, hi = m;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (x[order[mid]] < tv) lo = mid + 1; else hi = mid;
+  }
+  gt[i + lo] = tv, gp[i + lo] = i;
+}
+
+// e (n x nrhs): eps in, v = r - f(X) - sqrt(noise) eps out
+__global__ void qs_smp_resid(const double* __restrict__ resid, const double* __restrict__ noise,
+                             const double* __restrict__ f, double* __restrict__ e, int64_t n, int64_t nrhs) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n * nrhs) return;
+  const int64_t row = i / nrhs;
+  e[i] = resid[row] - f[i] - sqrt(noise[row]) * e[i];
+}
+
+// v (n x nrhs): v in, the latent sample at the data f(X) + v - noise alpha (= f + K alpha) out
+__global__ void qs_smp_data(const double* __restrict__ noise, const double* __restrict__ f,
+                            const double* __restrict__ alpha, double* __restrict__ v, int64_t n, int64_t nrhs) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n * nrhs) return;
+  v[i] = f[i] + v[i] - noise[i / nrhs] * alpha[i];
+}
+
+// The conditional mean k(x, X) alpha for a block of alpha columns: the F (dir 0) and B (dir 1) recurrences of the
+// prediction over J x 8 blocks, F_n = A_n F_{n-1} + P h alpha_n, B_n = A_{n+1}^T B_{n+1} + h alpha_n, with no
+// congruence beside them.  alpha: n x nrhs.  This lane's entry of step i's transition and of its forcing term:
+__device__ __forceinline__ double cm_step(int dir, const QModel& m, const double* __restrict__ t,
+                                          const double* __restrict__ alpha, int64_t n, int64_t i, int64_t nrhs,
+                                          int64_t col, double Ph_r, int r, int c, double* Phi) {
+  *Phi = phi_entry(m, dir == 0 ? dt_at(t, i) : (i + 1 < n ? t[i + 1] - t[i] : 0.0), r, c);
+  const double a = col < nrhs ? alpha[i * nrhs + col] : 0.0;
+  return (dir == 0 ? Ph_r : (r < m.J ? m.h[r] : 0.0)) * a;
+}
+
+__global__ __launch_bounds__(WAVE * WPB) void qs_cm_fold(int dir, const QModel* __restrict__ mp,
+                                                         const double* __restrict__ t, const double* __restrict__ alpha,
+                                                         int64_t n, int64_t lc, int64_t nchunks, int64_t nrhs,
+                                                         int64_t ncg, double* __restrict__ elem) {
+  const Lane L;
+  if (L.wave >= nchunks * ncg) return;
+  const QModel& m = *mp;
+  const int J = m.J, r = L.r, c = L.c;
+  const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
+  const double Ph_r = Xh(m, m.P[L.lane], r);
+  double M = (r == c && r < J) ? 1.0 : 0.0, V = 0.0, Phi;
+  const Chunk ch(dir != 0, k, nchunks, lc, n);
+  for (int64_t j = 0, len = ch.len(); j < len; ++j) {
+    const double Vf = cm_step(dir, m, t, alpha, n, ch.step(j), nrhs, col, Ph_r, r, c, &Phi);
+    M = lin(dir, Phi, M, J, r, c);
+    V = lin(dir, Phi, V, J, r, c) + Vf;
+  }
+  double* e = elem + L.wave * 2 * WAVE;
+  e[L.lane] = M, e[WAVE + L.lane] = V;
+}
+
+// The gathers, for the test point o whose interval starts dt before it with state F / ends dt after it with state B:
+// out[o, column] (+)= q^T F, q = A_l^T h  /  += (A_r P h)^T B
+__device__ __forceinline__ void cm_serve(int dir, int accumulate, const QModel& m, double X, double dt, double Ph_r,
+                                         int r, int c, bool writes, double* __restrict__ out) {
+  const int J = m.J;
+  const double A = phi_entry(m, dt, r, c);
+  double s = 0.0;
+  if (dir == 0) {
+    const double q_c = hT(m, A, c);
+    for (int k = 0; k < J; ++k) s += sh(q_c, k) * at(X, k, c);
+  } else {
+    double g = 0.0;
+    for (int k = 0; k < J; ++k) g += at(A, r, k) * sh(Ph_r, k * 8);
+    for (int k = 0; k < J; ++k) s += sh(g, k * 8) * at(X, k, c);
+  }
+  if (writes) *out = (accumulate ? *out : 0.0) + s;
+}
+
+// sidx, order, xt as in qs_pred_emit; out: mt x nrhs.  dir 0 writes (accumulate: adds to) its part, dir 1 adds its own.
+__global__ __launch_bounds__(WAVE * WPB) void qs_cm_emit(int dir, int accumulate, const QModel* __restrict__ mp,
+                                                         const double* __restrict__ t, const double* __restrict__ alpha,
+                                                         int64_t n, int64_t lc, int64_t nchunks, int64_t nrhs,
+                                                         int64_t ncg, const double* __restrict__ prefix,
+                                                         const double* __restrict__ xt,
+                                                         const int64_t* __restrict__ sidx,
+                                                         const int64_t* __restrict__ order, int64_t mt,
+                                                         double* __restrict__ out) {
+  const Lane L;
+  if (L.wave >= nchunks * ncg) return;
+  const QModel& m = *mp;
+  const int J = m.J, r = L.r, c = L.c;
+  const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
+  const bool writes = r == 0 && col < nrhs;
+  const double Ph_r = Xh(m, m.P[L.lane], r);
+  double X = prefix[L.wave * WAVE + L.lane], Phi;
+  const Chunk ch(dir != 0, k, nchunks, lc, n);
+  const int64_t n0 = ch.n0, n1 = ch.n1;
+  out += writes ? col : 0;
+  if (dir == 0) {
+    int64_t p = k == 0 ? 0 : lower_bound_idx(sidx, mt, n0);
+    for (; p < mt && sidx[p] < n0; ++p)
+      cm_serve(0, accumulate, m, X, 0.0, Ph_r, r, c, writes, out + order[p] * nrhs);
+    for (int64_t i = n0; i < n1; ++i) {
+      const double Vf = cm_step(0, m, t, alpha, n, i, nrhs, col, Ph_r, r, c, &Phi);
+      X = lin(0, Phi, X, J, r, c) + Vf;
+      for (; p < mt && sidx[p] == i; ++p) {
+        const int64_t o = order[p];
+        cm_serve(0, accumulate, m, X, xt[o] - t[i], Ph_r, r, c, writes, out + o * nrhs);
+      }
+    }
+  } else {
+    int64_t p = lower_bound_idx(sidx, mt, n1 - 1);
+    if (k == 0)
+      for (int64_t e = mt; e-- > p;) cm_serve(1, 1, m, X, 0.0, Ph_r, r, c, writes, out + order[e] * nrhs);
+    for (int64_t i = n1 - 1; i >= n0; --i) {
+      const double Vf = cm_step(1, m, t, alpha, n, i, nrhs, col, Ph_r, r, c, &Phi);
+      X = lin(1, Phi, X, J, r, c) + Vf;
+      for (; p > 0 && sidx[p - 1] == i - 1; --p) {
+        const int64_t o = order[p - 1];
+        cm_serve(1, 1, m, X, t[i] - xt[o], Ph_r, r, c, writes, out + o * nrhs);
+      }
+    }
+  }
+}
+
 // What qs_finish sums for member `mem`: a[0..na), b[0..nb) and the minimum of bad[0..na), as offsets from its pointers
 struct Sums {
   int64_t na, nb, a, b, bad;
@@ -1301,6 +1526,9 @@ struct tgp_qsep {
   // batches of models: the models and every array of one launch chain (the capped scratch; batch_layout)
   double* bat = nullptr;
   int64_t bat_elems = 0;
+  // posterior samples and the conditional mean of many columns: the arrays of one pass of columns (the capped scratch)
+  double* smp = nullptr;
+  int64_t smp_elems = 0;
 };
 
 // A set of series, each on coordinates of its own: the concatenated t and the extent table stay resident
@@ -2283,7 +2511,176 @@ int predict_guard(tgp_qsep* q, const double* v_host, int64_t m, bool xtest_ok, i
   return TGP_OK;
 }
 
-#define QS_GUARD(q)                                                                   \
+// ---- posterior samples and the conditional mean of many columns ------------------------------------------------------
+// Columns are served in passes of at most SAMPLE_MAX_COLS; a pass holds, in doubles per column, xi (G J, later z and
+// alpha: J counts as at least 2 so that both fit), f (G) and eps, later v (G): G (max(J, 2) + 2) with G = n + m, and is
+// made smaller until that and the scans' work space stay under SAMPLE_SCRATCH_BYTES.  A function of (n, m, J, nrhs).
+constexpr int64_t SAMPLE_MAX_COLS = 64;
+constexpr int64_t SAMPLE_SCRATCH_BYTES = int64_t(1) << 30;
+
+int64_t sample_pass_doubles(int64_t G, int64_t nchunks, int64_t J, int64_t cols) {
+  return G * (std::max<int64_t>(J, 2) + 2) * cols + scan_work<ScanAffine>(nchunks, ceil_div(cols, 8));
+}
+
+// columns per pass; 0: one column alone exceeds the cap
+int64_t sample_pass_cols(int64_t G, int64_t nchunks, int64_t J, int64_t nrhs) {
+  const int64_t cap = SAMPLE_SCRATCH_BYTES / int64_t(sizeof(double));
+  int64_t cols = std::min(nrhs, SAMPLE_MAX_COLS);
+  while (cols > 0 && sample_pass_doubles(G, nchunks, J, cols) > cap) cols -= cols > 8 ? (cols % 8 ? cols % 8 : 8) : 1;
+  return cols;
+}
+
+// columns [c0, c0 + cols) of a host array of `rows` x nrhs to / from a device array of rows x cols
+int copy_cols(hipStream_t st, bool up, double* dev, const double* host, int64_t rows, int64_t nrhs, int64_t c0,
+              int64_t cols) {
+  if (rows == 0 || cols == 0) return TGP_OK;
+  const size_t hp = size_t(nrhs) * sizeof(double), dp = size_t(cols) * sizeof(double);
+  if (cols == nrhs) {  // the whole array: one contiguous copy
+    if (up)
+      TGP_HIP_TRY(hipMemcpyAsync(dev, host, size_t(rows) * dp, hipMemcpyHostToDevice, st));
+    else
+      TGP_HIP_TRY(hipMemcpyAsync(const_cast<double*>(host), dev, size_t(rows) * dp, hipMemcpyDeviceToHost, st));
+    return TGP_OK;
+  }
+  if (up)
+    TGP_HIP_TRY(hipMemcpy2DAsync(dev, dp, host + c0, hp, dp, size_t(rows), hipMemcpyHostToDevice, st));
+  else
+    TGP_HIP_TRY(hipMemcpy2DAsync(const_cast<double*>(host) + c0, hp, dev, dp, dp, size_t(rows), hipMemcpyDeviceToHost,
+                                 st));
+  return TGP_OK;
+}
+
+// The test points of one call on the device: pred: xt (m) | gt (G, with a grid) | `extra` doubles for the caller;
+// pidx: sidx (m) | order (m) | gp (G).
+// They are sorted by value on the host (stable; NaN first), their intervals located on the device; with `grid` the
+// merged grid of data and test points is built too.
+struct TestPoints {
+  double *xt = nullptr, *gt = nullptr;
+  int64_t *sidx = nullptr, *order = nullptr, *gp = nullptr;
+};
+
+int place_test_points(tgp_qsep* q, int64_t m, const double* xtest_host, bool grid, int64_t extra, TestPoints* tp) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, G = n + m;
+  TGP_TRY(grow(&q->pred, &q->pred_elems, m + (grid ? G : 0) + extra));
+  TGP_TRY(grow(&q->pidx, &q->pidx_elems, 2 * m + (grid ? G : 0)));
+  tp->xt = q->pred, tp->gt = grid ? q->pred + m : nullptr;
+  tp->sidx = q->pidx, tp->order = q->pidx + m, tp->gp = grid ? q->pidx + 2 * m : nullptr;
+  if (m == 0) return TGP_OK;
+  std::vector<int64_t> h_order(static_cast<size_t>(m));
+  for (int64_t j = 0; j < m; ++j) h_order[size_t(j)] = j;
+  std::stable_sort(h_order.begin(), h_order.end(), [&](int64_t a, int64_t b) {
+    return sort_key(xtest_host[a]) < sort_key(xtest_host[b]);
+  });
+  TGP_HIP_TRY(hipMemcpyAsync(tp->xt, xtest_host, size_t(m) * sizeof(double), hipMemcpyHostToDevice, st));
+  TGP_HIP_TRY(hipMemcpyAsync(tp->order, h_order.data(), size_t(m) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));  // h_order leaves scope
+  qs_smp_locate<<<unsigned((m + 255) / 256), 256, 0, st>>>(q->t, n, tp->xt, tp->order, m, tp->sidx, tp->gt, tp->gp);
+  if (grid) qs_smp_place<<<unsigned((n + 255) / 256), 256, 0, st>>>(q->t, n, tp->xt, tp->order, m, tp->gt, tp->gp);
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
+// out (m x cols) = (accumulate ? out : 0) + k(x, X) alpha for the cols columns of alpha (n x cols); q->work is grown
+int cond_mean_cols(tgp_qsep* q, const double* alpha, int64_t cols, int64_t m, const TestPoints& tp, int accumulate,
+                   double* out) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, nc = q->nchunks, ncg = ceil_div(cols, 8);
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanAffine>(nc, ncg)));
+  const unsigned blocks = unsigned(blocks_for(nc * ncg));
+  for (int dir = 0; dir < 2; ++dir) {
+    qs_cm_fold<<<blocks, WAVE * WPB, 0, st>>>(dir, q->model, q->t, alpha, n, q->lc, nc, cols, ncg, q->work);
+    double* prefix = nullptr;
+    TGP_TRY(run_scan<ScanAffine>(q->model, st, nc, ncg, q->work, &prefix));
+    qs_cm_emit<<<blocks, WAVE * WPB, 0, st>>>(dir, accumulate, q->model, q->t, alpha, n, q->lc, nc, cols, ncg, prefix,
+                                              tp.xt, tp.sidx, tp.order, m, out);
+  }
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
+void fill_nan(double* a, int64_t len) {
+  for (int64_t j = 0; a && j < len; ++j) a[j] = NAN;
+}
+
+int sample(tgp_qsep* q, const double* resid_host, int64_t m, const double* xtest_host, int64_t nrhs,
+           const double* xi_host, const double* eps_host, double* data_host, double* test_host, int32_t* npasses) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, J = q->J, G = n + m;
+  const int64_t lcG = chunk_length(G), ncG = ceil_div(G, lcG);
+  const int64_t pc = sample_pass_cols(G, std::max(ncG, q->nchunks), J, nrhs);
+  TGP_ARG_CHECK(pc >= 1, "one column of samples at %lld points needs %lld doubles of scratch and exceeds its cap of %lld "
+                "bytes", (long long)G, (long long)sample_pass_doubles(G, std::max(ncG, q->nchunks), J, 1),
+                (long long)SAMPLE_SCRATCH_BYTES);
+  for (int64_t j = 0; j < m; ++j)
+    TGP_ARG_CHECK(std::isfinite(xtest_host[j]), "test point %lld is not finite: a sample is a recurrence over all points",
+                  (long long)j);
+  TestPoints tp;
+  TGP_TRY(place_test_points(q, m, xtest_host, m > 0, n, &tp));
+  double* resid = q->pred + m + (m > 0 ? G : 0);
+  const double* gt = m > 0 ? tp.gt : q->t;
+  TGP_HIP_TRY(hipMemcpyAsync(resid, resid_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+  const int64_t Jp = std::max<int64_t>(J, 2);
+  TGP_TRY(grow(&q->smp, &q->smp_elems, G * (Jp + 2) * pc));
+  TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanAffine>(std::max(ncG, q->nchunks), ceil_div(pc, 8))));
+  int32_t passes = 0;
+  for (int64_t c0 = 0; c0 < nrhs; c0 += pc, ++passes) {
+    const int64_t cols = std::min(pc, nrhs - c0), ncg = ceil_div(cols, 8);
+    double *xi = q->smp, *f = xi + G * Jp * cols, *e = f + G * cols;  // z and alpha take xi's place once it is read
+    double *z = xi, *alpha = xi + n * cols;
+    TGP_TRY(copy_cols(st, true, xi, xi_host, G * J, nrhs, c0, cols));
+    TGP_TRY(copy_cols(st, true, e, eps_host, n, nrhs, c0, cols));
+    const unsigned blocks = unsigned(blocks_for(ncG * ncg)), eblocks = unsigned((n * cols + 255) / 256);
+    qs_prior<<<blocks, WAVE * WPB, 0, st>>>(0, q->model, gt, tp.gp, G, lcG, ncG, xi, cols, ncg, nullptr, q->work,
+                                            nullptr);
+    double* prefix = nullptr;
+    TGP_TRY(run_scan<ScanAffine>(q->model, st, ncG, ncg, q->work, &prefix));
+    qs_prior<<<blocks, WAVE * WPB, 0, st>>>(1, q->model, gt, tp.gp, G, lcG, ncG, xi, cols, ncg, prefix, nullptr, f);
+    qs_smp_resid<<<eblocks, 256, 0, st>>>(resid, q->noise, f, e, n, cols);
+    TGP_HIP_TRY(hipGetLastError());
+    TGP_TRY(affine(q, TGP_QS_FWD, cols, e, z, nullptr));
+    TGP_TRY(affine(q, TGP_QS_BWD, cols, z, alpha, nullptr));
+    if (test_host && m > 0) {
+      TGP_TRY(cond_mean_cols(q, alpha, cols, m, tp, 1, f + n * cols));
+      TGP_TRY(copy_cols(st, false, f + n * cols, test_host, m, nrhs, c0, cols));
+    }
+    if (data_host) {
+      qs_smp_data<<<eblocks, 256, 0, st>>>(q->noise, f, alpha, e, n, cols);
+      TGP_HIP_TRY(hipGetLastError());
+      TGP_TRY(copy_cols(st, false, e, data_host, n, nrhs, c0, cols));
+    }
+  }
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  if (npasses) *npasses = passes;
+  return TGP_OK;
+}
+
+int predict_mean(tgp_qsep* q, int64_t nrhs, const double* v_host, int v_is_alpha, int64_t m, const double* xtest_host,
+                 double* mean_host) {
+  hipStream_t st = q->ctx->stream;
+  const int64_t n = q->n, J = q->J;
+  const int64_t pc = sample_pass_cols(n + m, q->nchunks, J, nrhs);
+  TGP_ARG_CHECK(pc >= 1, "one column of the conditional mean at %lld points exceeds the scratch cap of %lld bytes",
+                (long long)(n + m), (long long)SAMPLE_SCRATCH_BYTES);
+  TestPoints tp;
+  TGP_TRY(place_test_points(q, m, xtest_host, false, 0, &tp));
+  TGP_TRY(grow(&q->smp, &q->smp_elems, (3 * n + m) * pc));
+  for (int64_t c0 = 0; c0 < nrhs; c0 += pc) {
+    const int64_t cols = std::min(pc, nrhs - c0);
+    double *a = q->smp, *z = a + n * cols, *alpha = z + n * cols, *mean = alpha + n * cols;
+    TGP_TRY(copy_cols(st, true, v_is_alpha ? alpha : a, v_host, n, nrhs, c0, cols));
+    if (!v_is_alpha) {
+      TGP_TRY(affine(q, TGP_QS_FWD, cols, a, z, nullptr));
+      TGP_TRY(affine(q, TGP_QS_BWD, cols, z, alpha, nullptr));
+    }
+    TGP_TRY(cond_mean_cols(q, alpha, cols, m, tp, 0, mean));
+    TGP_TRY(copy_cols(st, false, mean, mean_host, m, nrhs, c0, cols));
+  }
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  return TGP_OK;
+}
+
+#define QS_GUARD(q)                                                                 \
   TGP_ARG_CHECK((q) != nullptr && (q)->ctx != nullptr, "null quasiseparable handle"); \
   std::unique_lock<std::recursive_mutex> _tgp_lock((q)->ctx->mu);                     \
   TGP_HIP_TRY(hipSetDevice((q)->ctx->device))
@@ -2330,7 +2727,7 @@ int tgp_qsep_destroy(tgp_qsep* q) {
   }
   void* bufs[] = {q->model, q->t,    q->noise, q->c,     q->w,    q->io,   q->io2,  q->work, q->red,
                   q->bad,   q->pred, q->pidx,  q->gkeep, q->gdir, q->gtan, q->gred, q->gout, q->gvec,
-                  q->bat};
+                  q->bat,   q->smp};
   for (void* b : bufs)
     if (b) hipFree(b);
   delete q;
@@ -2676,6 +3073,40 @@ int tgp_qsep_predict_terms(tgp_qsep* q, const double* v_host, int32_t v_is_alpha
     for (int j = 0; j < J; ++j) q->host_g[k * QJ + j] = g_host[k * J + j];
   TGP_HIP_TRY(hipMemcpyAsync(q->gvec, q->host_g, sizeof(q->host_g), hipMemcpyHostToDevice, q->ctx->stream));
   return predict(q, v_host, v_is_alpha, m, xtest_host, nterms, q->gvec, mean_host, var_host);
+}
+
+int tgp_qsep_sample(tgp_qsep* q, const double* resid_host, int64_t m, const double* xtest_host, int64_t nrhs,
+                    const double* xi_host, const double* eps_host, double* data_host, double* test_host,
+                    int32_t* npasses) {
+  QS_GUARD(q);
+  TGP_ARG_CHECK(q->factored, "the quasiseparable factor has not been computed (call tgp_qsep_factor first)");
+  TGP_ARG_CHECK(m >= 0 && nrhs >= 0, "negative number of test points or columns (%lld, %lld)", (long long)m,
+                (long long)nrhs);
+  if (npasses) *npasses = 0;
+  if (nrhs == 0 || (!data_host && (!test_host || m == 0))) return TGP_OK;
+  TGP_ARG_CHECK(m == 0 || xtest_host, "null test points");
+  TGP_ARG_CHECK(resid_host && xi_host && eps_host, "null array");
+  if (q->info != 0) {  // failed factor: c and w are not a factor of anything
+    fill_nan(data_host, q->n * nrhs);
+    fill_nan(test_host, m * nrhs);
+    return TGP_OK;
+  }
+  return sample(q, resid_host, m, xtest_host, nrhs, xi_host, eps_host, data_host, test_host, npasses);
+}
+
+int tgp_qsep_predict_mean(tgp_qsep* q, int64_t nrhs, const double* v_host, int32_t v_is_alpha, int64_t m,
+                          const double* xtest_host, double* mean_host) {
+  QS_GUARD(q);
+  TGP_ARG_CHECK(q->factored, "the quasiseparable factor has not been computed (call tgp_qsep_factor first)");
+  TGP_ARG_CHECK(m >= 0 && nrhs >= 0, "negative number of test points or columns (%lld, %lld)", (long long)m,
+                (long long)nrhs);
+  if (nrhs == 0 || m == 0) return TGP_OK;
+  TGP_ARG_CHECK(v_host && xtest_host && mean_host, "null array");
+  if (q->info != 0) {
+    fill_nan(mean_host, m * nrhs);
+    return TGP_OK;
+  }
+  return predict_mean(q, nrhs, v_host, v_is_alpha, m, xtest_host, mean_host);
 }
 
 }  // extern "C"

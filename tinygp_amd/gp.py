@@ -139,6 +139,32 @@ class GaussianProcess:
         out = self.solver.dot_triangular(z)
         return self.mean + np.moveaxis(out, 0, -1)
 
+    def sample_conditional(self, y, X_test=None, *, key, shape=None, include_mean: bool = True):
+        """Draw samples of the latent process from the posterior given ``y``, at ``X_test`` (``None``: at the data), in
+        O(N + M) per draw: what ``condition(y, X_test).gp.sample(key)`` draws from, without the M x M covariance and
+        its factorisation, and without the noise or jitter that route adds.
+
+        ``key``: an ``int`` seed or a ``numpy.random.Generator``, as in :meth:`sample`; the standard normals ``xi``
+        (N + M, J, R), then ``eps`` (N, R), are drawn from it.  Returns shape ``shape + (M,)``, the mean function at
+        the output points added when ``include_mean``.  Needs a solver with ``sample_conditional``
+        (:class:`solvers.QuasisepSolver`)."""
+        fused = getattr(self.solver, "sample_conditional", None)
+        if fused is None:
+            raise TypeError(f"{type(self.solver).__name__} has no sample_conditional: posterior samples in O(N + M) "
+                            "are drawn by QuasisepSolver (a kernels.quasisep kernel on sorted 1-D inputs)")
+        rng = key if isinstance(key, np.random.Generator) else np.random.default_rng(key)
+        shape = () if shape is None else tuple(shape)
+        R = int(np.prod(shape, dtype=np.int64))
+        n, m = self.num_data, 0 if X_test is None else _device.num_points(X_test)
+        resid = self._residual(y)
+        xi = rng.standard_normal((n + m, self.solver.state_dimension, R))
+        eps = rng.standard_normal((n, R))
+        out = np.asarray(fused(resid, X_test, xi=xi, eps=eps), dtype=self.dtype)
+        out = np.moveaxis(out, 0, -1).reshape(shape + (out.shape[0],))
+        if include_mean:
+            out = out + (self.loc if X_test is None else means.evaluate_mean(self.mean_function, X_test, m, self.dtype))
+        return out.astype(self.dtype, copy=False)
+
     # -- reference gp.py:126-138, 313-320 ---------------------------------------------
     def log_probability(self, y):
         """Marginal log-probability of ``y`` under this multivariate normal."""

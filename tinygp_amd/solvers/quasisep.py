@@ -6,6 +6,7 @@ factor described by O(N J) numbers (``c_n``, ``w_n``; ``tests/_quasisep_np.py`` 
 factorisation, both triangular solves and ``L @ z`` are chunked reduce-then-scan recurrences in
 ``csrc/qsep.hip``, and so are the conditional mean and variance at M test points (``predict_mean_var``; O(N + M),
 nothing of size N x M), the same for every term of a sum at once (``predict_terms``; also at the data themselves),
+posterior draws by Matheron's rule (``sample_conditional``; O(N + M) per draw),
 the gradient of the log-probability (``value_and_grad``; O(N) per parameter) and the log-probabilities of many
 hyper-parameter sets over the one series in one launch chain (``log_probability_batch``; with their gradients:
 ``value_and_grad_batch``).  :class:`QuasisepSeriesSet` evaluates many series, each on coordinates of its own, in one
@@ -192,6 +193,8 @@ class QuasisepSolver(Solver):
         the solver's own kernel at test points, on the host otherwise."""
         if kernel is self.kernel and X_out is not self.X and np.ndim(alpha) == 1:
             return self._predict(alpha, True, X_out, True, False)[0]
+        if kernel is self.kernel and X_out is not self.X and np.ndim(alpha) == 2:
+            return self._predict_mean_cols(alpha, True, X_out)
         return kernel.matmul(X_out, self.X, alpha)
 
     # -- prediction at test points -------------------------------------------------------
@@ -210,13 +213,32 @@ class QuasisepSolver(Solver):
         cast = lambda a: None if a is None else a.astype(self.dtype, copy=False)  # noqa: E731
         return cast(mean), cast(var)
 
+    def _predict_mean_cols(self, v, is_alpha, X_test):
+        """The conditional mean for the R columns of ``v`` (N, R) at once (``tgp_qsep_predict_mean``): (M, R)."""
+        from tinygp_amd.kernels.quasisep import _coords
+
+        x = _f64(_coords(X_test))
+        v = np.asarray(v)
+        if v.ndim != 2 or v.shape[0] != self.n:
+            raise ValueError(f"a block of residuals must have shape ({self.n}, R); got {v.shape}")
+        self._ensure_factor()
+        vv = _f64(v)
+        mean = np.empty((x.shape[0], vv.shape[1]))
+        _ffi.check(_ffi.lib().tgp_qsep_predict_mean(self._handle, vv.shape[1], _ffi.ptr(vv), int(bool(is_alpha)),
+                                                    x.shape[0], _ffi.ptr(x), _ffi.ptr(mean)), "tgp_qsep_predict_mean")
+        return mean.astype(self.dtype, copy=False)
+
     def predict_mean_var(self, resid, X_test, *, return_var: bool = True):
         """Conditional mean ``k(X_test, X) K^-1 resid`` and variance ``k(x, x) - k(x, X) K^-1 k(X, x)`` (no noise
         added) at M test points, in O((N + M) J^2 + M log N) on the device (``csrc/qsep.hip``, ``qs_pred_*``).
 
         ``X_test``: shape (M,) or (M, 1), in any order and anywhere relative to the data; M = 0 is allowed.
         Returns ``(mean, var)``, or the mean alone with ``return_var=False``.  After a failed factor both are NaN.
+        With ``return_var=False`` ``resid`` may also hold R residuals as the columns of an (N, R) array: the means come
+        back as (M, R) from one pair of scans per 8 columns (``qs_cm_*``).
         """
+        if np.ndim(resid) == 2 and not return_var:
+            return self._predict_mean_cols(resid, False, X_test)
         mean, var = self._predict(resid, False, X_test, True, return_var)
         return (mean, var) if return_var else mean
 
@@ -260,6 +282,54 @@ class QuasisepSolver(Solver):
                 vars_[b:b + len(g)] = var
         means = means.astype(self.dtype, copy=False)
         return (means, vars_.astype(self.dtype, copy=False)) if return_var else means
+
+    # -- posterior samples ------------------------------------------------------------------
+    @property
+    def state_dimension(self) -> int:
+        """J: the number of standard normals a sample takes per point."""
+        return self._ssm.J
+
+    def sample_conditional(self, resid, X_test=None, *, xi, eps, return_data: bool = False):
+        """Draws of the latent process conditioned on ``resid``, at M test points and at the data, in O((N + M) J^3) per
+        draw on the device (``tgp_qsep_sample``; Matheron's rule: a prior draw over the merged grid of data and test
+        points by the state-space recurrence, then the conditional mean of what the data say about it).  Nothing of
+        size N x M or M x M is formed.  No noise or jitter is added: the result is the latent process.
+
+        The draw is a function of the standard normals passed in: ``xi`` of shape (N + M, J, R), row p for point p of
+        ``[X; X_test]``, and ``eps`` of shape (N, R); ``xi`` (N + M, J) and ``eps`` (N,) give 1-D results.  Column c does
+        not depend on R or on the other columns, bit for bit.  ``X_test``: (M,) or (M, 1), any order, anywhere relative
+        to the data, finite.  Returns the samples at the test points (M, R), or ``(data (N, R), test (M, R))`` with
+        ``return_data``; ``X_test=None`` returns the (N, R) samples at the data.  After a failed factor the result is
+        NaN.  fp32 inputs are computed in fp64 and returned as fp32."""
+        from tinygp_amd.kernels.quasisep import _coords
+
+        x = None if X_test is None else _f64(_coords(X_test))
+        n, m, J = self.n, 0 if x is None else x.shape[0], self._ssm.J
+        xi, eps = np.asarray(xi), np.asarray(eps)
+        one = xi.ndim == 2
+        R = 1 if one else (xi.shape[2] if xi.ndim == 3 else -1)
+        if xi.ndim not in (2, 3) or xi.shape[:2] != (n + m, J):
+            raise ValueError(f"xi must have shape ({n + m}, {J}) or ({n + m}, {J}, R); got {xi.shape}")
+        if eps.shape != ((n,) if one else (n, R)):
+            raise ValueError(f"eps must have shape {(n,) if one else (n, R)} beside xi of shape {xi.shape}; got "
+                             f"{eps.shape}")
+        if x is not None and not np.all(np.isfinite(x)):
+            raise ValueError("X_test must be finite: a sample is a recurrence over all points")
+        r = _f64(resid, (n,))
+        self._ensure_factor()
+        xi, eps = _f64(xi.reshape(n + m, J, R)), _f64(eps.reshape(n, R))
+        want_data = return_data or x is None
+        data = np.empty((n, R)) if want_data else None
+        test = None if x is None else np.empty((m, R))
+        passes = C.c_int32(0)
+        _ffi.check(_ffi.lib().tgp_qsep_sample(self._handle, _ffi.ptr(r), m, _ffi.ptr(x), R, _ffi.ptr(xi), _ffi.ptr(eps),
+                                              _ffi.ptr(data), _ffi.ptr(test), C.byref(passes)), "tgp_qsep_sample")
+        self.sample_passes = int(passes.value)  # passes of columns the last call took
+        shape = lambda a: None if a is None else (a[:, 0] if one else a).astype(self.dtype, copy=False)  # noqa: E731
+        data, test = shape(data), shape(test)
+        if x is None:
+            return data
+        return (data, test) if return_data else test
 
     # -- fused entry points used by GaussianProcess ------------------------------------
     def log_probability(self, resid):
