@@ -352,6 +352,25 @@ int tgp_solver_device_factor(tgp_solver* s, void** L_dev, int64_t* n_pad);
  * priority stream overlap at large N: their sum can exceed the evaluation, the union cannot) */
 int tgp_solver_timings(tgp_solver* s, double* ms, int n);
 
+/* ---- batches of SMALL dense problems: one workgroup per member, one launch (csrc/small.hip) --------------------
+ * What the reference's users write as jax.vmap around the function that builds the GP and returns
+ * gp.log_probability(y) (gp.py:126-138): nb members, each with a kernel program, n[b] <= TGP_SMALL_MAX_N points of d
+ * coordinates, a noise diagonal and a residual of its own.  fp64.  Host pointers; blocking.
+ *   progs / prog_off   the members' postfix programs one after another; member b owns ops prog_off[b] .. prog_off[b + 1]
+ *                      (members may differ in structure)
+ *   x_off / n          member b reads rows x_off[b] .. x_off[b] + n[b] of X_host (x_rows, d) row-major; two members may
+ *                      name the same rows (shared coordinates)
+ *   vec_off            member b's noise diagonal and residual are the n[b] entries at vec_off[b] of noise_host / resid_host
+ *   info_host / out_host   per member: 0 or the 1-based index of the first pivot that is not > 0 (the value is then NaN),
+ *                      and -0.5 |L^-1 r|^2 - sum log L_pp - n/2 log(2 pi), not clamped.  A member's value depends on that
+ *                      member's data alone.
+ * TGP_E_ARG: n[b] outside 1 .. TGP_SMALL_MAX_N, d outside 1 .. TGP_MAX_DIM, an invalid program, rows outside X, a
+ * negative offset.  nb = 0 returns TGP_OK and touches nothing. */
+#define TGP_SMALL_MAX_N 192
+int tgp_small_logprob(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off, const int64_t* x_off,
+                      const int32_t* n, int32_t d, const double* X_host, int64_t x_rows, const int64_t* vec_off,
+                      const double* noise_host, const double* resid_host, int32_t* info_host, double* out_host);
+
 /* ---- block-cyclic column Cholesky over the GPUs of one node (BASELINE configs 4 / 5) ----------
  * The reference has NO multi-device code; these entry points are one RANK's share
  * of the same path -- `DirectSolver.__init__` (solvers/direct.py:49-53: assembly + cholesky),

@@ -98,6 +98,7 @@ SIGNATURES = {
     "tgp_solver_get_factor": [_vp, _vp],
     "tgp_solver_device_factor": [_vp, _pvp, _pi64],
     "tgp_solver_timings": [_vp, _pdbl, _int],
+    "tgp_small_logprob": [_vp, _i32, _vp, _pi32, _pi64, _pi32, _i32, _vp, _i64, _pi64, _vp, _vp, _pi32, _pdbl],
     "tgp_trace_factor": [_i64, C.c_char_p, _i32, _pi64, _i64, _pi64],
     "tgp_chain_stamps": [_vp, _pi64, _i64, _pi64],
     "tgp_chain_task": [_i64, _i64, _i64, _i64, _i64, _pi32, _pi64],
@@ -178,6 +179,7 @@ SIGNATURES = {
 
 
 ABI_VERSION = 6  # TGP_ABI_VERSION of include/tgp_hip.h
+SMALL_MAX_N = 192  # TGP_SMALL_MAX_N: the largest member of tgp_small_logprob (one workgroup, the matrix in LDS)
 
 
 def _mapped_hip_runtimes() -> list[str]:

@@ -246,6 +246,7 @@ struct tgp_ctx {
   void* d_gemm_ws = nullptr;  // split-tail workspace of the trailing update: partial tiles + per-tile counters
   size_t gemm_ws_bytes = 0;
   void* d_work = nullptr;  // generic workspace, grown on demand
+  bool small_lds_raised = false;  // small.hip: the one-workgroup kernel's dynamic-LDS limit has been raised on this device
   size_t work_bytes = 0;
   // profiling (option "profile"): event pairs around trailing-update launches
   std::vector<hipEvent_t> ev_pool;

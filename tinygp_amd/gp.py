@@ -179,15 +179,21 @@ class GaussianProcess:
         (the reference's ``jax.vmap`` over the function that builds the GP): the walkers of an ensemble sampler, the
         starts of an optimiser, a grid over a period.
 
-        ``kernels``: B kernels of one structure.  ``diags``: ``None`` (this GP's noise), (B,) one value per member or
-        (B, N) diagonals.  ``means``: ``None`` (this GP's mean vector), (B,) constants or (B, N) vectors.  Returns B
-        values; member b equals ``GaussianProcess(kernels[b], X, diag=diags[b], mean=means[b]).log_probability(y)``
-        to the bit.  Needs a solver with ``log_probability_batch`` (:class:`tinygp_amd.solvers.QuasisepSolver`)."""
+        ``kernels``: B kernels.  ``diags``: ``None`` (this GP's noise), (B,) one value per member or (B, N) diagonals.
+        ``means``: ``None`` (this GP's mean vector), (B,) constants or (B, N) vectors.  Returns B values; member b is
+        ``GaussianProcess(kernels[b], X, diag=diags[b], mean=means[b]).log_probability(y)``.
+
+        On a :class:`tinygp_amd.solvers.QuasisepSolver` the kernels are ``kernels.quasisep`` models of one structure
+        and every member equals that call to the bit.  On a :class:`tinygp_amd.solvers.DirectSolver` (the dense path)
+        the members may differ in structure -- leaves, sums, products, metrics, input transforms -- and each is held to
+        the project's 1e-8 bar against that call, not to the bits of a single call: up to ``TGP_SMALL_MAX_N`` points a
+        workgroup evaluates a whole member in LDS (``csrc/small.hip``), above it the members are evaluated one by one.
+        Needs a solver with ``log_probability_batch``."""
         fused = getattr(self.solver, "log_probability_batch", None)
         if fused is None:
             raise NotImplementedError(f"{type(self.solver).__name__} has no log_probability_batch: batches of models "
                                       "are evaluated by QuasisepSolver (a kernels.quasisep kernel on sorted 1-D "
-                                      "inputs)")
+                                      "inputs) and by DirectSolver (any other kernel)")
         kernels = list(kernels)
         return fused(kernels, *self._batch_inputs(y, len(kernels), diags, means))
 

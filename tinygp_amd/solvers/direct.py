@@ -337,6 +337,58 @@ class DirectSolver(Solver):
             v = -np.inf
         return self.dtype.type(v)
 
+    def log_probability_batch(self, kernels, resid, noise=None, *, return_info: bool = False):
+        """The log-probabilities of B models over this solver's coordinates, evaluated together on the device
+        (``tgp_small_logprob``, ``csrc/small.hip``: one workgroup per member assembles, factors and solves its matrix in
+        LDS, so that a batch of small problems fills the card where a loop of single calls is launch-bound).
+
+        ``kernels``: a sequence of B kernels; the members may differ in structure and in their input transforms.
+        ``resid``: (N,) shared or (B, N).  ``noise``: ``None`` (the solver's own diagonal), (N,) shared or (B, N)
+        diagonals.  Returns B values; a failed or non-finite member gives ``-inf``.  With ``return_info`` also the B
+        ``info`` values.  fp32 inputs are computed in fp64 and returned as fp32.  The solver's own kernel and factor
+        are neither used nor changed.
+
+        Each member is held to the project's 1e-8 bar against :meth:`log_probability` of a solver built with that
+        member's kernel and noise, not to its bits (another summation order); its value depends on its own data alone,
+        whatever the batch around it.  With more than ``TGP_SMALL_MAX_N`` points, a noise model that is not
+        :class:`~tinygp_amd.noise.Diagonal`, or a member without a device program (``kernels.Custom``, more than 16
+        dimensions, pytree inputs) every member is evaluated on a fresh single :class:`DirectSolver`, one after another.
+        ``kernels.quasisep`` members raise ``NotImplementedError``: their batches are ``QuasisepSolver``'s."""
+        from tinygp_amd.solvers import small
+
+        kernels = list(kernels)
+        nb = len(kernels)
+        if nb == 0:
+            out = np.empty(0, dtype=self.dtype)
+            return (out, np.empty(0, dtype=np.int32)) if return_info else out
+        small.reject_quasisep(kernels)
+
+        def rows(a, what):  # (N,) shared or (B, N) one per member -> (B, N)
+            a = np.asarray(a)
+            if a.shape not in ((self.n,), (nb, self.n)):
+                raise ValueError(f"{what} must have shape ({self.n},) or ({nb}, {self.n}); got {a.shape}")
+            return np.broadcast_to(a, (nb, self.n))
+
+        r = rows(resid, "resid")
+        d = None if noise is None else rows(noise, "noise")
+        lowered = [small.lower_member(k, self.X) for k in kernels]
+        out, info = np.empty(nb), np.zeros(nb, dtype=np.int32)
+        if small.batch_route(self.n, d is not None or isinstance(self.noise, Diagonal), lowered):
+            members = [(low[0], low[1], self._noise_diag if d is None else d[b], r[b]) for b, low in enumerate(lowered)]
+            out, info = small.run_packed(self._ctx, small.pack_members(members))
+        else:  # today's arithmetic, member by member: the interface does not change with N
+            for b, kernel in enumerate(kernels):
+                nz = self.noise if d is None else Diagonal(diag=np.asarray(d[b], dtype=self.dtype))
+                single = DirectSolver(kernel, self.X, nz, ctx=self._ctx)
+                try:
+                    out[b] = single.log_probability(np.asarray(r[b], dtype=self.dtype))
+                    info[b] = single.info
+                finally:
+                    single.close()
+        out[(info != 0) | ~np.isfinite(out)] = -np.inf
+        out = out.astype(self.dtype, copy=False)
+        return (out, info) if return_info else out
+
     def log_probability_and_grad(self, resid):
         """``(log_probability, grads)`` with ``grads = {"kernel": [...], "noise_diag": (N,),
         "mean": (N,), "transform": ...}``: derivatives with respect to ``kernel.parameters()`` (same order), to

@@ -1,0 +1,249 @@
+"""Batches of small dense GPs in one launch (``tgp_small_logprob``, ``csrc/small.hip``): one workgroup owns a whole
+member -- it assembles ``K + diag(noise)`` in LDS, factors it there, solves and reduces -- where the single dense
+path pays a handle, uploads, a launch chain and a host join per evaluation.
+
+This module is the host side: lowering of the members (:func:`lower_member`), the packing of programs, coordinates,
+noise and residuals into the arrays of the C ABI (:func:`pack_members`), the choice between the batched launches and
+the single path (:func:`batched_route`), and :func:`log_probability_datasets`, the entry point for sets of data sets
+with points of their own.  ``DirectSolver.log_probability_batch`` is built on the same pieces.
+"""
+
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import numpy as np
+
+from tinygp_amd import _device, _ffi
+
+__all__ = ["MAX_N", "KOP_DTYPE", "Packed", "lower_member", "pack_members", "batched_route", "batch_route", "run_packed",
+           "log_probability_datasets"]
+
+MAX_N = _ffi.SMALL_MAX_N  # TGP_SMALL_MAX_N: the largest member a workgroup holds in LDS
+
+# ``tgp_kop`` as a NumPy record: the programs of a batch are one contiguous array of these
+KOP_DTYPE = np.dtype([("op", np.int32), ("metric", np.int32), ("p0", np.float64), ("p1", np.float64)], align=True)
+assert KOP_DTYPE.itemsize == 24
+
+_QUASISEP_MESSAGE = ("batches of kernels.quasisep models are evaluated by QuasisepSolver (log_probability_batch on sorted "
+                     "1-D inputs, log_probability_series for series with time stamps of their own), not by the dense path")
+
+
+class Packed(NamedTuple):
+    """The host arrays of one ``tgp_small_logprob`` call."""
+
+    progs: np.ndarray     # (total ops,) KOP_DTYPE
+    prog_off: np.ndarray  # (B + 1,) int32
+    x_off: np.ndarray     # (B,) int64, rows into X
+    n: np.ndarray         # (B,) int32
+    d: int
+    X: np.ndarray         # (rows, d) float64
+    vec_off: np.ndarray   # (B,) int64, into noise and resid
+    noise: np.ndarray     # (sum n,) float64
+    resid: np.ndarray     # (sum n,) float64
+
+
+def lower_member(kernel, X):
+    """``(program, points)`` of one member -- the postfix program and the float64 (n, D) coordinates the device reads,
+    input transforms folded in -- or ``None`` when the device cannot evaluate it (``kernels.Custom``, more than 16
+    dimensions, pytree inputs): such a member takes the single path."""
+    if _device.is_tree(X):
+        return None
+    try:
+        prog, Xdev = kernel._lower(X)
+        if _device.is_tree(Xdev):
+            return None
+        P = _device.points(Xdev, np.float64)
+    except NotImplementedError:
+        return None
+    if prog is None or len(prog) == 0:
+        return None
+    return prog, P
+
+
+def batched_route(n: int, lowered) -> bool:
+    """Whether a member of ``n`` points goes into the batched launches: it has a device program and fits a workgroup."""
+    return lowered is not None and 1 <= n <= MAX_N
+
+
+def batch_route(n: int, diagonal_noise: bool, lowered) -> bool:
+    """Whether a batch over ONE set of n points runs in the batched launches: a diagonal noise model, and every member
+    with a device program, n within the cap and one input dimension after the members' transforms.  Otherwise every
+    member is evaluated on the single path, so that the interface does not change with N."""
+    lowered = list(lowered)
+    if not diagonal_noise or not all(batched_route(n, low) for low in lowered):
+        return False
+    return len({low[1].shape[1] for low in lowered}) == 1
+
+
+def pack_members(members, labels=None) -> Packed:
+    """Stack B members ``(program, points (n_b, D), noise (n_b,), resid (n_b,))`` into the arrays of
+    ``tgp_small_logprob``.  Members whose points are ``np.array_equal`` to member 0's share its rows of ``X`` (one
+    uploaded copy: the shared-coordinates batch); every other member ships its own.  A ``ValueError`` names the member
+    whose input dimension, length or vectors do not fit (``labels[b]`` instead of ``"member b"`` when given)."""
+    members = list(members)
+    labels = [f"member {b}" for b in range(len(members))] if labels is None else list(labels)
+    if not members:
+        raise ValueError("a batch needs at least one member")
+    P0 = np.asarray(members[0][1])
+    d = int(P0.shape[1])
+    ops, prog_off, x_off, ns, vec_off, Xs, noises, resids = [], [0], [], [], [], [], [], []
+    rows = total = 0
+    for b, (prog, P, noise, resid) in enumerate(members):
+        P = np.asarray(P, dtype=np.float64)
+        if P.ndim != 2 or P.shape[1] != d:
+            raise ValueError(f"{labels[b]}: its points must have shape (n, {d}) like member 0's; got {P.shape}")
+        n = int(P.shape[0])
+        if not 1 <= n <= MAX_N:
+            raise ValueError(f"{labels[b]}: the batched dense path holds 1 .. {MAX_N} points per member (got {n})")
+        noise, resid = np.asarray(noise, dtype=np.float64), np.asarray(resid, dtype=np.float64)
+        if noise.shape != (n,) or resid.shape != (n,):
+            raise ValueError(f"{labels[b]}: noise and resid must have shape ({n},); got {noise.shape} and {resid.shape}")
+        if not 1 <= len(prog) <= 32:
+            raise ValueError(f"{labels[b]}: a kernel program holds 1 .. 32 operations (got {len(prog)})")
+        ops.extend((int(op), int(metric), float(p0), float(p1)) for op, metric, p0, p1 in prog)
+        prog_off.append(len(ops))
+        if b > 0 and P.shape == P0.shape and np.array_equal(P, P0):
+            x_off.append(0)
+        else:
+            x_off.append(rows)
+            Xs.append(P)
+            rows += n
+        ns.append(n)
+        vec_off.append(total)
+        noises.append(noise)
+        resids.append(resid)
+        total += n
+    return Packed(np.array(ops, dtype=KOP_DTYPE), np.array(prog_off, dtype=np.int32), np.array(x_off, dtype=np.int64),
+                  np.array(ns, dtype=np.int32), d, np.ascontiguousarray(np.concatenate(Xs, axis=0)),
+                  np.array(vec_off, dtype=np.int64), np.concatenate(noises), np.concatenate(resids))
+
+
+def run_packed(ctx, packed: Packed):
+    """One ``tgp_small_logprob`` call: ``(values (B,) float64 -- NaN where the factor failed --, info (B,) int32)``."""
+    nb = len(packed.n)
+    info, out = np.zeros(nb, dtype=np.int32), np.empty(nb)
+    _ffi.check(_ffi.lib().tgp_small_logprob(
+        ctx.handle, nb, _ffi.ptr(packed.progs), packed.prog_off.ctypes.data_as(_ffi._pi32),
+        packed.x_off.ctypes.data_as(_ffi._pi64), packed.n.ctypes.data_as(_ffi._pi32), packed.d, _ffi.ptr(packed.X),
+        packed.X.shape[0], packed.vec_off.ctypes.data_as(_ffi._pi64), _ffi.ptr(packed.noise), _ffi.ptr(packed.resid),
+        info.ctypes.data_as(_ffi._pi32), out.ctypes.data_as(_ffi._pdbl)), "tgp_small_logprob")
+    return out, info
+
+
+def reject_quasisep(kernels):
+    """The dense batch does not take ``kernels.quasisep`` models: their batches are ``QuasisepSolver``'s."""
+    from tinygp_amd.kernels.quasisep import Quasisep
+
+    if any(isinstance(k, Quasisep) for k in kernels):
+        raise NotImplementedError(_QUASISEP_MESSAGE)
+
+
+def check_datasets(kernels, Xs, ys, diags, means=None):
+    """The members of a set of data sets, validated: a list of ``(kernel, X, y (n,), diag (n,), mean (n,) or None)`` with
+    the vectors in the dtype of that data set's coordinates.  ``kernels`` is one kernel or one per data set; ``Xs[b]``
+    is (n_b,) or (n_b, D) with one D for the whole set (pytrees pass through to the single path); ``diags[b]`` a scalar
+    or (n_b,); ``means[b]`` ``None``, a scalar or (n_b,).  A ``ValueError`` names the data set that does not fit."""
+    from tinygp_amd.kernels.base import Kernel
+
+    Xs = list(Xs)
+    nb = len(Xs)
+    if nb == 0:
+        raise ValueError("a set of data sets needs at least one data set")
+    if isinstance(kernels, Kernel):
+        kernels = [kernels] * nb
+    else:
+        kernels = list(kernels)
+        if len(kernels) != nb:
+            raise ValueError(f"kernels must be one kernel or one per data set ({nb}); got {len(kernels)}")
+
+    def entries(values, what):
+        values = list(values)
+        if len(values) != nb:
+            raise ValueError(f"{what} must hold one entry per data set ({nb}); got {len(values)}")
+        return values
+
+    ys, diags = entries(ys, "ys"), entries(diags, "diags")
+    means = [None] * nb if means is None else entries(means, "means")
+    out, dim = [], None
+    for b, X in enumerate(Xs):
+        if _device.is_tree(X):
+            n, dt = _device.num_points(X), _device.common_dtype(*_device.tree_leaves(X))
+        else:
+            try:
+                P = _device.points(X, limit=False)
+            except ValueError as e:
+                raise ValueError(f"data set {b}: {e}") from e
+            n, dt = P.shape[0], P.dtype
+            if n == 0:
+                raise ValueError(f"data set {b} is empty: every data set needs at least one data point")
+            if dim is None:
+                dim = P.shape[1]
+            if P.shape[1] != dim:
+                raise ValueError(f"data set {b}: its points have {P.shape[1]} input dimensions, the set's have {dim}")
+
+        def vector(v, what, scalar_ok):
+            v = np.asarray(v)
+            if v.ndim == 2 and v.shape[1] == 1:
+                v = v[:, 0]
+            if not (v.shape == (n,) or (scalar_ok and v.shape == ())):
+                raise ValueError(f"{what}[{b}] must have shape ({n},)" + (" or be a scalar" if scalar_ok else "")
+                                 + f" for data set {b}; got {v.shape}")
+            return np.broadcast_to(v.astype(dt, copy=False), (n,))
+
+        y = vector(ys[b], "ys", False)
+        diag = vector(diags[b], "diags", True)
+        mean = None if means[b] is None else vector(means[b], "means", True)
+        out.append((kernels[b], X, y, diag, mean))
+    return out
+
+
+def log_probability_datasets(kernels, Xs, ys, *, diags, means=None, return_info: bool = False, ctx=None):
+    """The log-probabilities of B data sets under dense GPs, each with points, length and noise of its own, in one call
+    (the reference's ``jax.vmap`` over the function that builds the GP, without its equal-length restriction): hundreds
+    of short multi-band light curves, the inner loop of Bayesian optimisation.
+
+    ``kernels``: one kernel or one per data set; the members may differ in structure.  ``Xs[b]``: (n_b,) or (n_b, D)
+    with one D for the whole set.  ``ys[b]``: (n_b,).  ``diags[b]``: a scalar or (n_b,).  ``means[b]``: ``None``, a
+    scalar or (n_b,).  Returns B float64 values in the caller's order; a failed or non-finite member gives ``-inf``.
+    With ``return_info`` also the B ``info`` values (0, or the 1-based index of the first non-positive pivot).
+
+    Data sets of up to ``TGP_SMALL_MAX_N`` points that the device can lower run in the batched launches
+    (``tgp_small_logprob``: one workgroup per data set, fp64); each is held to the project's 1e-8 bar against
+    ``GaussianProcess(kernels[b], Xs[b], diag=diags[b], mean=means[b]).log_probability(ys[b])``, not to its bits.
+    Larger ones, and any the device cannot lower (``kernels.Custom``, more than 16 dimensions, pytree inputs), are that
+    very call, one by one.  ``kernels.quasisep`` models belong to :func:`tinygp_amd.log_probability_series`."""
+    members = check_datasets(kernels, Xs, ys, diags, means)
+    reject_quasisep(m[0] for m in members)
+    nb = len(members)
+    out, info = np.empty(nb), np.zeros(nb, dtype=np.int32)
+    batched, where = [], []
+    for b, (kernel, X, y, diag, mean) in enumerate(members):
+        lowered = lower_member(kernel, X)
+        # (an input transform may change the dimension: the launches hold the first batched member's)
+        if batched_route(len(y), lowered) and (not batched or lowered[1].shape[1] == batched[0][1].shape[1]):
+            batched.append((lowered[0], lowered[1], diag, y if mean is None else y - mean))
+            where.append(b)
+        else:
+            out[b], info[b] = _single(kernel, X, y, diag, mean, ctx)
+    if batched:
+        packed = pack_members(batched, labels=[f"data set {b}" for b in where])
+        values, infos = run_packed(_ffi.default_ctx() if ctx is None else ctx, packed)
+        out[where], info[where] = values, infos
+    out[(info != 0) | ~np.isfinite(out)] = -np.inf
+    return (out, info) if return_info else out
+
+
+def _single(kernel, X, y, diag, mean, ctx):
+    """One data set on the single dense path: ``GaussianProcess(kernel, X, diag=diag, mean=mean).log_probability(y)``
+    itself, its solver closed behind it."""
+    from tinygp_amd.gp import GaussianProcess
+    from tinygp_amd.solvers.direct import DirectSolver
+
+    kwargs = {} if ctx is None else {"ctx": ctx}
+    gp = GaussianProcess(kernel, X, diag=diag, solver=DirectSolver, **({} if mean is None else {"mean_value": mean}),
+                         **kwargs)
+    try:
+        return float(gp.log_probability(y)), int(gp.solver.info)
+    finally:
+        gp.solver.close()
