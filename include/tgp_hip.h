@@ -370,6 +370,24 @@ int tgp_solver_timings(tgp_solver* s, double* ms, int n);
 int tgp_small_logprob(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off, const int64_t* x_off,
                       const int32_t* n, int32_t d, const double* X_host, int64_t x_rows, const int64_t* vec_off,
                       const double* noise_host, const double* resid_host, int32_t* info_host, double* out_host);
+/* The same members with their gradients, still one workgroup and one launch per batch: what the reference's users get
+ * from jax.vmap(jax.value_and_grad(...)).  The arguments of tgp_small_logprob, validated and split into launches in
+ * the same way, and
+ *   want_dims          nb flags, or NULL: member b also gets d ll / d log s_q for every input dimension q of its
+ *                      coordinates (transforms.Linear / Cholesky with per-dimension scales), as tgp_solver_grad
+ *   out_host           the values, with the bits of tgp_small_logprob's
+ *   grad_params_host   2 x (total ops) doubles in the layout of tgp_solver_grad: member b's start at 2 prog_off[b],
+ *                      [2 i + q] = parameter q of op i, zero for ADD / MUL and a p1 the leaf does not have
+ *   grad_noise_host / alpha_host   1/2 (alpha_i^2 - K^-1_ii) and alpha = K^-1 r, member b's n[b] entries at vec_off[b];
+ *                      either may be NULL (no copy back)
+ *   grad_logscale_host nb x d doubles, member b's at b d (zero without its flag), or NULL
+ * A member whose factorisation fails has NaN in its value and in all of its gradients.  A member's bits depend on that
+ * member's data alone. */
+int tgp_small_logprob_grad(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off, const int64_t* x_off,
+                           const int32_t* n, int32_t d, const double* X_host, int64_t x_rows, const int64_t* vec_off,
+                           const double* noise_host, const double* resid_host, const int32_t* want_dims,
+                           int32_t* info_host, double* out_host, double* grad_params_host, double* grad_noise_host,
+                           double* alpha_host, double* grad_logscale_host);
 
 /* ---- block-cyclic column Cholesky over the GPUs of one node (BASELINE configs 4 / 5) ----------
  * The reference has NO multi-device code; these entry points are one RANK's share

@@ -99,6 +99,8 @@ SIGNATURES = {
     "tgp_solver_device_factor": [_vp, _pvp, _pi64],
     "tgp_solver_timings": [_vp, _pdbl, _int],
     "tgp_small_logprob": [_vp, _i32, _vp, _pi32, _pi64, _pi32, _i32, _vp, _i64, _pi64, _vp, _vp, _pi32, _pdbl],
+    "tgp_small_logprob_grad": [_vp, _i32, _vp, _pi32, _pi64, _pi32, _i32, _vp, _i64, _pi64, _vp, _vp, _pi32, _pi32, _pdbl,
+                               _pdbl, _pdbl, _pdbl, _pdbl],
     "tgp_trace_factor": [_i64, C.c_char_p, _i32, _pi64, _i64, _pi64],
     "tgp_chain_stamps": [_vp, _pi64, _i64, _pi64],
     "tgp_chain_task": [_i64, _i64, _i64, _i64, _i64, _pi32, _pi64],

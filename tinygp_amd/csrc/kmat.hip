@@ -18,126 +18,6 @@ namespace tgp {
 
 namespace {
 
-// d(leaf)/d(param) at the pair's distances: param 0 = p0 (scale or constant), 1 = p1
-// (gamma / alpha / sigma).  Derived from the forms of kernels/stationary.py:76-235 and (FAM = 2)
-// of DOT, u = s + p1^2 with s = r3 / p0^2:  du/dp0 = -2 s / p0,  du/dp1 = 2 p1.
-template <typename T, int FAM = 0>
-__device__ __forceinline__ T leaf_deriv(const KProg& kp, int i, int param, T r1, T r2, T r3 = T(0)) {
-  const int op = kp.op[i];
-  const bool l2 = kp.metric[i] == TGP_METRIC_L2;
-  // (the derivative passes are not the hot ones: both distances up front)
-  const T dist = l2 ? ((r2 == T(0)) ? r1 : sqrt(r2)) : r1;
-  const T sq = l2 ? r2 : r1 * r1;
-  const T p0 = T(kp.p0[i]);
-  const T p1 = T(kp.p1[i]);
-  switch (op) {
-    case TGP_K_CONST: return param == 0 ? T(1) : T(0);
-    case TGP_K_EXP: return param == 0 ? exp(-dist / p0) * dist / (p0 * p0) : T(0);
-    case TGP_K_EXPSQ: return param == 0 ? exp(T(-0.5) * (sq / (p0 * p0))) * sq / (p0 * p0 * p0) : T(0);
-    case TGP_K_M32: { const T a = MathC<T>::SQRT3 * (dist / p0);
-                      return param == 0 ? a * a * exp(-a) / p0 : T(0); }
-    case TGP_K_M52: { const T a = MathC<T>::SQRT5 * (dist / p0);
-                      return param == 0 ? (a * a / T(3)) * (T(1) + a) * exp(-a) / p0 : T(0); }
-    case TGP_K_COS: { const T u = MathC<T>::TWO_PI * (dist / p0);
-                      return param == 0 ? sin(u) * u / p0 : T(0); }
-    case TGP_K_ESS: { const T u = MathC<T>::PI * (dist / p0);
-                      const T sn = sin(u), v = exp(-p1 * (sn * sn));
-                      return param == 0 ? v * p1 * T(2) * sn * cos(u) * u / p0 : -(sn * sn) * v; }
-    case TGP_K_RQ: { const T q = T(0.5) * (sq / (p0 * p0)) / p1;  // r^2 / (2 alpha l^2)
-                     const T u = T(1) + q, v = pow(u, -p1);
-                     return param == 0 ? v / u * sq / (p0 * p0 * p0) : v * (q / u - log(u)); }
-    default: break;
-  }
-  if constexpr (FAM == 2) {
-    if (op == TGP_K_DOT) return param == 0 ? T(-2) * (r3 / (p0 * p0)) / p0 : T(2) * p1;
-  }
-  (void)r3;
-  return T(0);
-}
-
-// POW on the stack: (v, dv) -> (v^p, p v^(p-1) dv [+ v^p log v when p itself is differentiated]).
-// The log is taken of v with v == 0 replaced by 1 -- JAX's rule for x ** y (a zero base gives 0,
-// not NaN); a negative base gives NaN there, as in the reference.
-template <typename T>
-__device__ __forceinline__ void pow_deriv(T p, bool seed, T& v, T& dv) {
-  const T w = pow(v, p);
-  T d = p * pow(v, p - T(1)) * dv;
-  if (seed) d += w * log(v == T(0) ? T(1) : v);
-  v = w;
-  dv = d;
-}
-
-// Forward-mode derivative of the whole program with respect to ONE leaf parameter: the stack
-// carries (value, derivative) pairs; only op `which_op` (a leaf, or FAM = 2 a POW) seeds a
-// non-zero derivative.
-template <typename T, int FAM = 0>
-__device__ __forceinline__ T eval_kprog_deriv(const KProg& kp, int which_op, int which_param, T r1,
-                                              T r2, T r3 = T(0)) {
-  T s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0;
-  T d0 = 0, d1 = 0, d2 = 0, d3 = 0, d4 = 0, d5 = 0, d6 = 0, d7 = 0;
-  for (int i = 0; i < kp.n; ++i) {
-    const int op = kp.op[i];
-    if constexpr (FAM == 2) {
-      if (op == TGP_K_POW) {
-        pow_deriv<T>(T(kp.p0[i]), i == which_op, s0, d0);
-        continue;
-      }
-    }
-    if (op >= TGP_K_ADD) {
-      const T v = (op == TGP_K_ADD) ? (s1 + s0) : (s1 * s0);
-      const T dv = (op == TGP_K_ADD) ? (d1 + d0) : (d1 * s0 + s1 * d0);
-      s0 = v; s1 = s2; s2 = s3; s3 = s4; s4 = s5; s5 = s6; s6 = s7;
-      d0 = dv; d1 = d2; d2 = d3; d3 = d4; d4 = d5; d5 = d6; d6 = d7;
-      continue;
-    }
-    const T v = leaf_value<T, FAM == 2 ? 2 : 0>(kp, i, r1, r2, r3);
-    const T dv = (i == which_op) ? leaf_deriv<T, FAM>(kp, i, which_param, r1, r2, r3) : T(0);
-    s7 = s6; s6 = s5; s5 = s4; s4 = s3; s3 = s2; s2 = s1; s1 = s0; s0 = v;
-    d7 = d6; d6 = d5; d5 = d4; d4 = d3; d3 = d2; d2 = d1; d1 = d0; d0 = dv;
-  }
-  return d0;
-}
-
-// Forward-mode derivative of the whole program with respect to the LOG-SCALE of one input dimension d (x_d -> s x_d
-// for every point): what `transforms.Linear` / `Cholesky` with a per-dimension scale need (reference
-// transforms.py:39-133; JAX differentiates through them for free).  Every stationary leaf depends on the
-// coordinates through dist / p0 resp. sq / p0^2 only, so
-//   d leaf / d log s_d = -p0 * (d leaf / d p0) * w_d,   w_d = dx_d^2 / r2 (L2 metric) or |dx_d| / r1 (L1),
-// (the w_d sum to one: scaling every dimension is scaling 1 / p0).  w1 / w2 are this pair's weights.
-// FAM = 2: a DOT leaf contributes 2 (z_id / p0)(z_jd / p0), zz = z_id z_jd, and POW chains.
-template <typename T, int FAM = 0>
-__device__ __forceinline__ T eval_kprog_deriv_dim(const KProg& kp, T r1, T r2, T w1, T w2, T r3 = T(0),
-                                                  T zz = T(0)) {
-  T s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0;
-  T d0 = 0, d1 = 0, d2 = 0, d3 = 0, d4 = 0, d5 = 0, d6 = 0, d7 = 0;
-  for (int i = 0; i < kp.n; ++i) {
-    const int op = kp.op[i];
-    if constexpr (FAM == 2) {
-      if (op == TGP_K_POW) {
-        pow_deriv<T>(T(kp.p0[i]), false, s0, d0);
-        continue;
-      }
-    }
-    if (op >= TGP_K_ADD) {
-      const T v = (op == TGP_K_ADD) ? (s1 + s0) : (s1 * s0);
-      const T dv = (op == TGP_K_ADD) ? (d1 + d0) : (d1 * s0 + s1 * d0);
-      s0 = v; s1 = s2; s2 = s3; s3 = s4; s4 = s5; s5 = s6; s6 = s7;
-      d0 = dv; d1 = d2; d2 = d3; d3 = d4; d4 = d5; d5 = d6; d6 = d7;
-      continue;
-    }
-    const T v = leaf_value<T, FAM == 2 ? 2 : 0>(kp, i, r1, r2, r3);
-    const T w = kp.metric[i] == TGP_METRIC_L2 ? w2 : w1;
-    T dv = (op == TGP_K_CONST) ? T(0) : -T(kp.p0[i]) * leaf_deriv<T, FAM>(kp, i, 0, r1, r2, r3) * w;
-    if constexpr (FAM == 2) {
-      if (op == TGP_K_DOT) { const T p0 = T(kp.p0[i]); dv = T(2) * (zz / (p0 * p0)); }
-    }
-    (void)zz;
-    s7 = s6; s6 = s5; s5 = s4; s4 = s3; s3 = s2; s2 = s1; s1 = s0; s0 = v;
-    d7 = d6; d6 = d5; d5 = d4; d4 = d3; d3 = d2; d2 = d1; d1 = d0; d0 = dv;
-  }
-  return d0;
-}
-
 constexpr int KT = 128;  // tile edge
 
 // Zero-padded load of two 128-point tiles -- rows r0.. of X1 into s1, rows c0.. of X2 into s2, [KT][d] each -- by the

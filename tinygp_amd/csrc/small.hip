@@ -1,4 +1,4 @@
-// small.hip -- batches of SMALL dense problems, one workgroup each (tgp_small_logprob).
+// small.hip -- batches of SMALL dense problems, one workgroup each (tgp_small_logprob, tgp_small_logprob_grad).
 //
 // The dense path of chol.hip pads every matrix to 128-row tiles and pays a handle, uploads, a launch chain and a host
 // join per evaluation: at N <= 192 that is all overhead.  Here a workgroup of 256 threads owns a whole member: it
@@ -17,6 +17,12 @@
 // Every sum runs in an order fixed by the indices alone: entry (i, j) receives its updates p = 0, 1, .. j - 1 one
 // after another from ONE thread per step (explicit FMAs; the file is built with -ffp-contract=off like kmat.hip, so
 // that the kernel's entries are kmat.hip's to the bit), the two reductions are a fixed LDS tree.
+//
+// The gradient (small_grad_kernel) goes on in the same workgroup and the same LDS: alpha = K^-1 r by the backward
+// substitution in row n, K^-1 in place in the packed triangle (L -> L^-1 -> L^-T L^-1, both as rank-1 updates in the
+// access pattern of the factorisation), then one pass over the entries i >= j per derivative with the evaluators of
+// kprog_eval.h.  The assembly, the factorisation and the two value reductions are ONE text for both kernels: the
+// gradient kernel's value has the bits of small_logprob_kernel's.
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -36,11 +42,13 @@ constexpr int SMALL_WAVES = SMALL_THREADS / 64;
 constexpr int64_t SMALL_STAGE_BYTES = int64_t(1) << 30;  // staging per launch, the cap of the quasisep batches (qsep.hip)
 
 // one member of a launch; offsets in elements from the launch's X (rows of d doubles), noise and residual arrays
+// (the gradient's outputs: noise gradient and alpha at noise_off like the inputs, the parameter gradients at gp_off,
+// the per-dimension scale gradients at member * d; want_dims: this member asks for the latter)
 struct SmallRow {
-  int64_t x_off, noise_off, resid_off;
-  int32_t n, d, prog, pad;
+  int64_t x_off, noise_off, resid_off, gp_off;
+  int32_t n, d, prog, want_dims;
 };
-static_assert(sizeof(SmallRow) == 40 && sizeof(KProg) % 8 == 0, "the staging buffer is carved in 8-byte units");
+static_assert(sizeof(SmallRow) == 48 && sizeof(KProg) % 8 == 0, "the staging buffer is carved in 8-byte units");
 
 __host__ __device__ constexpr int64_t small_lds_doubles(int64_t n) { return n * (n + 1) / 2 + n; }
 static_assert(small_lds_doubles(TGP_SMALL_MAX_N) * 8 + 2 * SMALL_THREADS * 8 <= 163840,
@@ -48,21 +56,10 @@ static_assert(small_lds_doubles(TGP_SMALL_MAX_N) * 8 + 2 * SMALL_THREADS * 8 <= 
 
 __device__ __forceinline__ int col_off(int j, int n) { return j * (n + 1) - j * (j - 1) / 2; }
 
-__global__ __launch_bounds__(SMALL_THREADS) void small_logprob_kernel(const SmallRow* __restrict__ rows,
-                                                                        const KProg* __restrict__ progs,
-                                                                        const double* __restrict__ X,
-                                                                        const double* __restrict__ noise,
-                                                                        const double* __restrict__ resid,
-                                                                        double* __restrict__ out,
-                                                                        int32_t* __restrict__ info) {
-  extern __shared__ __attribute__((aligned(16))) double A[];  // the packed trapezoid
-  __shared__ double red[2][SMALL_THREADS];
-  const SmallRow row = rows[blockIdx.x];
-  const KProg& kp = progs[row.prog];
-  const int n = row.n, d = row.d;
-  const double* x = X + row.x_off * d;
-  const double* nz = noise + row.noise_off;
-  const double* rs = resid + row.resid_off;
+// Steps 1 - 4 of a member: assemble the trapezoid [K + diag(noise); r^T] in A, factor it there.  Returns 0, or the
+// 1-based index of the first pivot that is not > 0 -- the same number in every thread of the workgroup.
+__device__ __forceinline__ int small_assemble_factor(double* A, const KProg& kp, const double* x, const double* nz,
+                                                     const double* rs, int n, int d) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 
   // 1 + 2: wave w assembles columns w, w + 4, ..; lane l their rows j + l, j + l + 64, ..; row n is the residual
@@ -104,7 +101,12 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_logprob_kernel(const Smal
     }
     __syncthreads();
   }
+  return fail;
+}
 
+// Steps 5 + 6: the value from the factored trapezoid (the pivots on the diagonal, z in row n), written by thread 0.
+__device__ __forceinline__ void small_write_value(const double* A, double (&red)[2][SMALL_THREADS], int n, int fail,
+                                                  double* __restrict__ out, int32_t* __restrict__ info) {
   // 5: sum log L_pp and sum z_p^2 (one term per thread: n < 256), a fixed tree
   double sl = 0.0, sz = 0.0;
   if (fail == 0 && int(threadIdx.x) < n) {
@@ -130,32 +132,236 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_logprob_kernel(const Smal
     info[blockIdx.x] = fail;
   }
 }
+
+__global__ __launch_bounds__(SMALL_THREADS) void small_logprob_kernel(const SmallRow* __restrict__ rows,
+                                                                        const KProg* __restrict__ progs,
+                                                                        const double* __restrict__ X,
+                                                                        const double* __restrict__ noise,
+                                                                        const double* __restrict__ resid,
+                                                                        double* __restrict__ out,
+                                                                        int32_t* __restrict__ info) {
+  extern __shared__ __attribute__((aligned(16))) double A[];  // the packed trapezoid
+  __shared__ double red[2][SMALL_THREADS];
+  const SmallRow row = rows[blockIdx.x];
+  const KProg& kp = progs[row.prog];
+  const int n = row.n, d = row.d;
+  const int fail = small_assemble_factor(A, kp, X + row.x_off * d, noise + row.noise_off, resid + row.resid_off, n, d);
+  small_write_value(A, red, n, fail, out, info);
+}
+
+// Value AND gradient of one member.  After the value (the text above):
+//   7  the diagonal words become L_pp (they held the pivots L_pp^2), once;
+//   8  alpha = K^-1 r: the backward substitution L^T alpha = z in place in row n.  Thread k carries z_k in a register
+//      and takes L_pk alpha_p from it for p = n - 1 .. k + 1, one barrier per step;
+//   9  W = L^-1 in place, column by column: column j below the diagonal becomes -L_ij / L_jj, then the block left of
+//      it takes the rank-1 update B_ic += B_ij B_jc (i > j > c) -- the elimination of L W = I carried on all right-hand
+//      sides at once, B_jc = L_jj W_jc; a last pass divides row j by L_jj and sets W_jj = 1 / L_jj;
+//  10  K^-1 = W^T W in place: entry (i, k), k <= i, is sum_{m >= i} W_mi W_mk, and row m of W is last needed at step
+//      m, so step m copies row m aside (the reduction scratch holds two rows: the copy of row m + 1 runs under step
+//      m's update) and adds its outer product to the rows above it, entry (m, k) itself STARTING from W_mm W_mk;
+//  11  per derivative one pass over the entries i >= j: g_ij = alpha_i alpha_j - K^-1_ij, weight 1/2 on the diagonal,
+//      the pair's distances recomputed from the points, one fp64 accumulator per thread, the fixed tree, thread 0
+//      writes; the noise gradient 1/2 (alpha_i^2 - K^-1_ii) and the mean gradient alpha, one entry per thread.
+// Every entry receives its updates one after another from ONE thread per step, in the order of the step index; the
+// loops' trip counts and every branch around a barrier depend on n, the program and `fail` alone.
+__global__ __launch_bounds__(SMALL_THREADS) void small_grad_kernel(const SmallRow* __restrict__ rows,
+                                                                     const KProg* __restrict__ progs,
+                                                                     const double* __restrict__ X,
+                                                                     const double* __restrict__ noise,
+                                                                     const double* __restrict__ resid,
+                                                                     double* __restrict__ out,
+                                                                     int32_t* __restrict__ info,
+                                                                     double* __restrict__ grad_params,
+                                                                     double* __restrict__ grad_noise,
+                                                                     double* __restrict__ alpha_out,
+                                                                     double* __restrict__ grad_dims) {
+  extern __shared__ __attribute__((aligned(16))) double A[];  // the packed trapezoid
+  __shared__ double red[2][SMALL_THREADS];
+  const SmallRow row = rows[blockIdx.x];
+  const KProg& kp = progs[row.prog];
+  const int n = row.n, d = row.d;
+  const double* x = X + row.x_off * d;
+  const int tid = threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double* gp = grad_params + row.gp_off;
+  double* gn = grad_noise + row.noise_off;
+  double* ga = alpha_out + row.noise_off;
+  double* gd = grad_dims + int64_t(blockIdx.x) * d;
+
+  const int fail = small_assemble_factor(A, kp, x, noise + row.noise_off, resid + row.resid_off, n, d);
+  small_write_value(A, red, n, fail, out, info);
+  if (fail) {  // the workgroup's decision: NaN in every gradient of this member
+    const double nan = __builtin_nan("");
+    for (int t = tid; t < 2 * kp.n; t += SMALL_THREADS) gp[t] = nan;
+    for (int t = tid; t < n; t += SMALL_THREADS) gn[t] = ga[t] = nan;
+    for (int t = tid; t < d; t += SMALL_THREADS) gd[t] = nan;
+    return;
+  }
+  __syncthreads();  // thread 0 has read the scratch
+
+  // 7
+  if (tid < n) A[col_off(tid, n)] = sqrt(A[col_off(tid, n)]);
+  __syncthreads();
+
+  // 8: alpha_p lands where z_p was
+  {
+    double zk = tid < n ? A[col_off(tid, n) + n - tid] : 0.0;
+    for (int p = n - 1; p >= 0; --p) {
+      const double* cp = A + col_off(p, n);
+      if (tid == p) A[col_off(p, n) + n - p] = zk / cp[0];
+      __syncthreads();
+      if (tid < p) zk = __builtin_fma(-A[col_off(tid, n) + p - tid], cp[n - p], zk);
+    }
+  }
+
+  // 9 (rows j + 1 .. n - 1 only: row n is alpha's)
+  for (int j = 0; j < n; ++j) {
+    double* cj = A + col_off(j, n);
+    const double ljj = cj[0];
+    for (int i = j + 1 + tid; i < n; i += SMALL_THREADS) cj[i - j] = -(cj[i - j] / ljj);
+    __syncthreads();
+    for (int c = wave; c < j; c += SMALL_WAVES) {
+      double* col = A + col_off(c, n);
+      const double bjc = col[j - c];
+      for (int i = j + 1 + lane; i < n; i += 64) col[i - c] = __builtin_fma(cj[i - j], bjc, col[i - c]);
+    }
+    __syncthreads();
+  }
+  for (int c = wave; c < n; c += SMALL_WAVES) {
+    double* col = A + col_off(c, n);
+    for (int i = c + 1 + lane; i < n; i += 64) col[i - c] = col[i - c] / A[col_off(i, n)];
+  }
+  __syncthreads();
+  double* rowbuf = &red[0][0];  // two rows of up to SMALL_THREADS entries
+  if (tid < n) {
+    const double wjj = 1.0 / A[col_off(tid, n)];
+    A[col_off(tid, n)] = wjj;
+    if (tid == 0) rowbuf[0] = wjj;  // row 0 of W, for step 10
+  }
+  __syncthreads();
+
+  // 10
+  for (int m = 0; m < n; ++m) {
+    const double* tm = rowbuf + (m & 1) * SMALL_THREADS;
+    for (int k = wave; k <= m; k += SMALL_WAVES) {
+      double* col = A + col_off(k, n);
+      const double tk = tm[k];
+      for (int i = k + lane; i <= m; i += 64) col[i - k] = (i == m) ? tm[i] * tk : __builtin_fma(tm[i], tk, col[i - k]);
+    }
+    if (m + 1 < n) {
+      double* tn = rowbuf + ((m + 1) & 1) * SMALL_THREADS;
+      for (int c = tid; c <= m + 1; c += SMALL_THREADS) tn[c] = A[col_off(c, n) + m + 1 - c];
+    }
+    __syncthreads();
+  }
+
+  // 11: the noise and mean gradients, then one pass per derivative: parameter q of op i is task 2 i + q (zero for
+  // ADD / MUL and a p1 the leaf does not have, as in tgp_solver_grad), input dimension t is task 2 kp.n + t
+  if (tid < n) {
+    const double a = A[col_off(tid, n) + n - tid];
+    gn[tid] = 0.5 * (a * a - A[col_off(tid, n)]);
+    ga[tid] = a;
+  }
+  const int ntask = 2 * kp.n + d;
+  for (int task = 0; task < ntask; ++task) {
+    int which_op, which_param = 0;
+    double* dst;
+    if (task < 2 * kp.n) {
+      which_op = task >> 1, which_param = task & 1;
+      dst = gp + task;
+      const int op = kp.op[which_op];
+      const bool two = op == TGP_K_ESS || op == TGP_K_RQ || op == TGP_K_DOT;
+      if (op == TGP_K_ADD || op == TGP_K_MUL || (which_param == 1 && !two)) {
+        if (tid == 0) *dst = 0.0;
+        continue;
+      }
+    } else {
+      which_op = -1 - (task - 2 * kp.n);
+      dst = gd + (task - 2 * kp.n);
+      if (!row.want_dims) {
+        if (tid == 0) *dst = 0.0;
+        continue;
+      }
+    }
+    double acc = 0.0;
+    for (int j = wave; j < n; j += SMALL_WAVES) {
+      const double* col = A + col_off(j, n);
+      const double aj = col[n - j];
+      for (int i = j + lane; i < n; i += 64) {
+        const double gij = A[col_off(i, n) + n - i] * aj - col[i - j];
+        double r1, r2, r3, dxd = 0.0, zz = 0.0;
+        pair_dist<double, 2, 0>(x + int64_t(i) * d, x + int64_t(j) * d, d, r1, r2, r3,
+                                [&](int t, double dx, double a, double b) {
+                                  if (t == -1 - which_op) dxd = dx, zz = a * b;
+                                });
+        const double dk = which_op >= 0
+                              ? eval_kprog_deriv<double, 2>(kp, which_op, which_param, r1, r2, r3)
+                              : eval_kprog_deriv_dim<double, 2>(kp, r1, r2, r1 > 0.0 ? fabs(dxd) / r1 : 0.0,
+                                                                r2 > 0.0 ? dxd * dxd / r2 : 0.0, r3, zz);
+        acc += gij * dk * (i == j ? 0.5 : 1.0);
+      }
+    }
+    red[0][tid] = acc;
+    __syncthreads();
+    for (int sft = SMALL_THREADS / 2; sft > 0; sft >>= 1) {
+      if (tid < sft) red[0][tid] += red[0][tid + sft];
+      __syncthreads();
+    }
+    if (tid == 0) *dst = red[0][0];
+    __syncthreads();  // the next pass writes the scratch again
+  }
+}
 static_assert(TGP_SMALL_MAX_N < SMALL_THREADS, "one reduction term per thread");
+
+// the gradient's host outputs (tgp_small_logprob_grad); `on` is false for the value alone
+struct SmallGradOut {
+  bool on = false;
+  const int32_t* want_dims = nullptr;
+  double* params = nullptr;
+  double* noise = nullptr;
+  double* alpha = nullptr;
+  double* logscale = nullptr;
+};
 
 // what members [b0, b1) need in the staging buffer, and where
 struct SmallLaunch {
   int64_t b0 = 0, b1 = 0, max_n = 0;
-  int64_t x_doubles = 0, vec_doubles = 0;
+  int64_t x_doubles = 0, vec_doubles = 0, ops = 0;
   std::vector<char> host;  // rows | programs | X | noise | residual, as on the device
+  std::vector<double> back;  // the gradient's noise gradient | alpha as on the device, scattered after the join
 };
 
-int64_t launch_bytes(int64_t nb, int64_t x_doubles, int64_t vec_doubles) {
-  return nb * int64_t(sizeof(SmallRow) + sizeof(KProg)) + (x_doubles + 2 * vec_doubles) * 8 + nb * 8 + round_up(nb * 4, 8);
+// inputs | values | info, and for the gradient | parameter gradients | noise gradient | alpha | scale gradients
+int64_t launch_bytes(int64_t nb, int64_t x_doubles, int64_t vec_doubles, int64_t grad_doubles) {
+  return nb * int64_t(sizeof(SmallRow) + sizeof(KProg)) + (x_doubles + 2 * vec_doubles) * 8 + nb * 8 +
+         round_up(nb * 4, 8) + grad_doubles * 8;
+}
+
+int64_t grad_doubles(bool grad, int64_t nb, int64_t ops, int64_t vec_doubles, int64_t d) {
+  return grad ? 2 * ops + 2 * vec_doubles + nb * d : 0;
 }
 
 // enqueues every launch; the host buffers in `launches` must outlive the join
-int small_enqueue(tgp_ctx* ctx, const std::vector<SmallLaunch>& launches, int32_t* info_host, double* out_host) {
+int small_enqueue(tgp_ctx* ctx, std::vector<SmallLaunch>& launches, int32_t d, const int32_t* prog_off,
+                  int32_t* info_host, double* out_host, const SmallGradOut& g) {
   hipStream_t st = ctx->stream;
-  if (!ctx->small_lds_raised) {
+  if (!g.on && !ctx->small_lds_raised) {
     TGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(small_logprob_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize,
                                     int(small_lds_doubles(TGP_SMALL_MAX_N) * 8)));
     ctx->small_lds_raised = true;
   }
+  if (g.on && !ctx->small_grad_lds_raised) {
+    TGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(small_grad_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    int(small_lds_doubles(TGP_SMALL_MAX_N) * 8)));
+    ctx->small_grad_lds_raised = true;
+  }
   int64_t need = 0;
-  for (const SmallLaunch& l : launches) need = std::max(need, launch_bytes(l.b1 - l.b0, l.x_doubles, l.vec_doubles));
+  for (const SmallLaunch& l : launches)
+    need = std::max(need, launch_bytes(l.b1 - l.b0, l.x_doubles, l.vec_doubles,
+                                       grad_doubles(g.on, l.b1 - l.b0, l.ops, l.vec_doubles, d)));
   TGP_TRY(ensure_work(ctx, size_t(need)));
-  for (const SmallLaunch& l : launches) {
+  for (SmallLaunch& l : launches) {
     const int64_t nb = l.b1 - l.b0;
     char* base = static_cast<char*>(ctx->d_work);
     const SmallRow* rows = reinterpret_cast<const SmallRow*>(base);
@@ -166,31 +372,46 @@ int small_enqueue(tgp_ctx* ctx, const std::vector<SmallLaunch>& launches, int32_
     double* out = const_cast<double*>(resid) + l.vec_doubles;
     int32_t* info = reinterpret_cast<int32_t*>(out + nb);
     TGP_HIP_TRY(hipMemcpyAsync(base, l.host.data(), l.host.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(small_logprob_kernel, dim3(unsigned(nb)), dim3(SMALL_THREADS),
-                       size_t(small_lds_doubles(l.max_n) * 8), st, rows, progs, X, noise, resid, out, info);
-    TGP_HIP_TRY(hipGetLastError());
+    if (!g.on) {
+      hipLaunchKernelGGL(small_logprob_kernel, dim3(unsigned(nb)), dim3(SMALL_THREADS),
+                         size_t(small_lds_doubles(l.max_n) * 8), st, rows, progs, X, noise, resid, out, info);
+      TGP_HIP_TRY(hipGetLastError());
+    } else {
+      double* gparams = out + nb + round_up(nb * 4, 8) / 8;
+      double* gnoise = gparams + 2 * l.ops;
+      double* galpha = gnoise + l.vec_doubles;
+      double* gdims = galpha + l.vec_doubles;
+      hipLaunchKernelGGL(small_grad_kernel, dim3(unsigned(nb)), dim3(SMALL_THREADS),
+                         size_t(small_lds_doubles(l.max_n) * 8), st, rows, progs, X, noise, resid, out, info, gparams,
+                         gnoise, galpha, gdims);
+      TGP_HIP_TRY(hipGetLastError());
+      TGP_HIP_TRY(hipMemcpyAsync(g.params + 2 * int64_t(prog_off[l.b0]), gparams, size_t(2 * l.ops) * 8,
+                                 hipMemcpyDeviceToHost, st));
+      if (g.noise || g.alpha) {
+        l.back.resize(size_t(2 * l.vec_doubles));
+        TGP_HIP_TRY(hipMemcpyAsync(l.back.data(), gnoise, l.back.size() * 8, hipMemcpyDeviceToHost, st));
+      }
+      if (g.logscale)
+        TGP_HIP_TRY(hipMemcpyAsync(g.logscale + l.b0 * d, gdims, size_t(nb * d) * 8, hipMemcpyDeviceToHost, st));
+    }
     TGP_HIP_TRY(hipMemcpyAsync(out_host + l.b0, out, size_t(nb) * 8, hipMemcpyDeviceToHost, st));
     TGP_HIP_TRY(hipMemcpyAsync(info_host + l.b0, info, size_t(nb) * 4, hipMemcpyDeviceToHost, st));
   }
   return TGP_OK;
 }
 
-}  // namespace
-
-}  // namespace tgp
-
-using namespace tgp;
-
-extern "C" int tgp_small_logprob(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off,
-                                 const int64_t* x_off, const int32_t* n, int32_t d, const double* X_host,
-                                 int64_t x_rows, const int64_t* vec_off, const double* noise_host,
-                                 const double* resid_host, int32_t* info_host, double* out_host) {
+// the body of both entry points: validation, the split into launches, one host join
+int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off, const int64_t* x_off,
+               const int32_t* n, int32_t d, const double* X_host, int64_t x_rows, const int64_t* vec_off,
+               const double* noise_host, const double* resid_host, int32_t* info_host, double* out_host,
+               const SmallGradOut& g) {
   TGP_ARG_CHECK(ctx != nullptr, "null context");
   TGP_ARG_CHECK(nb >= 0, "negative number of members (%d)", nb);
   if (nb == 0) return TGP_OK;
   std::unique_lock<std::recursive_mutex> lock(ctx->mu);
   TGP_HIP_TRY(hipSetDevice(ctx->device));
-  TGP_ARG_CHECK(progs && prog_off && x_off && n && X_host && vec_off && noise_host && resid_host && info_host && out_host,
+  TGP_ARG_CHECK(progs && prog_off && x_off && n && X_host && vec_off && noise_host && resid_host && info_host && out_host &&
+                    (!g.on || g.params),
                 "null argument");
   TGP_ARG_CHECK(d >= 1 && d <= TGP_MAX_DIM, "the input dimension must be 1 .. %d (got %d)", TGP_MAX_DIM, d);
   TGP_ARG_CHECK(x_rows >= 0, "negative number of coordinate rows (%lld)", (long long)x_rows);
@@ -223,10 +444,12 @@ extern "C" int tgp_small_logprob(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs,
       const auto key = std::make_pair(x_off[b], n[b]);
       const bool fresh = seen.find(key) == seen.end();
       const int64_t xd = l.x_doubles + (fresh ? int64_t(n[b]) * d : 0), vd = l.vec_doubles + n[b];
-      if (b > b0 && launch_bytes(b - b0 + 1, xd, vd) > SMALL_STAGE_BYTES) break;
+      const int64_t ops = int64_t(prog_off[b + 1]) - prog_off[b0];
+      if (b > b0 && launch_bytes(b - b0 + 1, xd, vd, grad_doubles(g.on, b - b0 + 1, ops, vd, d)) > SMALL_STAGE_BYTES) break;
       if (fresh) seen[key] = l.x_doubles / d;
-      rows.push_back(SmallRow{seen[key], l.vec_doubles, l.vec_doubles, n[b], d, int32_t(b - b0), 0});
-      l.x_doubles = xd, l.vec_doubles = vd;
+      rows.push_back(SmallRow{seen[key], l.vec_doubles, l.vec_doubles, 2 * (int64_t(prog_off[b]) - prog_off[b0]), n[b], d,
+                              int32_t(b - b0), int32_t(g.want_dims && g.want_dims[b] ? 1 : 0)});
+      l.x_doubles = xd, l.vec_doubles = vd, l.ops = ops;
       l.max_n = std::max<int64_t>(l.max_n, n[b]);
     }
     l.b1 = b;
@@ -251,9 +474,49 @@ extern "C" int tgp_small_logprob(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs,
     b0 = b;
   }
   // one host join, on every path: the host buffers above are read by the copies that were enqueued
-  const int status = small_enqueue(ctx, launches, info_host, out_host);
+  const int status = small_enqueue(ctx, launches, d, prog_off, info_host, out_host, g);
   const hipError_t joined = hipStreamSynchronize(ctx->stream);
   TGP_TRY(status);
   TGP_HIP_TRY(joined);
+  // the two vectors go back to the caller's offsets (the launch holds them member after member)
+  for (const SmallLaunch& l : launches) {
+    if (l.back.empty()) continue;
+    int64_t at = 0;
+    for (int64_t b = l.b0; b < l.b1; at += n[b], ++b) {
+      if (g.noise) std::memcpy(g.noise + vec_off[b], l.back.data() + at, size_t(n[b]) * 8);
+      if (g.alpha) std::memcpy(g.alpha + vec_off[b], l.back.data() + l.vec_doubles + at, size_t(n[b]) * 8);
+    }
+  }
   return TGP_OK;
+}
+
+}  // namespace
+
+}  // namespace tgp
+
+using namespace tgp;
+
+extern "C" int tgp_small_logprob(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off,
+                                 const int64_t* x_off, const int32_t* n, int32_t d, const double* X_host,
+                                 int64_t x_rows, const int64_t* vec_off, const double* noise_host,
+                                 const double* resid_host, int32_t* info_host, double* out_host) {
+  return small_call(ctx, nb, progs, prog_off, x_off, n, d, X_host, x_rows, vec_off, noise_host, resid_host, info_host,
+                    out_host, SmallGradOut{});
+}
+
+extern "C" int tgp_small_logprob_grad(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off,
+                                      const int64_t* x_off, const int32_t* n, int32_t d, const double* X_host,
+                                      int64_t x_rows, const int64_t* vec_off, const double* noise_host,
+                                      const double* resid_host, const int32_t* want_dims, int32_t* info_host,
+                                      double* out_host, double* grad_params_host, double* grad_noise_host,
+                                      double* alpha_host, double* grad_logscale_host) {
+  SmallGradOut g;
+  g.on = true;
+  g.want_dims = want_dims;
+  g.params = grad_params_host;
+  g.noise = grad_noise_host;
+  g.alpha = alpha_host;
+  g.logscale = grad_logscale_host;
+  return small_call(ctx, nb, progs, prog_off, x_off, n, d, X_host, x_rows, vec_off, noise_host, resid_host, info_host,
+                    out_host, g);
 }

@@ -202,12 +202,17 @@ class GaussianProcess:
         together: ``(values (B,), grads)`` with ``grads = {"kernel": (B, P), "noise_diag": (B, N), "mean": (B, N),
         "transform": None}``.  Arguments as in :meth:`log_probability_batch`; row b equals
         ``GaussianProcess(kernels[b], X, diag=diags[b], mean=means[b]).log_probability_and_grad(y)`` to the bit.
-        Needs a solver with ``value_and_grad_batch`` (:class:`tinygp_amd.solvers.QuasisepSolver`)."""
+        Needs a solver with ``value_and_grad_batch`` (:class:`tinygp_amd.solvers.QuasisepSolver`).  The dense path's
+        batches of gradients have another return shape (its members may differ in structure) and entry points of their
+        own: ``DirectSolver.log_probability_and_grad_batch`` over this GP's coordinates, and
+        :func:`tinygp_amd.log_probability_and_grad_datasets` for data sets with points of their own."""
         fused = getattr(self.solver, "value_and_grad_batch", None)
         if fused is None:
             raise NotImplementedError(f"{type(self.solver).__name__} has no value_and_grad_batch: batches of gradients "
-                                      "are evaluated by QuasisepSolver (a kernels.quasisep kernel on sorted 1-D "
-                                      "inputs)")
+                                      "through this method are evaluated by QuasisepSolver (a kernels.quasisep kernel "
+                                      "on sorted 1-D inputs); on the dense path use "
+                                      "DirectSolver.log_probability_and_grad_batch or "
+                                      "tinygp_amd.log_probability_and_grad_datasets")
         kernels = list(kernels)
         return fused(kernels, *self._batch_inputs(y, len(kernels), diags, means))
 

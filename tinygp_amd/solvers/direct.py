@@ -389,6 +389,72 @@ class DirectSolver(Solver):
         out = out.astype(self.dtype, copy=False)
         return (out, info) if return_info else out
 
+    def log_probability_and_grad_batch(self, kernels, resid, noise=None, *, vectors: bool = True,
+                                       return_info: bool = False):
+        """:meth:`log_probability_and_grad` of B models over this solver's coordinates, evaluated together on the device
+        (``tgp_small_logprob_grad``, ``csrc/small.hip``: the workgroup that assembles, factors and solves a member in
+        LDS also inverts there in place and weighs every derivative).  Arguments as in :meth:`log_probability_batch`.
+
+        Returns ``(values (B,), grads)`` with the keys of the single call: ``"kernel"``, a list of B float64 arrays,
+        member b's in the order of ``kernels[b].parameters()`` (the members may differ in structure, so this is never a
+        rectangular array); ``"noise_diag"`` and ``"mean"``, (B, N), or ``None`` with ``vectors=False`` (they are then
+        not copied back); ``"transform"``, a list of B entries, each ``None`` or what
+        ``covering_transform(kernels[b])._logscale_gradient`` gives, as in the single call.  With ``return_info`` the B
+        ``info`` values come third.  A failed or non-finite member gives ``-inf`` and NaN gradients.  fp32 inputs are
+        computed in fp64; values and vectors come back as fp32, the ``"kernel"`` rows stay float64.
+
+        The values have the bits of :meth:`log_probability_batch`; every gradient is held to the project's bars
+        against :meth:`log_probability_and_grad` of a solver built with that member's kernel and noise.  The routing is
+        that of :meth:`log_probability_batch`: above ``TGP_SMALL_MAX_N`` points, with a noise model that is not
+        :class:`~tinygp_amd.noise.Diagonal` or with a member without a device program, every member is that single
+        call on a fresh :class:`DirectSolver`, repacked into the same shape (with that call's own answers: it raises
+        ``NotImplementedError`` for a kernel without a device program, such as ``kernels.Custom``).  ``kernels.quasisep``
+        members raise
+        ``NotImplementedError``: their batches are ``QuasisepSolver``'s."""
+        from tinygp_amd.solvers import small
+
+        kernels = list(kernels)
+        nb = len(kernels)
+        if nb == 0:
+            empty = np.empty((0, self.n), dtype=self.dtype)
+            grads = {"kernel": [], "noise_diag": empty if vectors else None, "mean": empty.copy() if vectors else None,
+                     "transform": []}
+            out = (np.empty(0, dtype=self.dtype), grads)
+            return out + (np.empty(0, dtype=np.int32),) if return_info else out
+        small.reject_quasisep(kernels)
+
+        def rows(a, what):  # (N,) shared or (B, N) one per member -> (B, N)
+            a = np.asarray(a)
+            if a.shape not in ((self.n,), (nb, self.n)):
+                raise ValueError(f"{what} must have shape ({self.n},) or ({nb}, {self.n}); got {a.shape}")
+            return np.broadcast_to(a, (nb, self.n))
+
+        r = rows(resid, "resid")
+        d = None if noise is None else rows(noise, "noise")
+        lowered = [small.lower_member(k, self.X) for k in kernels]
+        values, info = np.empty(nb), np.zeros(nb, dtype=np.int32)
+        kgrads, tgrads, noise_rows, mean_rows = [None] * nb, [None] * nb, [None] * nb, [None] * nb
+        if small.batch_route(self.n, d is not None or isinstance(self.noise, Diagonal), lowered):
+            members = [(low[0], low[1], self._noise_diag if d is None else d[b], r[b]) for b, low in enumerate(lowered)]
+            packed = small.pack_members(members)
+            results = small.run_packed_grad(self._ctx, packed, small.dims_flags(kernels), vectors=vectors)
+            small.unpack_gradients(kernels, packed, results, range(nb), values, info, kgrads, tgrads, noise_rows,
+                                   mean_rows, [self.dtype] * nb)
+        else:  # the single call, member by member: the interface does not change with N
+            for b, kernel in enumerate(kernels):
+                nz = self.noise if d is None else Diagonal(diag=np.asarray(d[b], dtype=self.dtype))
+                single = DirectSolver(kernel, self.X, nz, ctx=self._ctx)
+                try:
+                    (values[b], info[b], kgrads[b], tgrads[b], noise_rows[b],
+                     mean_rows[b]) = small.single_gradient(single, np.asarray(r[b], dtype=self.dtype), vectors)
+                finally:
+                    single.close()
+        values[(info != 0) | ~np.isfinite(values)] = -np.inf
+        grads = {"kernel": kgrads, "noise_diag": np.stack(noise_rows) if vectors else None,
+                 "mean": np.stack(mean_rows) if vectors else None, "transform": tgrads}
+        out = (values.astype(self.dtype, copy=False), grads)
+        return out + (info,) if return_info else out
+
     def log_probability_and_grad(self, resid):
         """``(log_probability, grads)`` with ``grads = {"kernel": [...], "noise_diag": (N,),
         "mean": (N,), "transform": ...}``: derivatives with respect to ``kernel.parameters()`` (same order), to

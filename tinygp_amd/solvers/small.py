@@ -1,11 +1,14 @@
-"""Batches of small dense GPs in one launch (``tgp_small_logprob``, ``csrc/small.hip``): one workgroup owns a whole
-member -- it assembles ``K + diag(noise)`` in LDS, factors it there, solves and reduces -- where the single dense
-path pays a handle, uploads, a launch chain and a host join per evaluation.
+"""Batches of small dense GPs in one launch (``tgp_small_logprob``, ``tgp_small_logprob_grad``, ``csrc/small.hip``): one
+workgroup owns a whole member -- it assembles ``K + diag(noise)`` in LDS, factors it there, solves and reduces, and for
+the gradient inverts in place and weighs every derivative -- where the single dense path pays a handle, uploads, a
+launch chain and a host join per evaluation.
 
 This module is the host side: lowering of the members (:func:`lower_member`), the packing of programs, coordinates,
 noise and residuals into the arrays of the C ABI (:func:`pack_members`), the choice between the batched launches and
 the single path (:func:`batched_route`), and :func:`log_probability_datasets`, the entry point for sets of data sets
-with points of their own.  ``DirectSolver.log_probability_batch`` is built on the same pieces.
+with points of their own.  ``DirectSolver.log_probability_batch`` is built on the same pieces.  The gradient's side:
+:func:`run_packed_grad`, the mapping of the device's ``[2 i + q]`` layout onto ``kernel.parameters()``
+(:func:`member_gradient`), :func:`log_probability_and_grad_datasets` and ``DirectSolver.log_probability_and_grad_batch``.
 """
 
 from __future__ import annotations
@@ -17,7 +20,8 @@ import numpy as np
 from tinygp_amd import _device, _ffi
 
 __all__ = ["MAX_N", "KOP_DTYPE", "Packed", "lower_member", "pack_members", "batched_route", "batch_route", "run_packed",
-           "log_probability_datasets"]
+           "run_packed_grad", "member_gradient", "failed_gradient", "log_probability_datasets",
+           "log_probability_and_grad_datasets"]
 
 MAX_N = _ffi.SMALL_MAX_N  # TGP_SMALL_MAX_N: the largest member a workgroup holds in LDS
 
@@ -131,6 +135,92 @@ def run_packed(ctx, packed: Packed):
     return out, info
 
 
+def run_packed_grad(ctx, packed: Packed, want_dims=None, *, vectors: bool = True):
+    """One ``tgp_small_logprob_grad`` call: ``(values (B,), info (B,), grad_params (2 x total ops,), grad_noise (sum n,),
+    alpha (sum n,), grad_logscale (B, d))``, all float64.  Member b's parameter gradients start at
+    ``2 * packed.prog_off[b]`` in the ``[2 i + q]`` layout of ``tgp_solver_grad``; its two vectors sit at
+    ``packed.vec_off[b]``.  ``want_dims``: (B,) flags, the members that also get ``d ll / d log s_q`` per input
+    dimension (zero for the others); ``None``: nobody, and no such output.  ``vectors=False``: the two vectors are
+    ``None`` and are not copied back.  A failed member has NaN everywhere."""
+    nb = len(packed.n)
+    info, out = np.zeros(nb, dtype=np.int32), np.empty(nb)
+    gparams = np.zeros(2 * len(packed.progs))
+    total = int(packed.n.sum())
+    gnoise, alpha = (np.empty(total), np.empty(total)) if vectors else (None, None)
+    flags = None if want_dims is None else np.ascontiguousarray(want_dims, dtype=np.int32)
+    if flags is not None and flags.shape != (nb,):
+        raise ValueError(f"want_dims must hold one flag per member ({nb}); got {flags.shape}")
+    glog = None if flags is None else np.zeros((nb, packed.d))
+
+    def pdbl(a):
+        return None if a is None else a.ctypes.data_as(_ffi._pdbl)
+
+    _ffi.check(_ffi.lib().tgp_small_logprob_grad(
+        ctx.handle, nb, _ffi.ptr(packed.progs), packed.prog_off.ctypes.data_as(_ffi._pi32),
+        packed.x_off.ctypes.data_as(_ffi._pi64), packed.n.ctypes.data_as(_ffi._pi32), packed.d, _ffi.ptr(packed.X),
+        packed.X.shape[0], packed.vec_off.ctypes.data_as(_ffi._pi64), _ffi.ptr(packed.noise), _ffi.ptr(packed.resid),
+        None if flags is None else flags.ctypes.data_as(_ffi._pi32), info.ctypes.data_as(_ffi._pi32), pdbl(out),
+        pdbl(gparams), pdbl(gnoise), pdbl(alpha), pdbl(glog)), "tgp_small_logprob_grad")
+    return out, info, gparams, gnoise, alpha, glog
+
+
+def dims_flags(kernels):
+    """The ``want_dims`` flags of a batch: 1 for the members whose kernel sits under ONE input transform
+    (``transforms.covering_transform``), whose per-dimension scales the device then differentiates; ``None`` when no
+    member has one (the call then has no such output)."""
+    from tinygp_amd.transforms import covering_transform
+
+    flags = np.array([covering_transform(k) is not None for k in kernels], dtype=np.int32)
+    return flags if flags.any() else None
+
+
+def member_gradient(kernel, gparams, glog=None):
+    """``(kernel gradient, transform gradient)`` of one member from the device's layout: ``gparams[2 i + q]`` is
+    parameter q of op i, and the float64 array returned follows ``kernel.parameters()`` (the ``_slots`` mapping of
+    ``DirectSolver.log_probability_and_grad``).  ``glog``: the member's ``d ll / d log s_q`` row, or ``None``; the
+    transform gradient is what ``covering_transform(kernel)._logscale_gradient`` makes of it, ``None`` without one."""
+    slots: list = []
+    kernel._slots(slots)
+    if 2 * len(slots) != len(gparams):
+        raise ValueError(f"the kernel has {len(slots)} program ops, the gradient holds {len(gparams)} entries")
+    kgrad = np.array([gparams[2 * i + q] for i, pair in enumerate(slots) for q in (0, 1) if pair[q] is not None],
+                     dtype=np.float64)
+    from tinygp_amd.transforms import covering_transform
+
+    tgrad = None
+    tf = None if glog is None else covering_transform(kernel)
+    if tf is not None:
+        try:
+            tgrad = tf._logscale_gradient(np.array(glog, dtype=np.float64))
+        except NotImplementedError:
+            tgrad = None  # (Subspace, a Python callable, a full matrix: no per-dimension scale)
+    return kgrad, tgrad
+
+
+def failed_gradient(kgrad, tgrad):
+    """The two of :func:`member_gradient` for a member whose value is ``-inf``: NaN in the same shapes."""
+    kgrad = np.full(len(kgrad), np.nan)
+    return kgrad, (None if tgrad is None else np.full_like(np.asarray(tgrad, dtype=np.float64), np.nan))
+
+
+def unpack_gradients(kernels, packed: Packed, results, where, values, info, kgrads, tgrads, noise_rows, mean_rows, dtypes):
+    """Scatter one ``run_packed_grad`` result (launch member m is member ``where[m]`` of the caller's batch, its vectors
+    come back in ``dtypes[m]``) into the caller's arrays and lists; a failed or non-finite member gets NaN gradients
+    (the device already wrote NaN where the factor failed)."""
+    out, infos, gparams, gnoise, alpha, glog = results
+    for m, b in enumerate(where):
+        lo, hi = 2 * int(packed.prog_off[m]), 2 * int(packed.prog_off[m + 1])
+        kg, tg = member_gradient(kernels[b], gparams[lo:hi], None if glog is None else glog[m])
+        at, n = int(packed.vec_off[m]), int(packed.n[m])
+        bad = infos[m] != 0 or not np.isfinite(out[m])
+        if bad:
+            kg, tg = failed_gradient(kg, tg)
+        values[b], info[b], kgrads[b], tgrads[b] = out[m], infos[m], kg, tg
+        if gnoise is not None:
+            noise_rows[b] = np.full(n, np.nan, dtype=dtypes[m]) if bad else gnoise[at:at + n].astype(dtypes[m])
+            mean_rows[b] = np.full(n, np.nan, dtype=dtypes[m]) if bad else alpha[at:at + n].astype(dtypes[m])
+
+
 def reject_quasisep(kernels):
     """The dense batch does not take ``kernels.quasisep`` models: their batches are ``QuasisepSolver``'s."""
     from tinygp_amd.kernels.quasisep import Quasisep
@@ -232,6 +322,78 @@ def log_probability_datasets(kernels, Xs, ys, *, diags, means=None, return_info:
         out[where], info[where] = values, infos
     out[(info != 0) | ~np.isfinite(out)] = -np.inf
     return (out, info) if return_info else out
+
+
+def log_probability_and_grad_datasets(kernels, Xs, ys, *, diags, means=None, vectors: bool = True,
+                                      return_info: bool = False, ctx=None):
+    """:func:`log_probability_datasets` with the gradients: ``(values (B,) float64, grads)`` of B data sets under dense
+    GPs, each with points, length and noise of its own, in one call (the reference's ``jax.vmap`` over
+    ``jax.value_and_grad`` of the function that builds the GP): the restarts of an optimiser, populations of HMC
+    chains, many short light curves fitted at once.  Arguments as in :func:`log_probability_datasets`.
+
+    ``grads`` has the keys of ``GaussianProcess.log_probability_and_grad``: ``"kernel"``, a list of B float64 arrays,
+    member b's in the order of ``kernels[b].parameters()`` (the members may differ in structure); ``"noise_diag"`` and
+    ``"mean"``, lists of (n_b,) arrays in the dtype of that data set's coordinates, or ``None`` with
+    ``vectors=False`` (they are then not copied back); ``"transform"``, a list of B entries, each ``None`` or the
+    gradient with respect to the ``scale`` / ``factor`` of the one ``transforms.Linear`` / ``Cholesky`` that covers the
+    member's kernel.  A failed or non-finite member gives ``-inf`` and NaN gradients.  With ``return_info`` the B
+    ``info`` values come third.
+
+    Data sets of up to ``TGP_SMALL_MAX_N`` points that the device can lower run in the batched launches
+    (``tgp_small_logprob_grad``: one workgroup per data set, fp64; the value has the bits of
+    :func:`log_probability_datasets`); each is held to the project's bars against
+    ``GaussianProcess(kernels[b], Xs[b], diag=diags[b], mean=means[b]).log_probability_and_grad(ys[b])``.  Larger ones,
+    and any the device cannot lower, are that very call, one by one, repacked into the same shape (with its own answers:
+    it raises ``NotImplementedError`` for a kernel without a device program, such as ``kernels.Custom``)."""
+    members = check_datasets(kernels, Xs, ys, diags, means)
+    reject_quasisep(m[0] for m in members)
+    nb = len(members)
+    ks = [m[0] for m in members]
+    values, info = np.empty(nb), np.zeros(nb, dtype=np.int32)
+    kgrads, tgrads, noise_rows, mean_rows = [None] * nb, [None] * nb, [None] * nb, [None] * nb
+    batched, where = [], []
+    for b, (kernel, X, y, diag, mean) in enumerate(members):
+        lowered = lower_member(kernel, X)
+        if batched_route(len(y), lowered) and (not batched or lowered[1].shape[1] == batched[0][1].shape[1]):
+            batched.append((lowered[0], lowered[1], diag, y if mean is None else y - mean))
+            where.append(b)
+        else:
+            values[b], info[b], kgrads[b], tgrads[b], noise_rows[b], mean_rows[b] = _single_grad(kernel, X, y, diag,
+                                                                                                  mean, ctx, vectors)
+    if batched:
+        packed = pack_members(batched, labels=[f"data set {b}" for b in where])
+        results = run_packed_grad(_ffi.default_ctx() if ctx is None else ctx, packed, dims_flags(ks[b] for b in where),
+                                  vectors=vectors)
+        unpack_gradients(ks, packed, results, where, values, info, kgrads, tgrads, noise_rows, mean_rows,
+                         [members[b][2].dtype for b in where])  # (the vectors in the dtype of each data set)
+    values[(info != 0) | ~np.isfinite(values)] = -np.inf
+    grads = {"kernel": kgrads, "noise_diag": noise_rows if vectors else None, "mean": mean_rows if vectors else None,
+             "transform": tgrads}
+    return (values, grads, info) if return_info else (values, grads)
+
+
+def single_gradient(solver, resid, vectors: bool):
+    """``(value, info, kernel gradient, transform gradient, noise gradient, mean gradient)`` of one member on the
+    single path, in the batch's shapes: ``DirectSolver.log_probability_and_grad`` itself."""
+    value, g = solver.log_probability_and_grad(resid)
+    kgrad = np.array(g["kernel"], dtype=np.float64)
+    return (float(value), int(solver.info), kgrad, g["transform"], g["noise_diag"] if vectors else None,
+            g["mean"] if vectors else None)
+
+
+def _single_grad(kernel, X, y, diag, mean, ctx, vectors):
+    """One data set on the single dense path: ``GaussianProcess(kernel, X, diag=diag,
+    mean=mean).log_probability_and_grad(y)`` itself, its solver closed behind it."""
+    from tinygp_amd.gp import GaussianProcess
+    from tinygp_amd.solvers.direct import DirectSolver
+
+    kwargs = {} if ctx is None else {"ctx": ctx}
+    gp = GaussianProcess(kernel, X, diag=diag, solver=DirectSolver, **({} if mean is None else {"mean_value": mean}),
+                         **kwargs)
+    try:
+        return single_gradient(gp.solver, gp._residual(y), vectors)
+    finally:
+        gp.solver.close()
 
 
 def _single(kernel, X, y, diag, mean, ctx):
