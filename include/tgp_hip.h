@@ -388,6 +388,30 @@ int tgp_small_logprob_grad(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const
                            const double* noise_host, const double* resid_host, const int32_t* want_dims,
                            int32_t* info_host, double* out_host, double* grad_params_host, double* grad_noise_host,
                            double* alpha_host, double* grad_logscale_host);
+/* The same members with their predictions at test points of their own, still one launch per batch: what the
+ * reference's users get from jax.vmap over gp.predict(y, X_test, return_var=True) (gp.py:225-271).  The arguments of
+ * tgp_small_logprob, validated and split into launches in the same way, and
+ *   Xt_host / xt_off / m   member b predicts at rows xt_off[b] .. xt_off[b] + m[b] of Xt_host (xt_rows, d) row-major;
+ *                      m[b] = 0 is allowed (value only); two members may name the same rows (shared test points)
+ *   pred_progs / pred_prog_off   NULL, or second programs one after another: member b evaluates k* and k** with ops
+ *                      pred_prog_off[b] .. pred_prog_off[b + 1] (predict(kernel=k1): one term of a sum); an empty
+ *                      extent means the member's own program
+ *   out_off            member b's m[b] means and variances go to the entries at out_off[b] of mean_host / var_host
+ *   out_host / info_host   the values, with the bits of tgp_small_logprob's, and info
+ *   mean_host          k*^T K^-1 r per test point
+ *   var_host           k** - |L^-1 k*|^2 per test point (no jitter, no noise), or NULL: the solve is skipped
+ * A workgroup takes at most TGP_SMALL_PRED_CHUNK test points: a member with more is factored once per chunk, every
+ * copy with the same arithmetic, so that a prediction's bits depend on its member's data and its own test point
+ * alone.  A member whose factorisation fails has NaN in its value and in all of its predictions.
+ * TGP_E_ARG as for tgp_small_logprob, and for test rows outside Xt, a negative m or offset, an invalid second program. */
+#ifndef TGP_SMALL_PRED_CHUNK
+#define TGP_SMALL_PRED_CHUNK 512
+#endif
+int tgp_small_predict(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off, const int64_t* x_off,
+                      const int32_t* n, int32_t d, const double* X_host, int64_t x_rows, const int64_t* vec_off,
+                      const double* noise_host, const double* resid_host, const double* Xt_host, int64_t xt_rows,
+                      const int64_t* xt_off, const int32_t* m, const tgp_kop* pred_progs, const int32_t* pred_prog_off,
+                      const int64_t* out_off, int32_t* info_host, double* out_host, double* mean_host, double* var_host);
 
 /* ---- block-cyclic column Cholesky over the GPUs of one node (BASELINE configs 4 / 5) ----------
  * The reference has NO multi-device code; these entry points are one RANK's share

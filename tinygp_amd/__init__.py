@@ -17,5 +17,6 @@ from tinygp_amd.solvers.quasisep import log_probability_series as log_probabilit
 from tinygp_amd.solvers.quasisep import log_probability_and_grad_series as log_probability_and_grad_series
 from tinygp_amd.solvers.small import log_probability_and_grad_datasets as log_probability_and_grad_datasets
 from tinygp_amd.solvers.small import log_probability_datasets as log_probability_datasets
+from tinygp_amd.solvers.small import predict_datasets as predict_datasets
 
 __version__ = "0.1.0"

@@ -101,6 +101,8 @@ SIGNATURES = {
     "tgp_small_logprob": [_vp, _i32, _vp, _pi32, _pi64, _pi32, _i32, _vp, _i64, _pi64, _vp, _vp, _pi32, _pdbl],
     "tgp_small_logprob_grad": [_vp, _i32, _vp, _pi32, _pi64, _pi32, _i32, _vp, _i64, _pi64, _vp, _vp, _pi32, _pi32, _pdbl,
                                _pdbl, _pdbl, _pdbl, _pdbl],
+    "tgp_small_predict": [_vp, _i32, _vp, _pi32, _pi64, _pi32, _i32, _vp, _i64, _pi64, _vp, _vp, _vp, _i64, _pi64, _pi32,
+                          _vp, _pi32, _pi64, _pi32, _pdbl, _pdbl, _pdbl],
     "tgp_trace_factor": [_i64, C.c_char_p, _i32, _pi64, _i64, _pi64],
     "tgp_chain_stamps": [_vp, _pi64, _i64, _pi64],
     "tgp_chain_task": [_i64, _i64, _i64, _i64, _i64, _pi32, _pi64],
@@ -182,6 +184,8 @@ SIGNATURES = {
 
 ABI_VERSION = 6  # TGP_ABI_VERSION of include/tgp_hip.h
 SMALL_MAX_N = 192  # TGP_SMALL_MAX_N: the largest member of tgp_small_logprob (one workgroup, the matrix in LDS)
+SMALL_PRED_CHUNK = 512  # TGP_SMALL_PRED_CHUNK: the test points one workgroup of tgp_small_predict takes
+KPROG_BYTES = 776  # sizeof(KProg): n, 32 ops and 32 metrics (int32, padded to 8), 32 p0 and 32 p1 (double)
 
 
 def _mapped_hip_runtimes() -> list[str]:

@@ -1,4 +1,5 @@
-// small.hip -- batches of SMALL dense problems, one workgroup each (tgp_small_logprob, tgp_small_logprob_grad).
+// small.hip -- batches of SMALL dense problems, one workgroup each (tgp_small_logprob, tgp_small_logprob_grad,
+// tgp_small_predict).
 //
 // The dense path of chol.hip pads every matrix to 128-row tiles and pays a handle, uploads, a launch chain and a host
 // join per evaluation: at N <= 192 that is all overhead.  Here a workgroup of 256 threads owns a whole member: it
@@ -23,6 +24,11 @@
 // access pattern of the factorisation), then one pass over the entries i >= j per derivative with the evaluators of
 // kprog_eval.h.  The assembly, the factorisation and the two value reductions are ONE text for both kernels: the
 // gradient kernel's value has the bits of small_logprob_kernel's.
+//
+// The prediction (small_predict_kernel) shares the value's text and the gradient's alpha (small_alpha); L and alpha
+// then stay in LDS, read-only, and every wave walks test points of its own without another barrier: the cross
+// covariances of a point in registers, the mean as their product with alpha, the variance by a forward substitution
+// against L inside the wave.
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -49,6 +55,25 @@ struct SmallRow {
   int32_t n, d, prog, want_dims;
 };
 static_assert(sizeof(SmallRow) == 48 && sizeof(KProg) % 8 == 0, "the staging buffer is carved in 8-byte units");
+
+// one table row of a prediction launch: a member, or one chunk of a member's test points (every chunk factors the
+// member again).  The member's fields as in SmallRow; xt_off in rows of the launch's Xt and out_off in the launch's
+// mean / variance arrays, both at this chunk's first point; m: this chunk's points (0 .. TGP_SMALL_PRED_CHUNK);
+// pred_prog: the program of k* and k**, or -1 for the member's own; slot: where the value and info go, -1 for every
+// chunk but a member's first
+struct SmallPredRow {
+  int64_t x_off, noise_off, resid_off, xt_off, out_off;
+  int32_t n, d, prog, pred_prog, m, slot;
+};
+static_assert(sizeof(SmallPredRow) == 64, "the staging buffer is carved in 8-byte units");
+
+// test points a wave carries through the forward substitution at once (one LDS read of l_ip feeds this many FMAs)
+#ifndef TGP_SMALL_PRED_T
+#define TGP_SMALL_PRED_T 4
+#endif
+constexpr int SMALL_PRED_T = TGP_SMALL_PRED_T;
+static_assert(SMALL_PRED_T == 1 || SMALL_PRED_T == 2 || SMALL_PRED_T == 4, "T is chosen from {1, 2, 4}");
+constexpr int SMALL_PRED_ROWS = (TGP_SMALL_MAX_N + 63) / 64;  // rows of a member one lane holds in registers
 
 __host__ __device__ constexpr int64_t small_lds_doubles(int64_t n) { return n * (n + 1) / 2 + n; }
 static_assert(small_lds_doubles(TGP_SMALL_MAX_N) * 8 + 2 * SMALL_THREADS * 8 <= 163840,
@@ -104,9 +129,10 @@ __device__ __forceinline__ int small_assemble_factor(double* A, const KProg& kp,
   return fail;
 }
 
-// Steps 5 + 6: the value from the factored trapezoid (the pivots on the diagonal, z in row n), written by thread 0.
+// Steps 5 + 6: the value from the factored trapezoid (the pivots on the diagonal, z in row n), written by thread 0 to
+// entry `slot` of out and info (a negative slot: computed, not written -- a later chunk of a prediction).
 __device__ __forceinline__ void small_write_value(const double* A, double (&red)[2][SMALL_THREADS], int n, int fail,
-                                                  double* __restrict__ out, int32_t* __restrict__ info) {
+                                                  double* __restrict__ out, int32_t* __restrict__ info, int64_t slot) {
   // 5: sum log L_pp and sum z_p^2 (one term per thread: n < 256), a fixed tree
   double sl = 0.0, sz = 0.0;
   if (fail == 0 && int(threadIdx.x) < n) {
@@ -126,10 +152,29 @@ __device__ __forceinline__ void small_write_value(const double* A, double (&red)
     __syncthreads();
   }
   // 6
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0 && slot >= 0) {
     const double v = -0.5 * red[1][0] - red[0][0] - 0.5 * double(n) * 1.8378770664093453;  // log(2 pi)
-    out[blockIdx.x] = fail ? __builtin_nan("") : v;
-    info[blockIdx.x] = fail;
+    out[slot] = fail ? __builtin_nan("") : v;
+    info[slot] = fail;
+  }
+}
+
+// Steps 7 + 8 of the gradient and of the prediction: the diagonal words become L_pp (they held the pivots L_pp^2),
+// once; then alpha = K^-1 r by the backward substitution L^T alpha = z in place in row n: thread k carries z_k in a
+// register and takes L_pk alpha_p from it for p = n - 1 .. k + 1, one barrier per step.  alpha_p lands where z_p was;
+// the last barrier of the loop follows the last write.
+__device__ __forceinline__ void small_alpha(double* A, int n) {
+  const int tid = threadIdx.x;
+  // 7
+  if (tid < n) A[col_off(tid, n)] = sqrt(A[col_off(tid, n)]);
+  __syncthreads();
+  // 8
+  double zk = tid < n ? A[col_off(tid, n) + n - tid] : 0.0;
+  for (int p = n - 1; p >= 0; --p) {
+    const double* cp = A + col_off(p, n);
+    if (tid == p) A[col_off(p, n) + n - p] = zk / cp[0];
+    __syncthreads();
+    if (tid < p) zk = __builtin_fma(-A[col_off(tid, n) + p - tid], cp[n - p], zk);
   }
 }
 
@@ -146,7 +191,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_logprob_kernel(const Smal
   const KProg& kp = progs[row.prog];
   const int n = row.n, d = row.d;
   const int fail = small_assemble_factor(A, kp, X + row.x_off * d, noise + row.noise_off, resid + row.resid_off, n, d);
-  small_write_value(A, red, n, fail, out, info);
+  small_write_value(A, red, n, fail, out, info, blockIdx.x);
 }
 
 // Value AND gradient of one member.  After the value (the text above):
@@ -188,7 +233,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_grad_kernel(const SmallRo
   double* gd = grad_dims + int64_t(blockIdx.x) * d;
 
   const int fail = small_assemble_factor(A, kp, x, noise + row.noise_off, resid + row.resid_off, n, d);
-  small_write_value(A, red, n, fail, out, info);
+  small_write_value(A, red, n, fail, out, info, blockIdx.x);
   if (fail) {  // the workgroup's decision: NaN in every gradient of this member
     const double nan = __builtin_nan("");
     for (int t = tid; t < 2 * kp.n; t += SMALL_THREADS) gp[t] = nan;
@@ -198,20 +243,8 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_grad_kernel(const SmallRo
   }
   __syncthreads();  // thread 0 has read the scratch
 
-  // 7
-  if (tid < n) A[col_off(tid, n)] = sqrt(A[col_off(tid, n)]);
-  __syncthreads();
-
-  // 8: alpha_p lands where z_p was
-  {
-    double zk = tid < n ? A[col_off(tid, n) + n - tid] : 0.0;
-    for (int p = n - 1; p >= 0; --p) {
-      const double* cp = A + col_off(p, n);
-      if (tid == p) A[col_off(p, n) + n - p] = zk / cp[0];
-      __syncthreads();
-      if (tid < p) zk = __builtin_fma(-A[col_off(tid, n) + p - tid], cp[n - p], zk);
-    }
-  }
+  // 7 + 8
+  small_alpha(A, n);
 
   // 9 (rows j + 1 .. n - 1 only: row n is alpha's)
   for (int j = 0; j < n; ++j) {
@@ -312,6 +345,140 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_grad_kernel(const SmallRo
 }
 static_assert(TGP_SMALL_MAX_N < SMALL_THREADS, "one reduction term per thread");
 
+// Value and prediction of one table row.  After the value (steps 1 - 6, the text above) and alpha (small_alpha), L and
+// alpha are read-only and no barrier follows: wave w takes the groups g = w, w + 4, .. of T test points
+// t = g T .. g T + T - 1.  Lane l holds rows i = l, l + 64, l + 128 of every point of the group in registers:
+//   k*   k*_i = k(x_i, x*) and k** = k(x*, x*) from ONE loop over the (row, point) pairs -- one inlined copy of the
+//        evaluator, the registers picked by selects -- with the row's prediction program, or the member's own;
+//   mean sum_i k*_i alpha_i: each lane adds its rows in increasing i, then the fixed 64-lane butterfly;
+//   var  k** - sum_p v_p^2 with v = L^-1 k*, the column-oriented forward substitution inside the wave: for
+//        p = 0 .. n - 1 the lanes divide their row of p's 64-row block by l_pp, the owner's quotient v_p = k_p / l_pp
+//        is read from lane p mod 64 (p is wave-uniform), every lane takes l_ip v_p from its rows i > p by fma -- column p of L from LDS,
+//        consecutive rows, ONE read for the T points -- and adds v_p^2 to a sum that every lane carries alike, in
+//        increasing p.  Skipped when no variance is asked for.
+// A point's arithmetic never looks at the other points of its group: the last, partial group computes its missing
+// points on the chunk's last point and does not store them.  A failed pivot puts NaN into every prediction of the row.
+template <int T>
+__global__ __launch_bounds__(SMALL_THREADS) void small_predict_kernel(const SmallPredRow* __restrict__ rows,
+                                                                        const KProg* __restrict__ progs,
+                                                                        const double* __restrict__ X,
+                                                                        const double* __restrict__ noise,
+                                                                        const double* __restrict__ resid,
+                                                                        const double* __restrict__ Xt,
+                                                                        double* __restrict__ out,
+                                                                        int32_t* __restrict__ info,
+                                                                        double* __restrict__ mean_out,
+                                                                        double* __restrict__ var_out) {
+  extern __shared__ __attribute__((aligned(16))) double A[];  // the packed trapezoid
+  __shared__ double red[2][SMALL_THREADS];
+  const SmallPredRow row = rows[blockIdx.x];
+  const KProg& kp = progs[row.prog];
+  const KProg& pk = progs[row.pred_prog >= 0 ? row.pred_prog : row.prog];
+  const int n = row.n, d = row.d, m = row.m;
+  const double* x = X + row.x_off * d;
+  const double* xt = Xt + row.xt_off * d;
+  const int tid = threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double* pm = mean_out + row.out_off;
+  double* pv = var_out ? var_out + row.out_off : nullptr;
+
+  const int fail = small_assemble_factor(A, kp, x, noise + row.noise_off, resid + row.resid_off, n, d);
+  small_write_value(A, red, n, fail, out, info, row.slot);
+  if (fail) {  // the workgroup's decision: NaN in every prediction of this row
+    const double nan = __builtin_nan("");
+    for (int t = tid; t < m; t += SMALL_THREADS) {
+      pm[t] = nan;
+      if (pv) pv[t] = nan;
+    }
+    return;
+  }
+  __syncthreads();  // thread 0 has read the scratch
+
+  // 7 + 8
+  small_alpha(A, n);
+
+  constexpr int R = SMALL_PRED_ROWS;
+  // this lane's alpha_i and the offsets of its rows (rows past n: weight zero, never read)
+  double al[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = lane + 64 * r;
+    al[r] = i < n ? A[col_off(i, n) + n - i] : 0.0;
+  }
+
+  const int groups = (m + T - 1) / T;
+  for (int g = wave; g < groups; g += SMALL_WAVES) {
+    double k[R][T] = {}, kss[T] = {};
+    // k* and k**: pair q = r T + t is (row lane + 64 r, point t), pairs R T .. R T + T - 1 are (point t, point t)
+#pragma unroll 1
+    for (int q = 0; q < (R + 1) * T; ++q) {
+      const int r = q / T, t = q - r * T;
+      const int pt = min(g * T + t, m - 1);
+      const int i = lane + 64 * r;
+      if (r < R && 64 * r >= n) continue;  // (wave-uniform: no lane has a row here)
+      const double* b = xt + int64_t(pt) * d;
+      const double* a = r < R ? x + int64_t(min(i, n - 1)) * d : b;
+      double r1, r2, r3;
+      pair_dist<double, 2, 0>(a, b, d, r1, r2, r3);
+      double v = eval_kprog<double, 2>(pk, r1, r2, r3);
+      if (r < R && i >= n) v = 0.0;
+#pragma unroll
+      for (int rr = 0; rr < R; ++rr)
+#pragma unroll
+        for (int tt = 0; tt < T; ++tt)
+          if (q == rr * T + tt) k[rr][tt] = v;
+#pragma unroll
+      for (int tt = 0; tt < T; ++tt)
+        if (q == R * T + tt) kss[tt] = v;
+    }
+
+    // the mean
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      double s = 0.0;
+#pragma unroll
+      for (int r = 0; r < R; ++r) s += k[r][t] * al[r];
+#pragma unroll
+      for (int sft = 32; sft > 0; sft >>= 1) s += __shfl_xor(s, sft);
+      if (lane == 0 && g * T + t < m) pm[g * T + t] = s;
+    }
+    if (!pv) continue;
+
+    // the variance
+    double ss[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) ss[t] = 0.0;
+#pragma unroll
+    for (int r0 = 0; r0 < R; ++r0) {
+      const int pend = min(n, 64 * r0 + 64);
+      for (int p = 64 * r0; p < pend; ++p) {
+        const double* cp = A + col_off(p, n);
+        const double lpp = cp[0];
+        double vp[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+          const double q = k[r0][t] / lpp;  // (the owner's is v_p)
+          const int lo = __builtin_amdgcn_readlane(__double2loint(q), p & 63);
+          const int hi = __builtin_amdgcn_readlane(__double2hiint(q), p & 63);
+          vp[t] = __hiloint2double(hi, lo);
+          ss[t] += vp[t] * vp[t];
+        }
+#pragma unroll
+        for (int r = r0; r < R; ++r) {
+          const int i = lane + 64 * r;
+          if (i > p && i < n) {
+            const double lip = cp[i - p];
+#pragma unroll
+            for (int t = 0; t < T; ++t) k[r][t] = __builtin_fma(-lip, vp[t], k[r][t]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+      if (lane == 0 && g * T + t < m) pv[g * T + t] = kss[t] - ss[t];
+  }
+}
+
 // the gradient's host outputs (tgp_small_logprob_grad); `on` is false for the value alone
 struct SmallGradOut {
   bool on = false;
@@ -322,12 +489,28 @@ struct SmallGradOut {
   double* logscale = nullptr;
 };
 
+// the prediction's host arguments (tgp_small_predict); null for the other two entry points
+struct SmallPredIn {
+  const double* Xt = nullptr;
+  int64_t xt_rows = 0;
+  const int64_t* xt_off = nullptr;
+  const int32_t* m = nullptr;
+  const tgp_kop* progs = nullptr;
+  const int32_t* prog_off = nullptr;
+  const int64_t* out_off = nullptr;
+  double* mean = nullptr;
+  double* var = nullptr;
+};
+
 // what members [b0, b1) need in the staging buffer, and where
 struct SmallLaunch {
   int64_t b0 = 0, b1 = 0, max_n = 0;
   int64_t x_doubles = 0, vec_doubles = 0, ops = 0;
-  std::vector<char> host;  // rows | programs | X | noise | residual, as on the device
-  std::vector<double> back;  // the gradient's noise gradient | alpha as on the device, scattered after the join
+  int64_t pred_rows = 0, pred_progs = 0, xt_doubles = 0, out_doubles = 0;  // a prediction's table rows, second
+                                                                           // programs, test points and outputs
+  std::vector<char> host;  // rows | programs | X | noise | residual (| test points), as on the device
+  std::vector<double> back;  // the gradient's noise gradient | alpha, or the prediction's mean | variance, as on the
+                             // device, scattered after the join
 };
 
 // inputs | values | info, and for the gradient | parameter gradients | noise gradient | alpha | scale gradients
@@ -340,11 +523,27 @@ int64_t grad_doubles(bool grad, int64_t nb, int64_t ops, int64_t vec_doubles, in
   return grad ? 2 * ops + 2 * vec_doubles + nb * d : 0;
 }
 
+// a prediction launch: table rows (one per chunk of test points) | programs, the second ones behind the members' |
+// X | noise | residual | test points | values | info | means (| variances)
+int64_t pred_launch_bytes(int64_t nb, int64_t rows, int64_t pred_progs, int64_t x_doubles, int64_t vec_doubles,
+                          int64_t xt_doubles, int64_t out_doubles, bool var) {
+  return rows * int64_t(sizeof(SmallPredRow)) + (nb + pred_progs) * int64_t(sizeof(KProg)) +
+         (x_doubles + 2 * vec_doubles + xt_doubles) * 8 + nb * 8 + round_up(nb * 4, 8) + out_doubles * (var ? 16 : 8);
+}
+
+int64_t pred_chunks(int64_t m) { return m <= 0 ? 1 : (m + TGP_SMALL_PRED_CHUNK - 1) / TGP_SMALL_PRED_CHUNK; }
+
 // enqueues every launch; the host buffers in `launches` must outlive the join
 int small_enqueue(tgp_ctx* ctx, std::vector<SmallLaunch>& launches, int32_t d, const int32_t* prog_off,
-                  int32_t* info_host, double* out_host, const SmallGradOut& g) {
+                  int32_t* info_host, double* out_host, const SmallGradOut& g, const SmallPredIn* p) {
   hipStream_t st = ctx->stream;
-  if (!g.on && !ctx->small_lds_raised) {
+  if (p && !ctx->small_pred_lds_raised) {
+    TGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(small_predict_kernel<SMALL_PRED_T>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    int(small_lds_doubles(TGP_SMALL_MAX_N) * 8)));
+    ctx->small_pred_lds_raised = true;
+  }
+  if (!p && !g.on && !ctx->small_lds_raised) {
     TGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(small_logprob_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize,
                                     int(small_lds_doubles(TGP_SMALL_MAX_N) * 8)));
@@ -358,12 +557,37 @@ int small_enqueue(tgp_ctx* ctx, std::vector<SmallLaunch>& launches, int32_t d, c
   }
   int64_t need = 0;
   for (const SmallLaunch& l : launches)
-    need = std::max(need, launch_bytes(l.b1 - l.b0, l.x_doubles, l.vec_doubles,
-                                       grad_doubles(g.on, l.b1 - l.b0, l.ops, l.vec_doubles, d)));
+    need = std::max(need, p ? pred_launch_bytes(l.b1 - l.b0, l.pred_rows, l.pred_progs, l.x_doubles, l.vec_doubles,
+                                                l.xt_doubles, l.out_doubles, p->var != nullptr)
+                            : launch_bytes(l.b1 - l.b0, l.x_doubles, l.vec_doubles,
+                                           grad_doubles(g.on, l.b1 - l.b0, l.ops, l.vec_doubles, d)));
   TGP_TRY(ensure_work(ctx, size_t(need)));
   for (SmallLaunch& l : launches) {
     const int64_t nb = l.b1 - l.b0;
     char* base = static_cast<char*>(ctx->d_work);
+    if (p) {
+      const SmallPredRow* prows = reinterpret_cast<const SmallPredRow*>(base);
+      const KProg* progs = reinterpret_cast<const KProg*>(base + l.pred_rows * sizeof(SmallPredRow));
+      const double* X = reinterpret_cast<const double*>(progs + nb + l.pred_progs);
+      const double* noise = X + l.x_doubles;
+      const double* resid = noise + l.vec_doubles;
+      const double* Xt = resid + l.vec_doubles;
+      double* out = const_cast<double*>(Xt) + l.xt_doubles;
+      int32_t* info = reinterpret_cast<int32_t*>(out + nb);
+      double* mean = out + nb + round_up(nb * 4, 8) / 8;
+      double* var = p->var ? mean + l.out_doubles : nullptr;
+      TGP_HIP_TRY(hipMemcpyAsync(base, l.host.data(), l.host.size(), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(small_predict_kernel<SMALL_PRED_T>, dim3(unsigned(l.pred_rows)), dim3(SMALL_THREADS),
+                         size_t(small_lds_doubles(l.max_n) * 8), st, prows, progs, X, noise, resid, Xt, out, info, mean,
+                         var);
+      TGP_HIP_TRY(hipGetLastError());
+      l.back.resize(size_t(l.out_doubles * (p->var ? 2 : 1)));
+      if (!l.back.empty())
+        TGP_HIP_TRY(hipMemcpyAsync(l.back.data(), mean, l.back.size() * 8, hipMemcpyDeviceToHost, st));
+      TGP_HIP_TRY(hipMemcpyAsync(out_host + l.b0, out, size_t(nb) * 8, hipMemcpyDeviceToHost, st));
+      TGP_HIP_TRY(hipMemcpyAsync(info_host + l.b0, info, size_t(nb) * 4, hipMemcpyDeviceToHost, st));
+      continue;
+    }
     const SmallRow* rows = reinterpret_cast<const SmallRow*>(base);
     const KProg* progs = reinterpret_cast<const KProg*>(base + nb * sizeof(SmallRow));
     const double* X = reinterpret_cast<const double*>(base + nb * (sizeof(SmallRow) + sizeof(KProg)));
@@ -404,18 +628,22 @@ int small_enqueue(tgp_ctx* ctx, std::vector<SmallLaunch>& launches, int32_t d, c
 int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off, const int64_t* x_off,
                const int32_t* n, int32_t d, const double* X_host, int64_t x_rows, const int64_t* vec_off,
                const double* noise_host, const double* resid_host, int32_t* info_host, double* out_host,
-               const SmallGradOut& g) {
+               const SmallGradOut& g, const SmallPredIn* p = nullptr) {
   TGP_ARG_CHECK(ctx != nullptr, "null context");
   TGP_ARG_CHECK(nb >= 0, "negative number of members (%d)", nb);
   if (nb == 0) return TGP_OK;
   std::unique_lock<std::recursive_mutex> lock(ctx->mu);
   TGP_HIP_TRY(hipSetDevice(ctx->device));
   TGP_ARG_CHECK(progs && prog_off && x_off && n && X_host && vec_off && noise_host && resid_host && info_host && out_host &&
-                    (!g.on || g.params),
+                    (!g.on || g.params) && (!p || (p->xt_off && p->m && p->out_off && p->mean && (p->Xt || p->xt_rows == 0) &&
+                                                   (!p->progs == !p->prog_off))),
                 "null argument");
   TGP_ARG_CHECK(d >= 1 && d <= TGP_MAX_DIM, "the input dimension must be 1 .. %d (got %d)", TGP_MAX_DIM, d);
   TGP_ARG_CHECK(x_rows >= 0, "negative number of coordinate rows (%lld)", (long long)x_rows);
+  TGP_ARG_CHECK(!p || p->xt_rows >= 0, "negative number of test rows (%lld)", (long long)(p ? p->xt_rows : 0));
   std::vector<KProg> kps(size_t(nb), KProg{});
+  std::vector<KProg> pks(p && p->progs ? size_t(nb) : 0, KProg{});  // the second programs, where a member names one
+  std::vector<char> has_pk(size_t(nb), 0);
   for (int64_t b = 0; b < nb; ++b) {
     TGP_ARG_CHECK(n[b] >= 1 && n[b] <= TGP_SMALL_MAX_N, "member %lld: n must be 1 .. %d (got %d)", (long long)b,
                   TGP_SMALL_MAX_N, n[b]);
@@ -430,6 +658,25 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
       set_error("member %lld: %s", (long long)b, why.c_str());
       return TGP_E_ARG;
     }
+    if (!p) continue;
+    TGP_ARG_CHECK(p->m[b] >= 0, "member %lld: negative number of test points (%d)", (long long)b, p->m[b]);
+    TGP_ARG_CHECK(p->xt_off[b] >= 0 && p->xt_off[b] <= p->xt_rows - p->m[b],
+                  "member %lld: test rows %lld .. %lld lie outside Xt (%lld rows)", (long long)b, (long long)p->xt_off[b],
+                  (long long)(p->xt_off[b] + p->m[b]), (long long)p->xt_rows);
+    TGP_ARG_CHECK(p->out_off[b] >= 0, "member %lld: negative offset into the predictions (%lld)", (long long)b,
+                  (long long)p->out_off[b]);
+    if (p->progs) {
+      TGP_ARG_CHECK(p->prog_off[b] >= 0 && p->prog_off[b + 1] >= p->prog_off[b],
+                    "member %lld: negative prediction program extent", (long long)b);
+      if (p->prog_off[b + 1] > p->prog_off[b]) {
+        if (make_kprog(p->progs + p->prog_off[b], p->prog_off[b + 1] - p->prog_off[b], &pks[size_t(b)]) != TGP_OK) {
+          const std::string why = tgp_last_error();
+          set_error("member %lld: prediction program: %s", (long long)b, why.c_str());
+          return TGP_E_ARG;
+        }
+        has_pk[size_t(b)] = 1;
+      }
+    }
   }
   // the split: launches are filled in the order given and end before the member that would take the staging buffer
   // past its cap; coordinates that several members of a launch share (same offset, same length) are staged once
@@ -438,15 +685,38 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
     SmallLaunch l;
     l.b0 = b0;
     std::map<std::pair<int64_t, int32_t>, int64_t> seen;  // (x_off, n) -> first row in the launch's X
+    std::map<std::pair<int64_t, int32_t>, int64_t> seen_t;  // (xt_off, m) -> first row in the launch's Xt
     std::vector<SmallRow> rows;
+    std::vector<SmallPredRow> prows;
+    std::vector<KProg> lpks;
     int64_t b = b0;
     for (; b < nb; ++b) {
       const auto key = std::make_pair(x_off[b], n[b]);
       const bool fresh = seen.find(key) == seen.end();
       const int64_t xd = l.x_doubles + (fresh ? int64_t(n[b]) * d : 0), vd = l.vec_doubles + n[b];
       const int64_t ops = int64_t(prog_off[b + 1]) - prog_off[b0];
-      if (b > b0 && launch_bytes(b - b0 + 1, xd, vd, grad_doubles(g.on, b - b0 + 1, ops, vd, d)) > SMALL_STAGE_BYTES) break;
-      if (fresh) seen[key] = l.x_doubles / d;
+      if (p) {  // the member's chunks, second program, test points (staged once per (offset, count)) and outputs
+        const auto key_t = std::make_pair(p->xt_off[b], p->m[b]);
+        const bool fresh_t = p->m[b] > 0 && seen_t.find(key_t) == seen_t.end();
+        const int64_t nr = l.pred_rows + pred_chunks(p->m[b]), np = l.pred_progs + has_pk[size_t(b)];
+        const int64_t td = l.xt_doubles + (fresh_t ? int64_t(p->m[b]) * d : 0), od = l.out_doubles + p->m[b];
+        if (b > b0 && pred_launch_bytes(b - b0 + 1, nr, np, xd, vd, td, od, p->var != nullptr) > SMALL_STAGE_BYTES) break;
+        if (fresh) seen[key] = l.x_doubles / d;
+        if (fresh_t) seen_t[key_t] = l.xt_doubles / d;
+        for (int64_t c = 0; c < pred_chunks(p->m[b]); ++c) {
+          const int64_t at = c * TGP_SMALL_PRED_CHUNK;
+          prows.push_back(SmallPredRow{seen[key], l.vec_doubles, l.vec_doubles,
+                                       (p->m[b] > 0 ? seen_t[key_t] : 0) + at, l.out_doubles + at, n[b], d,
+                                       int32_t(b - b0), has_pk[size_t(b)] ? int32_t(l.pred_progs) : -1,
+                                       int32_t(std::min<int64_t>(p->m[b] - at, TGP_SMALL_PRED_CHUNK)),
+                                       c == 0 ? int32_t(b - b0) : -1});
+        }
+        if (has_pk[size_t(b)]) lpks.push_back(pks[size_t(b)]);
+        l.pred_rows = nr, l.pred_progs = np, l.xt_doubles = td, l.out_doubles = od;
+      } else {
+        if (b > b0 && launch_bytes(b - b0 + 1, xd, vd, grad_doubles(g.on, b - b0 + 1, ops, vd, d)) > SMALL_STAGE_BYTES) break;
+        if (fresh) seen[key] = l.x_doubles / d;
+      }
       rows.push_back(SmallRow{seen[key], l.vec_doubles, l.vec_doubles, 2 * (int64_t(prog_off[b]) - prog_off[b0]), n[b], d,
                               int32_t(b - b0), int32_t(g.want_dims && g.want_dims[b] ? 1 : 0)});
       l.x_doubles = xd, l.vec_doubles = vd, l.ops = ops;
@@ -454,15 +724,28 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
     }
     l.b1 = b;
     const int64_t cnt = b - b0;
-    l.host.resize(size_t(cnt * int64_t(sizeof(SmallRow) + sizeof(KProg)) + (l.x_doubles + 2 * l.vec_doubles) * 8));
+    for (SmallPredRow& r : prows)  // the second programs follow the launch's cnt member programs
+      if (r.pred_prog >= 0) r.pred_prog += int32_t(cnt);
+    const int64_t table = p ? l.pred_rows * int64_t(sizeof(SmallPredRow)) : cnt * int64_t(sizeof(SmallRow));
+    l.host.resize(size_t(table + (cnt + l.pred_progs) * int64_t(sizeof(KProg)) +
+                         (l.x_doubles + 2 * l.vec_doubles + l.xt_doubles) * 8));
     char* w = l.host.data();
-    std::memcpy(w, rows.data(), size_t(cnt) * sizeof(SmallRow));
-    w += cnt * sizeof(SmallRow);
+    if (p) {
+      std::memcpy(w, prows.data(), size_t(table));
+    } else {
+      std::memcpy(w, rows.data(), size_t(table));
+    }
+    w += table;
     std::memcpy(w, &kps[size_t(b0)], size_t(cnt) * sizeof(KProg));
     w += cnt * sizeof(KProg);
+    if (l.pred_progs) std::memcpy(w, lpks.data(), size_t(l.pred_progs) * sizeof(KProg));
+    w += l.pred_progs * sizeof(KProg);
     double* xs = reinterpret_cast<double*>(w);
     double* nzs = xs + l.x_doubles;
     double* rss = nzs + l.vec_doubles;
+    double* xts = rss + l.vec_doubles;
+    for (const auto& kv : seen_t)
+      std::memcpy(xts + kv.second * d, p->Xt + kv.first.first * d, size_t(kv.first.second) * d * 8);
     for (const auto& kv : seen)
       std::memcpy(xs + kv.second * d, X_host + kv.first.first * d, size_t(kv.first.second) * d * 8);
     for (int64_t m = 0; m < cnt; ++m) {
@@ -474,7 +757,7 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
     b0 = b;
   }
   // one host join, on every path: the host buffers above are read by the copies that were enqueued
-  const int status = small_enqueue(ctx, launches, d, prog_off, info_host, out_host, g);
+  const int status = small_enqueue(ctx, launches, d, prog_off, info_host, out_host, g, p);
   const hipError_t joined = hipStreamSynchronize(ctx->stream);
   TGP_TRY(status);
   TGP_HIP_TRY(joined);
@@ -482,6 +765,13 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
   for (const SmallLaunch& l : launches) {
     if (l.back.empty()) continue;
     int64_t at = 0;
+    if (p) {  // the predictions go to the caller's offsets
+      for (int64_t b = l.b0; b < l.b1; at += p->m[b], ++b) {
+        std::memcpy(p->mean + p->out_off[b], l.back.data() + at, size_t(p->m[b]) * 8);
+        if (p->var) std::memcpy(p->var + p->out_off[b], l.back.data() + l.out_doubles + at, size_t(p->m[b]) * 8);
+      }
+      continue;
+    }
     for (int64_t b = l.b0; b < l.b1; at += n[b], ++b) {
       if (g.noise) std::memcpy(g.noise + vec_off[b], l.back.data() + at, size_t(n[b]) * 8);
       if (g.alpha) std::memcpy(g.alpha + vec_off[b], l.back.data() + l.vec_doubles + at, size_t(n[b]) * 8);
@@ -519,4 +809,25 @@ extern "C" int tgp_small_logprob_grad(tgp_ctx* ctx, int32_t nb, const tgp_kop* p
   g.logscale = grad_logscale_host;
   return small_call(ctx, nb, progs, prog_off, x_off, n, d, X_host, x_rows, vec_off, noise_host, resid_host, info_host,
                     out_host, g);
+}
+
+extern "C" int tgp_small_predict(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off,
+                                 const int64_t* x_off, const int32_t* n, int32_t d, const double* X_host,
+                                 int64_t x_rows, const int64_t* vec_off, const double* noise_host,
+                                 const double* resid_host, const double* Xt_host, int64_t xt_rows,
+                                 const int64_t* xt_off, const int32_t* m, const tgp_kop* pred_progs,
+                                 const int32_t* pred_prog_off, const int64_t* out_off, int32_t* info_host,
+                                 double* out_host, double* mean_host, double* var_host) {
+  SmallPredIn p;
+  p.Xt = Xt_host;
+  p.xt_rows = xt_rows;
+  p.xt_off = xt_off;
+  p.m = m;
+  p.progs = pred_progs;
+  p.prog_off = pred_prog_off;
+  p.out_off = out_off;
+  p.mean = mean_host;
+  p.var = var_host;
+  return small_call(ctx, nb, progs, prog_off, x_off, n, d, X_host, x_rows, vec_off, noise_host, resid_host, info_host,
+                    out_host, SmallGradOut{}, &p);
 }

@@ -29,6 +29,10 @@ from tinygp_amd.solvers import DirectSolver, QuasisepSolver
 __all__ = ["GaussianProcess", "ConditionResult"]
 
 
+def _eval_mean(mean_function, X, n, dtype):
+    return means.evaluate_mean(mean_function, X, n, dtype)  # (methods below take an argument named ``means``)
+
+
 def _default_diag(reference: np.ndarray):
     """sqrt(eps) of the mean's dtype (reference ``gp.py:388-393``)."""
     return np.sqrt(np.finfo(np.asarray(reference).dtype).eps)
@@ -215,6 +219,41 @@ class GaussianProcess:
                                       "tinygp_amd.log_probability_and_grad_datasets")
         kernels = list(kernels)
         return fused(kernels, *self._batch_inputs(y, len(kernels), diags, means))
+
+    def predict_batch(self, y, kernels, X_test=None, *, diags=None, means=None, return_var: bool = True,
+                      include_mean: bool = True):
+        """:meth:`predict` of ``y`` under B models that share this GP's coordinates, at one shared set of test points,
+        evaluated together (the reference's ``jax.vmap`` over the function that builds the GP and predicts): the
+        candidates of an acquisition function under every member of an ensemble, restarts compared on held-out points.
+
+        ``kernels``, ``diags`` and ``means`` as in :meth:`log_probability_batch`; ``X_test``: ``None`` for this GP's
+        points.  Returns the (B, M) means, or ``(means, variances)`` with ``return_var``; row b is
+        ``GaussianProcess(kernels[b], X, diag=diags[b], mean=means[b]).predict(y, X_test, return_var=True)`` with the
+        default jitter of :meth:`condition` in the variances, held to the project's posterior bar against that call.
+        With ``include_mean`` the constant ``means[b]`` -- or, with ``means=None``, this GP's mean function at the
+        test points -- is added to row b; (B, N) mean vectors enter the residual only.  Needs a solver with
+        ``predict_batch`` (:class:`tinygp_amd.solvers.DirectSolver`: up to ``TGP_SMALL_MAX_N`` points a workgroup
+        conditions and predicts a whole member in LDS, ``csrc/small.hip``; above it the members are evaluated one by
+        one).  Data sets with points of their own: :func:`tinygp_amd.predict_datasets`."""
+        fused = getattr(self.solver, "predict_batch", None)
+        if fused is None:
+            raise NotImplementedError(f"{type(self.solver).__name__} has no predict_batch: batches of predictions are "
+                                      "evaluated by DirectSolver (the dense path); a kernels.quasisep model predicts "
+                                      "through QuasisepSolver's predict and predict_terms")
+        kernels = list(kernels)
+        nb = len(kernels)
+        resid, noise = self._batch_inputs(y, nb, diags, means)
+        _, mu, var = fused(kernels, resid, X_test, noise, return_var=return_var)
+        if include_mean:
+            if means is None:
+                mu = mu + (self.loc if X_test is None else
+                           _eval_mean(self.mean_function, X_test, _device.num_points(X_test), self.dtype))
+            elif np.ndim(means) == 1:
+                mu = mu + np.asarray(means, dtype=self.dtype)[:, None]
+        mu = np.asarray(mu, dtype=self.dtype)
+        if not return_var:
+            return mu
+        return mu, np.asarray(var + _default_diag(self.mean), dtype=self.dtype)
 
     def _batch_inputs(self, y, nb, diags, means):
         """``(resid, noise)`` of a batch of nb models: the arguments of the solver's batch methods."""

@@ -455,6 +455,79 @@ class DirectSolver(Solver):
         out = (values.astype(self.dtype, copy=False), grads)
         return out + (info,) if return_info else out
 
+    def predict_batch(self, kernels, resid, X_test=None, noise=None, *, return_var: bool = True,
+                      return_info: bool = False):
+        """B models over this solver's coordinates conditioned on their residuals and predicted at ONE set of test
+        points, evaluated together on the device (``tgp_small_predict``, ``csrc/small.hip``: the workgroup that
+        assembles, factors and solves a member in LDS also walks the test points).  ``kernels``, ``resid`` and
+        ``noise`` as in :meth:`log_probability_batch`; ``X_test``: (M,) or (M, D), ``None`` for the solver's own points.
+
+        Returns ``(values (B,), means (B, M), variances (B, M))``: ``K(X_test, X) K^-1 r`` and
+        ``diag(K(X_test, X_test)) - |L^-1 K(X, X_test)|^2`` per member -- what :meth:`conditional_mean` and
+        :meth:`condition_variance` of a solver built with that member's kernel and noise give, without mean function,
+        noise or jitter -- ``variances`` ``None`` without ``return_var`` (the triangular solve is then skipped).  With
+        ``return_info`` the B ``info`` values come fourth.  A failed or non-finite member gives ``-inf`` and NaN
+        predictions.  fp32 inputs are computed in fp64 and returned as fp32.
+
+        The values have the bits of :meth:`log_probability_batch`; the predictions are held to the project's posterior
+        bar against the single calls.  The routing is that of :meth:`log_probability_batch`, all members batched or
+        none: above ``TGP_SMALL_MAX_N`` points, with a noise model that is not
+        :class:`~tinygp_amd.noise.Diagonal` or with a member without a device program, every member is evaluated on a
+        fresh single :class:`DirectSolver`.  ``kernels.quasisep`` members raise ``NotImplementedError``."""
+        from tinygp_amd.solvers import small
+
+        kernels = list(kernels)
+        nb = len(kernels)
+        Xt = self.X if X_test is None else X_test
+        M = _device.num_points(Xt)
+        if nb == 0:
+            empty = np.empty((0, M), dtype=self.dtype)
+            out = (np.empty(0, dtype=self.dtype), empty, empty.copy() if return_var else None)
+            return out + (np.empty(0, dtype=np.int32),) if return_info else out
+        small.reject_quasisep(kernels)
+
+        def rows(a, what):  # (N,) shared or (B, N) one per member -> (B, N)
+            a = np.asarray(a)
+            if a.shape not in ((self.n,), (nb, self.n)):
+                raise ValueError(f"{what} must have shape ({self.n},) or ({nb}, {self.n}); got {a.shape}")
+            return np.broadcast_to(a, (nb, self.n))
+
+        r = rows(resid, "resid")
+        d = None if noise is None else rows(noise, "noise")
+        lowered = [small.lower_member(k, self.X) for k in kernels]
+        values, info = np.empty(nb), np.zeros(nb, dtype=np.int32)
+        mu, var = np.empty((nb, M)), (np.empty((nb, M)) if return_var else None)
+        tests = None
+        if small.batch_route(self.n, d is not None or isinstance(self.noise, Diagonal), lowered):
+            tests = [small.lower_test(k, None, self.X, X_test, low) for k, low in zip(kernels, lowered)]
+            if any(t is None for t in tests):
+                tests = None
+        if tests is not None:
+            members = [(low[0], low[1], self._noise_diag if d is None else d[b], r[b]) for b, low in enumerate(lowered)]
+            pp = small.pack_predict(members, [t[0] for t in tests])
+            values, info, flat, flat_var = small.run_packed_predict(self._ctx, pp, return_var)
+            mu = flat.reshape(nb, M)
+            var = flat_var.reshape(nb, M) if return_var else None
+        else:  # the single calls, member by member: the interface does not change with N
+            for b, kernel in enumerate(kernels):
+                nz = self.noise if d is None else Diagonal(diag=np.asarray(d[b], dtype=self.dtype))
+                single = DirectSolver(kernel, self.X, nz, ctx=self._ctx)
+                try:
+                    alpha, values[b] = single.alpha(np.asarray(r[b], dtype=self.dtype))
+                    info[b] = single.info
+                    mu[b] = single.conditional_mean(kernel, Xt, alpha)
+                    if return_var:
+                        var[b] = single.condition_variance(kernel, X_test)
+                finally:
+                    single.close()
+        bad = (info != 0) | ~np.isfinite(values)
+        values = np.where(bad, -np.inf, values).astype(self.dtype, copy=False)
+        mu = np.where(bad[:, None], np.nan, mu).astype(self.dtype, copy=False)
+        if return_var:
+            var = np.where(bad[:, None], np.nan, var).astype(self.dtype, copy=False)
+        out = (values, mu, var)
+        return out + (info,) if return_info else out
+
     def log_probability_and_grad(self, resid):
         """``(log_probability, grads)`` with ``grads = {"kernel": [...], "noise_diag": (N,),
         "mean": (N,), "transform": ...}``: derivatives with respect to ``kernel.parameters()`` (same order), to

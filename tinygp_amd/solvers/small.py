@@ -1,4 +1,5 @@
-"""Batches of small dense GPs in one launch (``tgp_small_logprob``, ``tgp_small_logprob_grad``, ``csrc/small.hip``): one
+"""Batches of small dense GPs in one launch (``tgp_small_logprob``, ``tgp_small_logprob_grad``, ``tgp_small_predict``,
+``csrc/small.hip``): one
 workgroup owns a whole member -- it assembles ``K + diag(noise)`` in LDS, factors it there, solves and reduces, and for
 the gradient inverts in place and weighs every derivative -- where the single dense path pays a handle, uploads, a
 launch chain and a host join per evaluation.
@@ -8,7 +9,10 @@ noise and residuals into the arrays of the C ABI (:func:`pack_members`), the cho
 the single path (:func:`batched_route`), and :func:`log_probability_datasets`, the entry point for sets of data sets
 with points of their own.  ``DirectSolver.log_probability_batch`` is built on the same pieces.  The gradient's side:
 :func:`run_packed_grad`, the mapping of the device's ``[2 i + q]`` layout onto ``kernel.parameters()``
-(:func:`member_gradient`), :func:`log_probability_and_grad_datasets` and ``DirectSolver.log_probability_and_grad_batch``.
+(:func:`member_gradient`), :func:`log_probability_and_grad_datasets` and ``DirectSolver.log_probability_and_grad_batch``.  The prediction's side:
+:func:`pack_predict` (test points, second programs and output offsets beside the members), :func:`predict_rows` and
+:func:`predict_launch_bytes` (the table rows and the staging bytes the C side makes of them),
+:func:`run_packed_predict`, :func:`predict_datasets` and ``DirectSolver.predict_batch``.
 """
 
 from __future__ import annotations
@@ -21,9 +25,12 @@ from tinygp_amd import _device, _ffi
 
 __all__ = ["MAX_N", "KOP_DTYPE", "Packed", "lower_member", "pack_members", "batched_route", "batch_route", "run_packed",
            "run_packed_grad", "member_gradient", "failed_gradient", "log_probability_datasets",
-           "log_probability_and_grad_datasets"]
+           "log_probability_and_grad_datasets", "PRED_CHUNK", "PackedPredict", "pack_predict", "predict_rows",
+           "predict_launch_bytes", "run_packed_predict", "predict_datasets"]
 
 MAX_N = _ffi.SMALL_MAX_N  # TGP_SMALL_MAX_N: the largest member a workgroup holds in LDS
+PRED_CHUNK = _ffi.SMALL_PRED_CHUNK  # TGP_SMALL_PRED_CHUNK: the test points one workgroup takes
+STAGE_BYTES = 1 << 30  # the staging cap of one launch (SMALL_STAGE_BYTES of small.hip)
 
 # ``tgp_kop`` as a NumPy record: the programs of a batch are one contiguous array of these
 KOP_DTYPE = np.dtype([("op", np.int32), ("metric", np.int32), ("p0", np.float64), ("p1", np.float64)], align=True)
@@ -370,6 +377,259 @@ def log_probability_and_grad_datasets(kernels, Xs, ys, *, diags, means=None, vec
     grads = {"kernel": kgrads, "noise_diag": noise_rows if vectors else None, "mean": mean_rows if vectors else None,
              "transform": tgrads}
     return (values, grads, info) if return_info else (values, grads)
+
+
+# ---- predictions ------------------------------------------------------------------------------------------------------
+class PackedPredict(NamedTuple):
+    """The host arrays of one ``tgp_small_predict`` call beside those of ``tgp_small_logprob``."""
+
+    packed: Packed
+    Xt: np.ndarray             # (test rows, d) float64
+    xt_off: np.ndarray         # (B,) int64, rows into Xt
+    m: np.ndarray              # (B,) int32
+    pred_progs: np.ndarray | None     # (total second ops,) KOP_DTYPE, or None: every member predicts with its own
+    pred_prog_off: np.ndarray | None  # (B + 1,) int32; an empty extent: the member's own program
+    out_off: np.ndarray        # (B,) int64, into the means and variances
+
+
+def pack_predict(members, tests, pred_progs=None, labels=None) -> PackedPredict:
+    """:func:`pack_members` of ``members`` plus their test points: ``tests[b]`` is (m_b, D) float64, m_b = 0 allowed.
+    Test points ``np.array_equal`` to the first member's share its rows of ``Xt`` (one uploaded copy: a shared grid of
+    candidates); ``pred_progs[b]``: ``None`` or the postfix program of k* and k**.  The outputs of member b start at
+    ``out_off[b] = m_0 + .. + m_{b-1}``.  A ``ValueError`` names the member whose test points do not fit."""
+    members = list(members)
+    packed = pack_members(members, labels)
+    labels = [f"member {b}" for b in range(len(members))] if labels is None else list(labels)
+    tests = list(tests)
+    if len(tests) != len(members):
+        raise ValueError(f"tests must hold one entry per member ({len(members)}); got {len(tests)}")
+    xt_off, ms, out_off, Xts = [], [], [], []
+    rows = total = 0
+    T0 = None
+    for b, T in enumerate(tests):
+        T = np.asarray(T, dtype=np.float64)
+        if T.ndim != 2 or T.shape[1] != packed.d:
+            raise ValueError(f"{labels[b]}: its test points must have shape (m, {packed.d}) like its points; got {T.shape}")
+        if b == 0:
+            T0 = T
+        if b > 0 and T.shape == T0.shape and np.array_equal(T, T0):
+            xt_off.append(0)
+        else:
+            xt_off.append(rows)
+            Xts.append(T)
+            rows += T.shape[0]
+        ms.append(T.shape[0])
+        out_off.append(total)
+        total += T.shape[0]
+    pp = ppo = None
+    if pred_progs is not None and any(q is not None for q in pred_progs):
+        pred_progs = list(pred_progs)
+        if len(pred_progs) != len(members):
+            raise ValueError(f"pred_progs must hold one entry per member ({len(members)}); got {len(pred_progs)}")
+        ops, ppo = [], [0]
+        for b, prog in enumerate(pred_progs):
+            if prog is not None:
+                if not 1 <= len(prog) <= 32:
+                    raise ValueError(f"{labels[b]}: a kernel program holds 1 .. 32 operations (got {len(prog)})")
+                ops.extend((int(op), int(metric), float(p0), float(p1)) for op, metric, p0, p1 in prog)
+            ppo.append(len(ops))
+        pp, ppo = np.array(ops, dtype=KOP_DTYPE), np.array(ppo, dtype=np.int32)
+    Xt = np.concatenate(Xts, axis=0) if Xts else np.empty((0, packed.d))
+    return PackedPredict(packed, np.ascontiguousarray(Xt.reshape(-1, packed.d)), np.array(xt_off, dtype=np.int64),
+                         np.array(ms, dtype=np.int32), pp, ppo, np.array(out_off, dtype=np.int64))
+
+
+def predict_rows(m: int, chunk: int = PRED_CHUNK):
+    """The table rows ``tgp_small_predict`` makes of a member with m test points: ``[(first point, points)]``, one per
+    workgroup, each at most ``chunk`` points; every row factors the member again, the first alone writes the value.
+    m = 0 is one row without points."""
+    if m <= 0:
+        return [(0, 0)]
+    return [(at, min(chunk, m - at)) for at in range(0, m, chunk)]
+
+
+def predict_launch_bytes(pp: PackedPredict, var: bool = True) -> int:
+    """The staging bytes of ``pp`` as ONE launch (``pred_launch_bytes`` of small.hip): table rows of 64 bytes, the
+    programs (``KPROG_BYTES`` each) with the second ones behind the members', coordinates, noise, residual, test points,
+    values, info, means and variances.  The C side ends a launch before the member that would take this past
+    ``STAGE_BYTES``."""
+    nb, d = len(pp.packed.n), pp.packed.d
+    rows = sum(len(predict_rows(int(m))) for m in pp.m)
+    second = 0 if pp.pred_prog_off is None else int(np.count_nonzero(np.diff(pp.pred_prog_off)))
+    # coordinates and test points are staged once per (offset, count)
+    x_doubles = sum(n * d for _, n in {(int(o), int(n)) for o, n in zip(pp.packed.x_off, pp.packed.n)})
+    xt_doubles = sum(m * d for _, m in {(int(o), int(m)) for o, m in zip(pp.xt_off, pp.m) if m > 0})
+    vec, outs = int(pp.packed.n.sum()), int(pp.m.sum())
+    return (rows * 64 + (nb + second) * _ffi.KPROG_BYTES + (x_doubles + 2 * vec + xt_doubles) * 8 + nb * 8
+            + -(-nb * 4 // 8) * 8 + outs * (16 if var else 8))
+
+
+def run_packed_predict(ctx, pp: PackedPredict, return_var: bool = True):
+    """One ``tgp_small_predict`` call: ``(values (B,), info (B,) int32, means (sum m,), variances (sum m,) or None)``,
+    float64; member b's predictions sit at ``pp.out_off[b]``.  The variances are ``k** - |L^-1 k*|^2``: no jitter.  A
+    failed member has NaN in its value and predictions."""
+    packed = pp.packed
+    nb, total = len(packed.n), int(pp.m.sum())
+    info, out = np.zeros(nb, dtype=np.int32), np.empty(nb)
+    mean = np.empty(max(total, 1))
+    var = np.empty(max(total, 1)) if return_var else None
+    _ffi.check(_ffi.lib().tgp_small_predict(
+        ctx.handle, nb, _ffi.ptr(packed.progs), packed.prog_off.ctypes.data_as(_ffi._pi32),
+        packed.x_off.ctypes.data_as(_ffi._pi64), packed.n.ctypes.data_as(_ffi._pi32), packed.d, _ffi.ptr(packed.X),
+        packed.X.shape[0], packed.vec_off.ctypes.data_as(_ffi._pi64), _ffi.ptr(packed.noise), _ffi.ptr(packed.resid),
+        _ffi.ptr(pp.Xt) if pp.Xt.shape[0] else None, pp.Xt.shape[0], pp.xt_off.ctypes.data_as(_ffi._pi64),
+        pp.m.ctypes.data_as(_ffi._pi32), None if pp.pred_progs is None else _ffi.ptr(pp.pred_progs),
+        None if pp.pred_prog_off is None else pp.pred_prog_off.ctypes.data_as(_ffi._pi32),
+        pp.out_off.ctypes.data_as(_ffi._pi64), info.ctypes.data_as(_ffi._pi32), out.ctypes.data_as(_ffi._pdbl),
+        mean.ctypes.data_as(_ffi._pdbl), None if var is None else var.ctypes.data_as(_ffi._pdbl)), "tgp_small_predict")
+    return out, info, mean[:total], None if var is None else var[:total]
+
+
+def lower_test(kernel, predict_kernel, X, X_test, lowered):
+    """``(test points (m, D) float64, second program or None)`` of a batched member, or ``None`` when it has to take the
+    single path: the prediction kernel has no device program, or lowers the data points differently from the model
+    kernel (another input transform), or the test points do not lower to the member's dimension."""
+    pk = kernel if predict_kernel is None else predict_kernel
+    try:
+        if predict_kernel is not None:
+            low = lower_member(predict_kernel, X)
+            if low is None or low[1].shape != lowered[1].shape or not np.array_equal(low[1], lowered[1]):
+                return None
+        if X_test is None:
+            return lowered[1], (None if predict_kernel is None else low[0])
+        if _device.is_tree(X_test):
+            return None
+        Xt = pk._lower(X_test)[1]
+        if _device.is_tree(Xt):
+            return None
+        Pt = _device.points(Xt, np.float64)
+    except NotImplementedError:
+        return None
+    if Pt.shape[1] != lowered[1].shape[1]:
+        return None
+    return Pt, (None if predict_kernel is None else low[0])
+
+
+def jitter(dtype):
+    """What ``GaussianProcess.condition`` adds to the diagonal of a conditional covariance by default: sqrt(eps) of the
+    data's dtype (``gp._default_diag``)."""
+    return np.sqrt(np.finfo(np.dtype(dtype)).eps)
+
+
+def predict_datasets(kernels, Xs, ys, X_tests, *, diags, means=None, test_means=None, predict_kernels=None,
+                     return_var: bool = True, include_mean: bool = True, return_info: bool = False, ctx=None):
+    """Condition B dense GPs on their data and predict at test points, each with points, length, noise and test points
+    of its own, in one call (the reference's ``jax.vmap`` over the function that builds the GP and calls ``predict``):
+    the acquisition step of Bayesian optimisation, hundreds of short light curves interpolated after the fit, restarts
+    compared on held-out points.
+
+    Arguments as in :func:`log_probability_datasets`, and ``X_tests[b]``: (m_b,) or (m_b, D), m_b = 0 allowed, or
+    ``None`` for the data set's own points (they are sent as test points: the mean is K alpha).  ``means[b]``: a
+    scalar is added to the predicted mean when ``include_mean``; a vector (n_b,) enters the residual only and needs
+    ``test_means[b]``, a scalar or (m_b,), which is then what ``include_mean`` adds.  ``predict_kernels[b]``: ``None``
+    or the kernel of k* and k** (``predict(kernel=k1)``: the contribution of one term of a sum).
+
+    Returns ``(values (B,) float64, means, variances)``: lists of B arrays (m_b,) in the dtype of that data set's
+    coordinates, ``variances`` ``None`` without ``return_var`` (the triangular solve is then skipped); with
+    ``return_info`` the B ``info`` values come fourth.  A failed or non-finite member gives ``-inf`` and NaN
+    predictions.
+
+    Member b is ``GaussianProcess(kernels[b], Xs[b], diag=diags[b], mean=means[b]).predict(ys[b], X_tests[b],
+    kernel=predict_kernels[b], return_var=True)``, the default jitter of ``condition`` included in the variances, held
+    to the project's posterior bar against that call.  Data sets of up to ``TGP_SMALL_MAX_N`` points that the device
+    can lower run in the batched launches (``tgp_small_predict``: one workgroup per data set and per
+    ``TGP_SMALL_PRED_CHUNK`` test points, fp64; the value has the bits of :func:`log_probability_datasets`, and a
+    prediction's bits depend on its data set and its own test point alone).  Larger ones, any the device cannot lower
+    (``kernels.Custom``, more than 16 dimensions, pytree inputs) and a ``predict_kernels[b]`` under another input
+    transform than the model's are that very call, one by one.  ``kernels.quasisep`` models belong to
+    ``QuasisepSolver``."""
+    members = check_datasets(kernels, Xs, ys, diags, means)
+    nb = len(members)
+
+    def entries(values, what):
+        values = [None] * nb if values is None else list(values)
+        if len(values) != nb:
+            raise ValueError(f"{what} must hold one entry per data set ({nb}); got {len(values)}")
+        return values
+
+    X_tests, test_means = entries(X_tests, "X_tests"), entries(test_means, "test_means")
+    predict_kernels, raw_means = entries(predict_kernels, "predict_kernels"), entries(means, "means")
+    reject_quasisep(m[0] for m in members)
+    reject_quasisep(k for k in predict_kernels if k is not None)
+    values, info = np.empty(nb), np.zeros(nb, dtype=np.int32)
+    out_means, out_vars = [None] * nb, [None] * nb
+    added = [None] * nb  # what include_mean adds to member b's predictions
+    for b, (kernel, X, y, diag, mean) in enumerate(members):
+        m = len(y) if X_tests[b] is None else _device.num_points(X_tests[b])
+        if mean is None or np.ndim(raw_means[b]) == 0:
+            if test_means[b] is not None:
+                raise ValueError(f"test_means[{b}] is given, but means[{b}] of data set {b} is not a vector: a scalar "
+                                 "mean is added to the predictions by itself")
+            added[b] = np.zeros(m) if mean is None else np.full(m, np.asarray(raw_means[b], dtype=np.float64))
+        else:
+            if test_means[b] is None:
+                if include_mean:
+                    raise ValueError(f"means[{b}] of data set {b} is a vector: the mean at its test points must be given "
+                                     f"as test_means[{b}] (a scalar or ({m},)), or include_mean=False")
+                added[b] = np.zeros(m)
+            else:
+                t = np.asarray(test_means[b], dtype=np.float64)
+                if t.shape not in ((), (m,)):
+                    raise ValueError(f"test_means[{b}] must have shape ({m},) or be a scalar for data set {b}; got {t.shape}")
+                added[b] = np.broadcast_to(t, (m,))
+    batched, tests, seconds, where = [], [], [], []
+    for b, (kernel, X, y, diag, mean) in enumerate(members):
+        lowered = lower_member(kernel, X)
+        test = None
+        if batched_route(len(y), lowered) and (not batched or lowered[1].shape[1] == batched[0][1].shape[1]):
+            test = lower_test(kernel, predict_kernels[b], X, X_tests[b], lowered)
+        if test is not None:
+            batched.append((lowered[0], lowered[1], diag, y if mean is None else y - mean))
+            tests.append(test[0])
+            seconds.append(test[1])
+            where.append(b)
+        else:
+            values[b], info[b], out_means[b], out_vars[b] = _single_predict(
+                kernel, X, y, diag, mean, X_tests[b], predict_kernels[b], return_var, ctx)
+    if batched:
+        pp = pack_predict(batched, tests, seconds, labels=[f"data set {b}" for b in where])
+        vals, infos, mu, var = run_packed_predict(_ffi.default_ctx() if ctx is None else ctx, pp, return_var)
+        for k, b in enumerate(where):
+            at, m = int(pp.out_off[k]), int(pp.m[k])
+            values[b], info[b] = vals[k], infos[k]
+            out_means[b] = mu[at:at + m]
+            if return_var:
+                out_vars[b] = var[at:at + m] + jitter(members[b][2].dtype)
+    bad = (info != 0) | ~np.isfinite(values)
+    values[bad] = -np.inf
+    for b in range(nb):
+        dt = members[b][2].dtype
+        mu = np.asarray(out_means[b], dtype=np.float64)
+        mu = mu + added[b] if include_mean else mu
+        out_means[b] = np.full(len(mu), np.nan, dtype=dt) if bad[b] else mu.astype(dt)
+        if return_var:
+            v = np.asarray(out_vars[b], dtype=np.float64)
+            out_vars[b] = np.full(len(v), np.nan, dtype=dt) if bad[b] else v.astype(dt)
+    out = (values, out_means, out_vars if return_var else None)
+    return out + (info,) if return_info else out
+
+
+def _single_predict(kernel, X, y, diag, mean, X_test, predict_kernel, return_var, ctx):
+    """One data set on the single dense path: ``GaussianProcess(kernel, X, diag=diag).predict(y - mean, X_test,
+    kernel=predict_kernel, return_var=True)`` itself -- the mean enters through the residual, the caller adds it to the
+    predictions -- its solver closed behind it: ``(value, info, means, variances or None)``."""
+    from tinygp_amd.gp import GaussianProcess
+    from tinygp_amd.solvers.direct import DirectSolver
+
+    kwargs = {} if ctx is None else {"ctx": ctx}
+    gp = GaussianProcess(kernel, X, diag=diag, solver=DirectSolver, **({} if mean is None else {"mean_value": mean}),
+                         **kwargs)
+    try:
+        value, cond = gp.condition(y, X if X_test is None else X_test, kernel=predict_kernel, include_mean=False)
+        var = np.asarray(cond.variance) if return_var else None
+        return float(value), int(gp.solver.info), np.asarray(cond.loc), var
+    finally:
+        gp.solver.close()
 
 
 def single_gradient(solver, resid, vectors: bool):
