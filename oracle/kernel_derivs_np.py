@@ -15,6 +15,26 @@ each other.  With r the kernel's distance, l its scale:
   Cosine             u = 2 pi r / l, k = cos u                dk/dl = u sin(u) / l
   ExpSineSquared     u = pi r / l, k = exp(-g sin^2 u)        dk/dl = k g 2 sin(u) cos(u) u / l,  dk/dg = -sin^2(u) k
   RationalQuadratic  q = r^2 / (2 a l^2), k = (1 + q)^-a      dk/dl = k / (1 + q) r^2 / l^3,  dk/da = k (q / (1 + q) - ln(1 + q))
+
+The derivative with respect to the LOG of a per-dimension input scale (x_q -> s_q x_q for every point, what
+``transforms.Linear`` / ``Cholesky`` with a vector do) is stated here through dk/dr, not through dk/dl: a stationary
+leaf is a function of its distance r alone, so  dk/dlog s_q = (dk/dr)(dr/dlog s_q)  with, for the scaled difference
+d_q = s_q (x1_q - x2_q),
+
+  L1  r = sum_q |d_q|          dr/dlog s_q = |d_q|
+  L2  r = sqrt(sum_q d_q^2)    dr/dlog s_q = d_q^2 / r   (0 at r = 0: |d_q| <= r, so the quotient is at most r)
+
+and dk/dr from the definitions above (``dleaf_dr``):
+
+  Exp  -k / l       ExpSquared  -k r / l^2       Matern32  -(sqrt(3) / l) a e^-a       Matern52  -(sqrt(5) / l)(a / 3)(1 + a) e^-a
+  Cosine  -(2 pi / l) sin u       ExpSineSquared  -k g sin(2 u) pi / l       RationalQuadratic  -(r / l^2)(1 + q)^(-a - 1)
+
+The dot-product leaf (reference kernels/base.py:212-256: DotProduct is l = 1, sigma = 0; Polynomial raises it to a
+power, which the callers compose by the power rule  d u^P = P u^(P - 1) du [+ u^P ln u dP]):
+
+  u = x1 . x2 / l^2 + sigma^2      du/dl = -2 x1 . x2 / l^3      du/dsigma = 2 sigma      du/dlog s_q = 2 x1_q x2_q / l^2
+                                                                                          (x the scaled coordinates)
+Every function keeps the dtype of its points (the two-point probe of tests/_kernel_derivs.py runs them in long double).
 """
 import numpy as np
 
@@ -67,3 +87,67 @@ def dleaf(kernel, X1, X2, param="scale"):
         assert param == "alpha"
         return k * (q / (1 + q) - np.log1p(q))
     raise TypeError(f"no closed form for {type(kernel).__name__}")
+
+
+def dleaf_dr(kernel, X1, X2):
+    """d k / d r at the leaf's own distance r (L1 or L2), from the definitions; X (n, d)."""
+    l = float(kernel.scale)
+    r = _r(kernel, X1, X2)
+    if isinstance(kernel, o.Exp):
+        return -np.exp(-r / l) / l
+    if isinstance(kernel, o.ExpSquared):
+        return -np.exp(-0.5 * (r / l) ** 2) * r / l**2
+    if isinstance(kernel, o.Matern32):
+        a = np.sqrt(3) * r / l
+        return -(np.sqrt(3) / l) * a * np.exp(-a)
+    if isinstance(kernel, o.Matern52):
+        a = np.sqrt(5) * r / l
+        return -(np.sqrt(5) / l) * (a / 3) * (1 + a) * np.exp(-a)
+    if isinstance(kernel, o.Cosine):
+        return -(2 * np.pi / l) * np.sin(2 * np.pi * r / l)
+    if isinstance(kernel, o.ExpSineSquared):
+        u = np.pi * r / l
+        g = float(kernel.gamma)
+        return -np.exp(-g * np.sin(u) ** 2) * g * np.sin(2 * u) * np.pi / l
+    if isinstance(kernel, o.RationalQuadratic):
+        a = float(kernel.alpha)
+        q = 0.5 * (r / l) ** 2 / a
+        return -(r / l**2) * (1 + q) ** (-a - 1)
+    raise TypeError(f"no closed form for {type(kernel).__name__}")
+
+
+def ddistance_dlogscale(kernel, X1, X2):
+    """d r / d log s_q for every input dimension q, at points that already carry the scales: (d, n1, n2)."""
+    d = np.asarray(X1)[:, None, :] - np.asarray(X2)[None, :, :]
+    if isinstance(kernel.distance, o.L1Distance):
+        return np.moveaxis(np.abs(d), -1, 0)
+    assert isinstance(kernel.distance, o.L2Distance)
+    r = np.sqrt(np.sum(d * d, axis=-1))
+    safe = np.where(r > 0, r, np.ones_like(r))
+    return np.moveaxis(np.where((r > 0)[..., None], d * d / safe[..., None], np.zeros_like(d)), -1, 0)
+
+
+def dleaf_dlogscale(kernel, X1, X2):
+    """d k / d log s_q of a stationary leaf for every input dimension q: (d, n1, n2)."""
+    return dleaf_dr(kernel, X1, X2)[None] * ddistance_dlogscale(kernel, X1, X2)
+
+
+def dot_value(X1, X2, scale=1.0, sigma=0.0):
+    """u = (x1 / l) . (x2 / l) + sigma^2 (DotProduct: l = 1, sigma = 0): (n1, n2)."""
+    X1, X2 = np.asarray(X1), np.asarray(X2)
+    return (X1 / scale) @ (X2 / scale).T + sigma * sigma * np.ones((len(X1), len(X2)), dtype=X1.dtype)
+
+
+def ddot(X1, X2, scale, sigma, param):
+    """d u / d scale or d u / d sigma."""
+    X1, X2 = np.asarray(X1), np.asarray(X2)
+    if param == "scale":
+        return -2 * (X1 @ X2.T) / scale**3
+    assert param == "sigma"
+    return 2 * sigma * np.ones((len(X1), len(X2)), dtype=X1.dtype)
+
+
+def ddot_dlogscale(X1, X2, scale):
+    """d u / d log s_q for every input dimension q, at points that already carry the scales: (d, n1, n2)."""
+    X1, X2 = np.asarray(X1), np.asarray(X2)
+    return 2 * np.moveaxis(X1[:, None, :] * X2[None, :, :], -1, 0) / scale**2

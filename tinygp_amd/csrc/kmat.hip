@@ -320,9 +320,10 @@ struct GeneralEval {
   }
   __device__ __forceinline__ void add_sums(const Pair& p, T r1, T r2, T r3, T gij, double half,
                                            double (&acc)[NSUM]) const {
+    T w1 = 0, w2 = 0;
+    if (which_op < 0) dim_weights<T>(p.dxd, r1, r2, w1, w2);
     const T dk = which_op >= 0 ? eval_kprog_deriv<T, FAM>(kp, which_op, which_param, r1, r2, r3)
-                               : eval_kprog_deriv_dim<T, FAM>(kp, r1, r2, r1 > T(0) ? fabs(p.dxd) / r1 : T(0),
-                                                              r2 > T(0) ? p.dxd * p.dxd / r2 : T(0), r3, p.zz);
+                               : eval_kprog_deriv_dim<T, FAM>(kp, r1, r2, w1, w2, r3, p.zz);
     acc[0] += double(gij) * double(dk) * half;
   }
 };

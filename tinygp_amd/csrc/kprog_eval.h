@@ -133,7 +133,9 @@ __device__ __forceinline__ T leaf_deriv(const KProg& kp, int i, int param, T r1,
                       return param == 0 ? v * p1 * T(2) * sn * cos(u) * u / p0 : -(sn * sn) * v; }
     case TGP_K_RQ: { const T q = T(0.5) * (sq / (p0 * p0)) / p1;  // r^2 / (2 alpha l^2)
                      const T u = T(1) + q, v = pow(u, -p1);
-                     return param == 0 ? v / u * sq / (p0 * p0 * p0) : v * (q / u - log(u)); }
+                     // log1p(q), not log(u): u rounds to 1 below q = eps, and q / u - log(u) = q there where the
+                     // derivative is -q^2 / 2 -- an error of the size of the scale derivative, 2 alpha q / l
+                     return param == 0 ? v / u * sq / (p0 * p0 * p0) : v * (q / u - log1p(q)); }
     default: break;
   }
   if constexpr (FAM == 2) {
@@ -186,12 +188,22 @@ __device__ __forceinline__ T eval_kprog_deriv(const KProg& kp, int which_op, int
   return d0;
 }
 
+// This pair's weights of one input dimension (eval_kprog_deriv_dim's w1 / w2), dx its coordinate difference there:
+// w1 = |dx| / r1 and w2 = dx^2 / r2, zero at coincident points.  Where r2 underflows to zero while r1 > 0 the L2
+// distance of every leaf IS r1 (the zero-safe square root of leaf_value / leaf_deriv), so the weight is the L1 one
+// there, not zero.
+template <typename T>
+__device__ __forceinline__ void dim_weights(T dx, T r1, T r2, T& w1, T& w2) {
+  w1 = r1 > T(0) ? fabs(dx) / r1 : T(0);
+  w2 = r2 > T(0) ? dx * dx / r2 : w1;
+}
+
 // Forward-mode derivative of the whole program with respect to the LOG-SCALE of one input dimension d (x_d -> s x_d
 // for every point): what `transforms.Linear` / `Cholesky` with a per-dimension scale need (reference
 // transforms.py:39-133; JAX differentiates through them for free).  Every stationary leaf depends on the
 // coordinates through dist / p0 resp. sq / p0^2 only, so
 //   d leaf / d log s_d = -p0 * (d leaf / d p0) * w_d,   w_d = dx_d^2 / r2 (L2 metric) or |dx_d| / r1 (L1),
-// (the w_d sum to one: scaling every dimension is scaling 1 / p0).  w1 / w2 are this pair's weights.
+// (the w_d sum to one: scaling every dimension is scaling 1 / p0).  w1 / w2 are this pair's weights (dim_weights).
 // FAM = 2: a DOT leaf contributes 2 (z_id / p0)(z_jd / p0), zz = z_id z_jd, and POW chains.
 template <typename T, int FAM = 0>
 __device__ __forceinline__ T eval_kprog_deriv_dim(const KProg& kp, T r1, T r2, T w1, T w2, T r3 = T(0),

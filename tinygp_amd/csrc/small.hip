@@ -326,10 +326,10 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_grad_kernel(const SmallRo
                                 [&](int t, double dx, double a, double b) {
                                   if (t == -1 - which_op) dxd = dx, zz = a * b;
                                 });
-        const double dk = which_op >= 0
-                              ? eval_kprog_deriv<double, 2>(kp, which_op, which_param, r1, r2, r3)
-                              : eval_kprog_deriv_dim<double, 2>(kp, r1, r2, r1 > 0.0 ? fabs(dxd) / r1 : 0.0,
-                                                                r2 > 0.0 ? dxd * dxd / r2 : 0.0, r3, zz);
+        double w1 = 0.0, w2 = 0.0;
+        if (which_op < 0) dim_weights<double>(dxd, r1, r2, w1, w2);
+        const double dk = which_op >= 0 ? eval_kprog_deriv<double, 2>(kp, which_op, which_param, r1, r2, r3)
+                                        : eval_kprog_deriv_dim<double, 2>(kp, r1, r2, w1, w2, r3, zz);
         acc += gij * dk * (i == j ? 0.5 : 1.0);
       }
     }
