@@ -388,3 +388,65 @@ def test_a_series_beyond_the_cap_is_refused():
     with pytest.raises(ValueError, match=r"series 1 \(n = 6000000\) .*exceeds its cap"):
         s.value_and_grad(_member("celerite4", 0), [t[:40], t], [1.0, 1.0])
     s.close()
+
+
+# -- 12. the set and the batch run one sequence ------------------------------------------------------------------------------
+def test_a_set_on_equal_time_stamps_has_the_bits_of_the_batch():
+    """Three series on the same 1040 time stamps (chunks of 16 steps, 65 chunks, a two-level scan) as a set, where an
+    extent table says where each member lies, and as a batch over one handle, where strides do: the same host arrays
+    give the same bits.  Members have their own model, noise and residual; P = 3."""
+    name, n, nb = "sho_over", 1040, 3
+    assert qs.extent(n) == (16, 65, (65, 2))
+    t, noise, _ = qs.series(n)
+    ks = [_member(name, b) for b in range(nb)]
+    nz = [member_noise(noise, b) for b in range(nb)]
+    rs = [qs.series(n, seed=b + 1)[2] for b in range(nb)]
+    lengths = np.full(nb, n, dtype=np.int64)
+    leaves, smap, h, P, noise_c, resid_c = pack_series(lengths, ks, rs, nz)
+    dleaves, dh, dP, _ = pack_series_tangents(lengths, ks)
+    nl, J, ndir = leaves.shape[1], h.shape[1], dh.shape[1]
+    assert ndir == 3 and noise_c.shape == resid_c.shape == (nb * n,)
+    lib = _ffi.lib()
+
+    def outputs(p, vectors):
+        return (np.empty(nb), np.zeros(nb, dtype=np.int32), np.zeros((nb, p)),
+                np.empty(nb * n) if vectors else None, np.empty(nb * n) if vectors else None)
+
+    def as_set(s, p, vectors):
+        out, info, dout, gn, al = outputs(p, vectors)
+        _ffi.check(lib.tgp_qsep_series_grad(
+            s._handle, _ffi.ptr(leaves), nl, _ffi.ptr(smap), J, _ffi.ptr(h), _ffi.ptr(P), _ffi.ptr(noise_c),
+            _ffi.ptr(resid_c), p, _ffi.ptr(dleaves), _ffi.ptr(dh), _ffi.ptr(dP), _ffi.ptr(info), _ffi.ptr(out),
+            _ffi.ptr(dout), _ffi.ptr(gn), _ffi.ptr(al), None, None), "tgp_qsep_series_grad")
+        return out, info, dout, gn, al
+
+    def as_batch(b, p, vectors):
+        out, info, dout, gn, al = outputs(p, vectors)
+        _ffi.check(lib.tgp_qsep_grad_batch(
+            b._handle, nb, _ffi.ptr(leaves), nl, _ffi.ptr(smap), J, _ffi.ptr(h), _ffi.ptr(P), _ffi.ptr(noise_c), n,
+            _ffi.ptr(resid_c), n, p, _ffi.ptr(dleaves), _ffi.ptr(dh), _ffi.ptr(dP), _ffi.ptr(info), _ffi.ptr(out),
+            _ffi.ptr(dout), _ffi.ptr(gn), _ffi.ptr(al), None, None), "tgp_qsep_grad_batch")
+        return out, info, dout, gn, al
+
+    s = QuasisepSeriesSet([t] * nb, assume_sorted=True)
+    b = QuasisepSolver(ks[0], t, Diagonal(nz[0]), assume_sorted=True)
+    try:
+        set_full, batch_full = as_set(s, ndir, True), as_batch(b, ndir, True)
+        set_value, batch_value = as_set(s, 0, False), as_batch(b, 0, False)
+        set_plain, batch_plain = outputs(0, False)[:2], outputs(0, False)[:2]
+        _ffi.check(lib.tgp_qsep_series_logprob(
+            s._handle, _ffi.ptr(leaves), nl, _ffi.ptr(smap), J, _ffi.ptr(h), _ffi.ptr(P), _ffi.ptr(noise_c),
+            _ffi.ptr(resid_c), _ffi.ptr(set_plain[1]), _ffi.ptr(set_plain[0]), None), "tgp_qsep_series_logprob")
+        _ffi.check(lib.tgp_qsep_logprob_batch(
+            b._handle, nb, _ffi.ptr(leaves), nl, _ffi.ptr(smap), J, _ffi.ptr(h), _ffi.ptr(P), _ffi.ptr(noise_c), n,
+            _ffi.ptr(resid_c), n, _ffi.ptr(batch_plain[1]), _ffi.ptr(batch_plain[0]), None), "tgp_qsep_logprob_batch")
+    finally:
+        s.close()
+        b.close()
+    assert not set_full[1].any() and all(np.all(np.isfinite(a)) for a in set_full)
+    assert len(set(set_full[0])) == nb  # the members differ
+    for what, got, want in zip(("out", "info", "dout", "gnoise", "alpha"), set_full, batch_full):
+        assert got.shape == want.shape and got.dtype == want.dtype and np.array_equal(got, want), what
+    assert set_value[3] is None and set_value[4] is None and batch_value[3] is None and batch_value[4] is None
+    for got in (set_value, batch_value, set_plain, batch_plain):
+        assert np.array_equal(got[0], set_full[0]) and np.array_equal(got[1], set_full[1])

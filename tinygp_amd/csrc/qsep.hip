@@ -1536,7 +1536,7 @@ struct tgp_qsep_series {
   tgp_ctx* ctx = nullptr;
   int64_t nseries = 0;
   std::vector<int64_t> offsets;  // nseries + 1: series b is [offsets[b], offsets[b + 1]) of the concatenated arrays
-  std::vector<QExtent> ext;      // the table's host copy; series_split fills the offsets inside a chain
+  std::vector<QExtent> ext;      // the table's host copy; series_fill sets the offsets inside a chain
   std::vector<int64_t> chain0;   // the split the table was cut for: every chain's first member, then nseries
   std::vector<int64_t> chain_d;  // gradient: every chain's directions per pass
   // what the resident table's chains were cut for: the call (0: none yet, 1: value, 2: value and gradient), the state
@@ -1673,38 +1673,177 @@ int set_model(tgp_qsep* q, const double* leaves, int32_t nleaves, const int32_t*
   return TGP_OK;
 }
 
-// The factor of `members` models (grid y) over the handle's t: qs_fold, the Riccati scan, qs_emit.  Member b: model
-// models[b], its noise noise_stride, its scan work space work_stride, its per-chunk sums of log c red_stride doubles
-// after member b - 1's; c, w and the bad-pivot slots as in qs_emit.  *prefix: the chunks' incoming filtered
-// covariances (member 0's; nchunks x WAVE), valid until `work` is written again.
-int launch_factor(tgp_qsep* q, const QModel* models, int64_t members, const double* noise, int64_t noise_stride,
-                  double* work, int64_t work_stride, double* cbuf, double* wbuf, double* logsum, int64_t red_stride,
-                  int64_t* bad, double** prefix) {
-  hipStream_t st = q->ctx->stream;
-  const int64_t n = q->n, nc = q->nchunks;
-  const dim3 grid(unsigned(blocks_for(nc)), unsigned(members));
-  const UniformExtent ext{n, q->lc, nc, noise_stride, 0, work_stride, red_stride};
-  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, ext, work);
-  TGP_TRY(run_scan<ScanRiccati>(models, st, nc, 1, work, prefix, members, work_stride));
-  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, q->t, noise, ext, *prefix, cbuf, wbuf, logsum, bad);
+// ---- who the members of a launch chain are -------------------------------------------------------------------------------
+// The launch helpers and the chain below are written once over a host-side description of the chain's members, of the
+// same two kinds as the device policies:
+//   UniformMembers   `count` models over the one series of a handle, every array one stride per member apart; the single
+//                    call is such a chain of one member
+//   TableMembers     `count` series of a set, each where the resident extent table says
+// Either kind supplies
+//   t, count          the first member's coordinates (device) and the grid's member extent
+//   chunks()          the grid's x extent: the chain's largest chunk count
+//   ext(), gext(tangent), sums(nd)
+//                     the device policies; `tangent`: the work space is that of a direction pass
+//   scan<S>()         the hierarchical scan over the elements a fold kernel left in `work`, `width` scans per member
+//                     interleaved; *prefix: what the emit kernel takes as its prefix argument, valid until `work` is
+//                     written again (uniform: level 0's prefixes, member 0's; table: `work` itself, where the extent
+//                     policies look for each member's)
+//   set_aside<S>()    the chunk prefixes of that scan (width 1) into slot `which` of every member's keep (0: filtered
+//                     covariances, 1: solve states)
+//   own_rhs()         the same members for a right-hand side the chain made itself: one per member
+//   own_noise(), own_resid(), room(), held(), n_of(b), off_of(b)
+//                     for the chain's buffer: whether every member brings its noise / residual, the totals the buffer
+//                     is carved for and those of the members held, member b's length and where it lies in the
+//                     chain's arrays
+struct Totals {
+  int64_t members, points, chunks, work, twork;  // twork: the tangent scans' work space for a pass of D directions
+};
+
+struct UniformMembers {
+  const double* t;
+  int64_t n, lc, nchunks;
+  int64_t count = 1, cap = 1;  // members held; members the buffer is carved for (the layout depends on the call alone)
+  // member b's noise, right-hand side, primal and tangent scan work space lie one stride after member b - 1's; its
+  // per-chunk sums nchunks and its keep 2 nchunks WAVE doubles, its c, out and z n doubles
+  int64_t noise_stride = 0, y_stride = 0, work_stride = 0, twork_stride = 0;
+
+  int64_t chunks() const { return nchunks; }
+  UniformExtent ext() const { return {n, lc, nchunks, noise_stride, y_stride, work_stride, nchunks}; }
+  UniformGExtent gext(bool tangent) const {
+    return {n, lc, nchunks, noise_stride, y_stride, 2 * nchunks * WAVE, tangent ? twork_stride : work_stride};
+  }
+  // block x: row x of the per-chunk arrays, whatever nd (the layout "extents" states)
+  UniformSums sums(int64_t) const { return {nchunks, nchunks, nchunks, nchunks}; }
+  template <class S>
+  int scan(hipStream_t st, const QModel* models, double* work, int64_t width, bool tangent, double** prefix) const {
+    return run_scan<S>(models, st, nchunks, width, work, prefix, count, tangent ? twork_stride : work_stride);
+  }
+  template <class S>
+  void set_aside(hipStream_t st, const double* prefix, double* keep, int64_t which) const {
+    const int64_t len = nchunks * WAVE;
+    qs_keep_rows<<<dim3(unsigned(ceil_div(len, 256)), unsigned(count)), 256, 0, st>>>(prefix, work_stride,
+                                                                                     keep + which * len, 2 * len, len);
+  }
+  UniformMembers own_rhs() const {
+    UniformMembers m = *this;
+    m.y_stride = n;
+    return m;
+  }
+  bool own_noise() const { return noise_stride != 0; }
+  bool own_resid() const { return y_stride != 0; }
+  Totals totals(int64_t k) const { return {k, k * n, k * nchunks, k * work_stride, k * twork_stride}; }
+  Totals room() const { return totals(cap); }
+  Totals held() const { return totals(count); }
+  int64_t n_of(int64_t) const { return n; }
+  int64_t off_of(int64_t b) const { return b * n; }
+};
+
+struct TableMembers {
+  const double* t;
+  const QExtent* tab;            // the first member's extent (device)
+  const QExtent* mine;           // and its host copy
+  int64_t count = 0;
+  int64_t top[MAXLEV + 1] = {};  // the largest size of every scan level
+  int depth = 1;                 // the deepest member's levels: the level sizes grow with the chunk count
+  Totals tot{};                  // the buffer holds what the chain's own members need and no more
+
+  int64_t chunks() const { return top[0]; }
+  TableExtent ext() const { return {tab}; }
+  TableGExtent gext(bool) const { return {tab}; }
+  TableSums sums(int64_t nd) const { return {tab, nd}; }
+  // the primal work space has room for one scan per member (width 1)
+  template <class S>
+  int scan(hipStream_t st, const QModel* models, double* work, int64_t width, bool tangent, double** prefix) const {
+    *prefix = work;
+    return run_scan_table<S>(models, st, tab, count, top, depth, work, tangent ? width : 0);
+  }
+  template <class S>
+  void set_aside(hipStream_t st, const double* prefix, double* keep, int64_t which) const {
+    qs_keep_table<<<dim3(unsigned(ceil_div(top[0] * WAVE, 256)), unsigned(count)), 256, 0, st>>>(tab, prefix, S::ESZ,
+                                                                                                keep, which);
+  }
+  const TableMembers& own_rhs() const { return *this; }  // y lies where the extent says, whose it is
+  bool own_noise() const { return true; }
+  bool own_resid() const { return true; }
+  Totals room() const { return tot; }
+  Totals held() const { return tot; }
+  int64_t n_of(int64_t b) const { return mine[b].n; }
+  int64_t off_of(int64_t b) const { return mine[b].off; }
+};
+
+// the single call: a uniform chain of one member in the handle's own arrays
+UniformMembers single(const tgp_qsep* q) { return {q->t, q->n, q->lc, q->nchunks}; }
+
+// The factor of the members' models (grid y) over their t: qs_fold, the Riccati scan, qs_emit.  c, w, the per-chunk sums
+// of log c and the bad-pivot slots as in qs_emit.  *prefix: the chunks' incoming filtered covariances (see scan).
+template <class M>
+int launch_factor(const M& m, hipStream_t st, const QModel* models, const double* noise, double* work, double* cbuf,
+                  double* wbuf, double* logsum, int64_t* bad, double** prefix) {
+  const dim3 grid(unsigned(blocks_for(m.chunks())), unsigned(m.count));
+  const auto ext = m.ext();
+  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, m.t, noise, ext, work);
+  TGP_TRY(m.template scan<ScanRiccati>(st, models, work, 1, false, prefix));
+  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, m.t, noise, ext, *prefix, cbuf, wbuf, logsum, bad);
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
 
-// out = op(y) for nrhs columns (N x nrhs, row-major) against the factors c, w of `members` models: qs_aff_fold, the
-// affine scan, qs_aff_emit.  Member b: its y y_stride, its work space work_stride, its per-chunk sums of out^2
-// (sumsq; optional) red_stride doubles after member b - 1's.  *prefix: the chunks' incoming states (member 0's;
-// nchunks x ncg x WAVE), valid until `work` is written again.
-int launch_affine(tgp_qsep* q, int op, const QModel* models, int64_t members, const double* cbuf, const double* wbuf,
-                  int64_t nrhs, const double* y, int64_t y_stride, double* work, int64_t work_stride, double* out,
-                  double* sumsq, int64_t red_stride, double** prefix) {
-  hipStream_t st = q->ctx->stream;
-  const int64_t n = q->n, nc = q->nchunks, ncg = ceil_div(nrhs, 8);
-  const dim3 grid(unsigned(blocks_for(nc * ncg)), unsigned(members));
-  const UniformExtent ext{n, q->lc, nc, 0, y_stride, work_stride, red_stride};
-  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(op, models, q->t, cbuf, wbuf, ext, nrhs, ncg, y, work);
-  TGP_TRY(run_scan<ScanAffine>(models, st, nc, ncg, work, prefix, members, work_stride));
-  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(op, models, q->t, cbuf, wbuf, ext, nrhs, ncg, *prefix, y, out, sumsq);
+// out = op(y) for nrhs columns (N x nrhs, row-major) against the members' factors c, w: qs_aff_fold, the affine scan,
+// qs_aff_emit.  sumsq: the per-chunk sums of out^2 (optional).  *prefix: the chunks' incoming states (nchunks x ncg x
+// WAVE per member; see scan).  Table members take one column.
+template <class M>
+int launch_affine(const M& m, hipStream_t st, int op, const QModel* models, const double* cbuf, const double* wbuf,
+                  int64_t nrhs, const double* y, double* work, double* out, double* sumsq, double** prefix) {
+  const int64_t ncg = ceil_div(nrhs, 8);
+  const dim3 grid(unsigned(blocks_for(m.chunks() * ncg)), unsigned(m.count));
+  const auto ext = m.ext();
+  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(op, models, m.t, cbuf, wbuf, ext, nrhs, ncg, y, work);
+  TGP_TRY(m.template scan<ScanAffine>(st, models, work, ncg, false, prefix));
+  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(op, models, m.t, cbuf, wbuf, ext, nrhs, ncg, *prefix, y, out, sumsq);
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
+// One direction pass for the members x nd directions (grid z x y), after their factors and forward solves: the factor's
+// tangent (qs_gfac_fold, the congruence scan, qs_gfac_emit), the solve's (qs_gsol, the affine scan, qs_gsol) and one
+// qs_finish block per (member, direction), which leaves (sum dc / c, sum z dz) at res[2 (member nd + direction)].
+// dirs: members x nd; keep: per member the chunks' incoming filtered covariances, then solve states; work: the tangent
+// scans' work space; tan: dc | dw (nd n (1 + J) per member) and red: the per-chunk sums (2 nd nchunks per member), laid
+// out as "extents" states.
+template <class M>
+int launch_tangents(const M& m, hipStream_t st, const QModel* models, const QDir* dirs, int64_t nd, const double* noise,
+                    const double* cbuf, const double* wbuf, const double* resid, const double* keep, double* work,
+                    double* tan, double* red, double* res) {
+  const Totals h = m.held();
+  const dim3 grid(unsigned(blocks_for(m.chunks())), unsigned(nd), unsigned(m.count));
+  const auto ext = m.gext(true);
+  double *dcb = tan, *dwb = tan + nd * h.points, *dsum = red, *dsum2 = red + nd * h.chunks;
+  double* prefix = nullptr;
+  qs_gfac_fold<<<grid, WAVE * WPB, 0, st>>>(models, dirs, m.t, noise, ext, keep, work);
+  TGP_TRY(m.template scan<ScanCong>(st, models, work, nd, true, &prefix));
+  qs_gfac_emit<<<grid, WAVE * WPB, 0, st>>>(models, dirs, m.t, noise, ext, keep, prefix, dcb, dwb, dsum);
+  qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, m.t, cbuf, wbuf, dcb, dwb, resid, ext, keep, nullptr, work,
+                                       nullptr);
+  TGP_TRY(m.template scan<ScanAffine>(st, models, work, nd, true, &prefix));
+  qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, m.t, cbuf, wbuf, dcb, dwb, resid, ext, keep, prefix, nullptr,
+                                       dsum2);
+  // block b nd + d: (member b, direction d)'s two sums
+  qs_finish<<<unsigned(m.count * nd), WAVE, 0, st>>>(dsum, dsum2, nullptr, res, nullptr, m.sums(nd), 2);
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
+// The noise gradient 1/2 (alpha^2 - diag K^-1) of the members from their factors and alpha: the variance half of
+// qs_pred_fold from the end, the prediction's scan, qs_invdiag_emit.  In the primal work space.
+template <class M>
+int launch_invdiag(const M& m, hipStream_t st, const QModel* models, const double* cbuf, const double* wbuf,
+                   const double* alpha, double* work, double* out) {
+  const dim3 grid(unsigned(blocks_for(m.chunks())), unsigned(m.count));
+  const auto ext = m.gext(false);
+  qs_pred_fold<<<grid, WAVE * WPB, 0, st>>>(1, 0, 1, models, m.t, cbuf, wbuf, nullptr, ext, work);
+  double* prefix = nullptr;
+  TGP_TRY(m.template scan<ScanPred>(st, models, work, 1, false, &prefix));
+  qs_invdiag_emit<<<grid, WAVE * WPB, 0, st>>>(models, m.t, cbuf, wbuf, alpha, ext, prefix, out);
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
@@ -1717,7 +1856,7 @@ int factor(tgp_qsep* q, const double* noise_host, double* keep = nullptr) {
   TGP_HIP_TRY(hipMemcpyAsync(q->noise, noise_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
   TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanRiccati>(nc, 1)));
   double* prefix = nullptr;
-  TGP_TRY(launch_factor(q, q->model, 1, q->noise, 0, q->work, 0, q->c, q->w, q->red, 0, q->bad, &prefix));
+  TGP_TRY(launch_factor(single(q), st, q->model, q->noise, q->work, q->c, q->w, q->red, q->bad, &prefix));
   if (keep)
     TGP_HIP_TRY(hipMemcpyAsync(keep, prefix, size_t(nc) * WAVE * sizeof(double), hipMemcpyDeviceToDevice, st));
   qs_finish<<<1, WAVE, 0, st>>>(q->red, nullptr, q->bad, q->red + 2 * nc, q->bad + nc, UniformSums{nc, 0, 0, 0}, 0);
@@ -1740,7 +1879,7 @@ int affine(tgp_qsep* q, int op, int64_t nrhs, const double* y, double* out, doub
   const int64_t nc = q->nchunks, ncg = ceil_div(nrhs, 8);
   TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanAffine>(nc, ncg)));
   double* prefix = nullptr;
-  TGP_TRY(launch_affine(q, op, q->model, 1, q->c, q->w, nrhs, y, 0, q->work, 0, out, sumsq ? q->red : nullptr, 0,
+  TGP_TRY(launch_affine(single(q), st, op, q->model, q->c, q->w, nrhs, y, q->work, out, sumsq ? q->red : nullptr,
                         &prefix));
   if (keep)
     TGP_HIP_TRY(hipMemcpyAsync(keep, prefix, size_t(nc * ncg) * WAVE * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -1860,53 +1999,6 @@ void pack_dirs(QDir* out, int64_t d0, int64_t nd, int64_t nl, int64_t J, const d
 // the derivative along one direction from its two sums; one function, so that single and batched calls round alike
 __attribute__((noinline)) double grad_value(const double* sums) { return -0.5 * sums[0] - sums[1]; }
 
-// One direction pass for `members` models x nd directions (grid z x y), after their factors and forward solves: the
-// factor's tangent (qs_gfac_fold, the congruence scan, qs_gfac_emit), the solve's (qs_gsol, the affine scan, qs_gsol)
-// and one qs_finish block per (member, direction), which leaves (sum dc / c, sum z dz) at res[2 (member nd + direction)].
-// dirs: members x nd; keep: per member the chunks' incoming filtered covariances, then solve states (nchunks x WAVE
-// each); tan: dc | dw (members nd n (1 + J)); red: the per-chunk sums (2 members nd nchunks).  Member b: its noise,
-// residual, keep and work space one stride after member b - 1's, its c and w as in qs_emit.
-int launch_tangents(tgp_qsep* q, const QModel* models, int64_t members, const QDir* dirs, int64_t nd,
-                    const double* noise, int64_t noise_stride, const double* cbuf, const double* wbuf,
-                    const double* resid, int64_t resid_stride, const double* keep, int64_t keep_stride, double* work,
-                    int64_t work_stride, double* tan, double* red, double* res) {
-  hipStream_t st = q->ctx->stream;
-  const int64_t n = q->n, nc = q->nchunks, md = members * nd;
-  const dim3 grid(unsigned(blocks_for(nc)), unsigned(nd), unsigned(members));
-  const UniformGExtent ext{n, q->lc, nc, noise_stride, resid_stride, keep_stride, work_stride};
-  double *dcb = tan, *dwb = tan + md * n, *dsum = red, *dsum2 = red + md * nc;
-  double* prefix = nullptr;
-  qs_gfac_fold<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, noise, ext, keep, work);
-  TGP_TRY(run_scan<ScanCong>(models, st, nc, nd, work, &prefix, members, work_stride));
-  qs_gfac_emit<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, noise, ext, keep, prefix, dcb, dwb, dsum);
-  qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, cbuf, wbuf, dcb, dwb, resid, ext, keep, nullptr, work,
-                                       nullptr);
-  TGP_TRY(run_scan<ScanAffine>(models, st, nc, nd, work, &prefix, members, work_stride));
-  qs_gsol<<<grid, WAVE * WPB, 0, st>>>(models, dirs, q->t, cbuf, wbuf, dcb, dwb, resid, ext, keep, prefix, nullptr,
-                                       dsum2);
-  // block b: (member, direction) b's two sums (dsum2 lies md nc doubles after dsum, like its rows)
-  qs_finish<<<unsigned(md), WAVE, 0, st>>>(dsum, dsum2, nullptr, res, nullptr, UniformSums{nc, nc, nc, 0}, 2);
-  TGP_HIP_TRY(hipGetLastError());
-  return TGP_OK;
-}
-
-// The noise gradient 1/2 (alpha^2 - diag K^-1) of `members` models (grid y) from their factors and alpha: the variance
-// half of qs_pred_fold from the end, the prediction's scan, qs_invdiag_emit.  c, alpha and out n, w n J doubles per
-// member, the work space work_stride.
-int launch_invdiag(tgp_qsep* q, const QModel* models, int64_t members, const double* cbuf, const double* wbuf,
-                   const double* alpha, double* work, int64_t work_stride, double* out) {
-  hipStream_t st = q->ctx->stream;
-  const int64_t n = q->n, nc = q->nchunks;
-  const dim3 grid(unsigned(blocks_for(nc)), unsigned(members));
-  const UniformGExtent ext{n, q->lc, nc, 0, 0, 0, work_stride};
-  qs_pred_fold<<<grid, WAVE * WPB, 0, st>>>(1, 0, 1, models, q->t, cbuf, wbuf, nullptr, ext, work);
-  double* prefix = nullptr;
-  TGP_TRY(run_scan<ScanPred>(models, st, nc, 1, work, &prefix, members, work_stride));
-  qs_invdiag_emit<<<grid, WAVE * WPB, 0, st>>>(models, q->t, cbuf, wbuf, alpha, ext, prefix, out);
-  TGP_HIP_TRY(hipGetLastError());
-  return TGP_OK;
-}
-
 // After factor() and the forward solve of the residual (q->io: r, q->io2: z; gkeep: both scans' chunk prefixes):
 // the derivative of the log-likelihood along each of ndir directions, -1/2 sum dc/c - sum z dz.
 int grad_directions(tgp_qsep* q, int32_t ndir, const double* dleaves, const double* dh, const double* dPinf,
@@ -1931,8 +2023,8 @@ int grad_directions(tgp_qsep* q, int32_t ndir, const double* dleaves, const doub
     pack_dirs(hd.data(), d0, nb, nl, J, dleaves, dh, dPinf);
     TGP_HIP_TRY(hipMemcpyAsync(q->gdir, hd.data(), size_t(nb) * sizeof(QDir), hipMemcpyHostToDevice, st));
     double* res = q->gred + 2 * nb * nc;
-    TGP_TRY(launch_tangents(q, q->model, 1, dirs, nb, q->noise, 0, q->c, q->w, q->io, 0, q->gkeep, 0, q->work, 0,
-                            q->gtan, q->gred, res));
+    TGP_TRY(launch_tangents(single(q), st, q->model, dirs, nb, q->noise, q->c, q->w, q->io, q->gkeep, q->work, q->gtan,
+                            q->gred, res));
     // the host vectors are reused by the next batch: wait for this one
     TGP_HIP_TRY(hipMemcpyAsync(sums.data(), res, size_t(2 * nb) * sizeof(double), hipMemcpyDeviceToHost, st));
     TGP_HIP_TRY(hipStreamSynchronize(st));
@@ -1951,7 +2043,7 @@ int grad_vectors(tgp_qsep* q, double* gnoise_host, double* alpha_host) {
   if (gnoise_host) {
     TGP_TRY(grow(&q->gout, &q->gout_elems, n));
     TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanPred>(nc, 1)));
-    TGP_TRY(launch_invdiag(q, q->model, 1, q->c, q->w, q->io, q->work, 0, q->gout));
+    TGP_TRY(launch_invdiag(single(q), st, q->model, q->c, q->w, q->io, q->work, q->gout));
     TGP_HIP_TRY(hipMemcpyAsync(gnoise_host, q->gout, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   TGP_HIP_TRY(hipStreamSynchronize(st));
@@ -1963,27 +2055,181 @@ __attribute__((noinline)) double logprob_value(double zz, double logdet, int64_t
   return -0.5 * zz - 0.5 * logdet - 0.5 * double(n) * kLog2Pi;
 }
 
-// what qs_finish leaves per member of a batch -- (sum log c, sum z^2, first bad pivot), the third an int64 in a double's
-// slot -- as that member's info and value
-void member_value(const double* got, int64_t n, int32_t* info, double* out) {
+// what qs_finish leaves per member of a chain -- (sum log c, sum z^2, first bad pivot), the third an int64 in a double's
+// slot -- as that member's info and value; one function, so that every kind of chain decodes alike
+__attribute__((noinline)) void member_value(const double* got, int64_t n, int32_t* info, double* out) {
   int64_t first_bad;
   memcpy(&first_bad, &got[2], sizeof(first_bad));
   *info = first_bad == INT64_MAX ? 0 : int32_t(first_bad + 1);
   *out = *info ? NAN : logprob_value(got[1], got[0], n);
 }
 
-// ---- batches of models over the one series -----------------------------------------------------------------------------
-// A launch chain evaluates up to BATCH_MAX_MEMBERS models, and as many as keep the handle's batch buffer at or under
-// BATCH_SCRATCH_BYTES.  The buffer, in doubles:
-//   fixed        BATCH_MAX_MEMBERS models (MODEL_DOUBLES each) | the noise, if shared (n) | the residual, if shared (n)
-//   per member   noise, if its own (n) | residual, if its own (n) | c (n) | w (n J) | z (n) | scan work space (W) |
-//                per-chunk sums of log c and of z^2 (2 nchunks) | bad-pivot slots (nchunks) | results (3)
-// with W the larger need of the chain's two scans (the Riccati one's: 4 lane-blocks per element and level).
+// ---- launch chains: many models over one series, or a set of series -----------------------------------------------------
+// A launch chain evaluates up to BATCH_MAX_MEMBERS members in one sequence of launches with one synchronisation, in a
+// buffer of at most BATCH_SCRATCH_BYTES: the value (log-probability) of each, or its value and gradient.  Who the members
+// are is a UniformMembers (models of a batch over the handle's series) or a TableMembers (series of a set); the sequence
+// is written once (chain).  The buffer, in doubles, with the totals over the members it is carved for (Totals: N points,
+// C chunks, W primal and T tangent scan work space, B members), P directions per member and D of them per pass:
+//   fixed          BATCH_MAX_MEMBERS models | value and gradient: BATCH_MAX_MEMBERS x GRAD_MAX_BATCH directions (one pass's)
+//   value          noise | residual (N each; n where a batch shares one) | c (N) | w (N J) | z (N) | scan work space (W) |
+//                  per-chunk sums of log c | of z^2 | bad-pivot slots (C each) | results (3 B)
+//   and gradient   both primal scans' chunk prefixes (2 x 64 C, before the work space) | results (2 P B) | with the
+//                  vectors: alpha | noise gradient (N each) | dc, dw (D N (1 + J)) | tangent scan work space (T) |
+//                  per-chunk tangent sums (2 D C)
+// W holds the largest of the scans that share it (Riccati and affine: 4 lane-blocks per element and level; with the
+// vectors the prediction's: 6), T the congruence scan's (3 per direction).
 constexpr int64_t BATCH_MAX_MEMBERS = 64;
 constexpr int64_t BATCH_SCRATCH_BYTES = int64_t(1) << 30;
 static_assert(sizeof(QModel) % sizeof(double) == 0, "models are laid out in a buffer of doubles");
 constexpr int64_t MODEL_DOUBLES = sizeof(QModel) / sizeof(double);
+constexpr int64_t BATCH_BUDGET = BATCH_SCRATCH_BYTES / int64_t(sizeof(double));
 
+// One call's host arrays from a chain's first member on, and what the call wants
+struct ChainCall {
+  bool grad;      // value and gradient (also with no direction and no vector: the prefixes are kept all the same)
+  int64_t nl, J;
+  int64_t P, D;   // directions per member, per pass
+  const QModel* models;
+  const double *noise, *resid;         // a batch's shared ones are on the device already
+  const double *dleaves, *dh, *dPinf;  // P per member
+  int32_t* info;
+  double *out, *dout, *gnoise, *alpha;  // the last two may be null
+  bool vectors() const { return gnoise || alpha; }
+
+  // the same call from member b0 on, whose points start `at`, whose noise and residual noise_at and resid_at doubles in
+  ChainCall from(int64_t b0, int64_t at, int64_t noise_at, int64_t resid_at) const {
+    auto adv = [](auto* p, int64_t k) { return p ? p + k : p; };
+    ChainCall c = *this;
+    c.models += b0, c.noise += noise_at, c.resid += resid_at;
+    c.dleaves = adv(dleaves, b0 * P * nl * 4), c.dh = adv(dh, b0 * P * J), c.dPinf = adv(dPinf, b0 * P * J * J);
+    c.info += b0, c.out += b0, c.dout = adv(dout, b0 * P);
+    c.gnoise = adv(gnoise, at), c.alpha = adv(alpha, at);
+    return c;
+  }
+};
+
+struct ChainArrays {
+  QModel* models;
+  QDir* dirs;
+  double *noise, *resid, *c, *w, *z, *keep, *work, *logsum, *sumsq;
+  int64_t* bad;
+  double *res, *dres, *alpha, *gnoise, *tan, *twork, *tred;
+};
+
+// the chain's buffer, carved for the members it has room for
+template <class M>
+ChainArrays carve(const M& m, double* buf, const ChainCall& a) {
+  const Totals r = m.room();
+  const int64_t J = a.J, vec = a.vectors() ? r.points : 0;
+  double* p = buf;
+  auto take = [&](int64_t len) {
+    double* got = p;
+    p += len;
+    return got;
+  };
+  ChainArrays A{};
+  A.models = reinterpret_cast<QModel*>(take(BATCH_MAX_MEMBERS * MODEL_DOUBLES));
+  A.dirs = reinterpret_cast<QDir*>(take(a.grad ? BATCH_MAX_MEMBERS * GRAD_MAX_BATCH * DIR_DOUBLES : 0));
+  A.noise = take(m.own_noise() ? r.points : m.n_of(0));
+  A.resid = take(m.own_resid() ? r.points : m.n_of(0));
+  A.c = take(r.points), A.w = take(r.points * J), A.z = take(r.points);
+  A.keep = take(a.grad ? 2 * r.chunks * WAVE : 0);
+  A.work = take(r.work);
+  A.logsum = take(r.chunks), A.sumsq = take(r.chunks), A.bad = reinterpret_cast<int64_t*>(take(r.chunks));
+  A.res = take(3 * r.members), A.dres = take(2 * a.P * r.members);
+  A.alpha = take(vec), A.gnoise = take(vec);
+  A.tan = take(a.D * r.points * (1 + J)), A.twork = take(r.twork), A.tred = take(a.D * 2 * r.chunks);
+  return A;
+}
+
+// The value part of a chain: the members' models, noise and residual go up, then factor, forward solve and one qs_finish
+// block per member, which leaves (sum log c, sum z^2, first bad pivot) at res[3 member], the third an int64 in a double's
+// slot.  Value and gradient: each scan's chunk prefixes are set aside before the next scan writes there.
+template <class M>
+int chain_value(const M& m, hipStream_t st, const ChainArrays& A, const ChainCall& a) {
+  const Totals h = m.held();
+  TGP_HIP_TRY(hipMemcpyAsync(A.models, a.models, size_t(h.members) * sizeof(QModel), hipMemcpyHostToDevice, st));
+  if (m.own_noise())
+    TGP_HIP_TRY(hipMemcpyAsync(A.noise, a.noise, size_t(h.points) * sizeof(double), hipMemcpyHostToDevice, st));
+  if (m.own_resid())
+    TGP_HIP_TRY(hipMemcpyAsync(A.resid, a.resid, size_t(h.points) * sizeof(double), hipMemcpyHostToDevice, st));
+  double* prefix = nullptr;
+  TGP_TRY(launch_factor(m, st, A.models, A.noise, A.work, A.c, A.w, A.logsum, A.bad, &prefix));
+  if (a.grad) m.template set_aside<ScanRiccati>(st, prefix, A.keep, 0);
+  TGP_TRY(launch_affine(m, st, TGP_QS_FWD, A.models, A.c, A.w, 1, A.resid, A.work, A.z, A.sumsq, &prefix));
+  if (a.grad) m.template set_aside<ScanAffine>(st, prefix, A.keep, 1);
+  qs_finish<<<unsigned(h.members), WAVE, 0, st>>>(A.logsum, A.sumsq, A.bad, A.res,
+                                                  reinterpret_cast<int64_t*>(A.res) + 2, m.sums(1), 3);
+  TGP_HIP_TRY(hipGetLastError());
+  return TGP_OK;
+}
+
+// One launch chain over the members m in `buf`: the value part; value and gradient: the direction passes, then, with
+// the vectors, the backward solve and the noise gradient; one stream synchronisation; the results decoded into the
+// call's host arrays.  A failed member gets NaN for everything but its info: its c and w are not a factor of anything,
+// and what ran on them is overwritten.
+template <class M>
+int chain(const M& m, hipStream_t st, double* buf, const ChainCall& a, int32_t* passes) {
+  const ChainArrays A = carve(m, buf, a);
+  const Totals h = m.held();
+  const int64_t nb = h.members, J = a.J, P = a.P, D = a.D;
+  TGP_TRY(chain_value(m, st, A, a));
+  // direction passes: pass k's host directions (member-major) stay alive until the synchronisation below, its results
+  // land after those of the passes before it (2 nb d0 doubles)
+  std::vector<QDir> hd(size_t(nb * P));
+  for (int64_t d0 = 0; d0 < P; d0 += D, ++*passes) {
+    const int64_t nd = std::min<int64_t>(D, P - d0);
+    QDir* h0 = hd.data() + nb * d0;
+    for (int64_t b = 0; b < nb; ++b)
+      pack_dirs(h0 + b * nd, d0, nd, a.nl, J, a.dleaves + b * P * a.nl * 4, a.dh + b * P * J, a.dPinf + b * P * J * J);
+    TGP_HIP_TRY(hipMemcpyAsync(A.dirs, h0, size_t(nb * nd) * sizeof(QDir), hipMemcpyHostToDevice, st));
+    TGP_TRY(launch_tangents(m, st, A.models, A.dirs, nd, A.noise, A.c, A.w, A.resid, A.keep, A.twork, A.tan, A.tred,
+                            A.dres + 2 * nb * d0));
+  }
+  if (a.vectors()) {
+    double* prefix = nullptr;
+    TGP_TRY(launch_affine(m.own_rhs(), st, TGP_QS_BWD, A.models, A.c, A.w, 1, A.z, A.work, A.alpha, nullptr, &prefix));
+    if (a.alpha)
+      TGP_HIP_TRY(hipMemcpyAsync(a.alpha, A.alpha, size_t(h.points) * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (a.gnoise) {
+      TGP_TRY(launch_invdiag(m, st, A.models, A.c, A.w, A.alpha, A.work, A.gnoise));
+      TGP_HIP_TRY(hipMemcpyAsync(a.gnoise, A.gnoise, size_t(h.points) * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+  }
+  std::vector<double> got(size_t(3 * nb)), dgot(size_t(2 * nb * P));
+  TGP_HIP_TRY(hipMemcpyAsync(got.data(), A.res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (P > 0) TGP_HIP_TRY(hipMemcpyAsync(dgot.data(), A.dres, dgot.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t b = 0; b < nb; ++b) {
+    const int64_t n = m.n_of(b), lo = m.off_of(b);
+    member_value(&got[size_t(3 * b)], n, &a.info[b], &a.out[b]);
+    const bool failed = a.info[b] != 0;
+    for (int64_t d0 = 0; d0 < P; d0 += D) {
+      const int64_t nd = std::min<int64_t>(D, P - d0);
+      for (int64_t d = 0; d < nd; ++d)
+        a.dout[b * P + d0 + d] = failed ? NAN : grad_value(&dgot[size_t(2 * (nb * d0 + b * nd + d))]);
+    }
+    for (int64_t i = 0; failed && i < n; ++i) {
+      if (a.gnoise) a.gnoise[lo + i] = NAN;
+      if (a.alpha) a.alpha[lo + i] = NAN;
+    }
+  }
+  return TGP_OK;
+}
+
+// checks `nb` models' host arrays and packs them (leaves: nb x nleaves x 5, hvec: nb x J, Pinf: nb x J x J; one state map)
+int pack_models(std::vector<QModel>* out, int64_t nb, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                int32_t J, const double* hvec, const double* Pinf) {
+  out->assign(size_t(nb), QModel{});
+  for (int64_t b = 0; b < nb; ++b)
+    TGP_TRY(pack_model(&(*out)[size_t(b)], leaves + b * nleaves * 5, nleaves, state_map, J, hvec + b * J,
+                       Pinf + b * J * J));
+  return TGP_OK;
+}
+
+// ---- batches of models over the one series: how many members a chain holds --------------------------------------------
+// Value: as many members as keep the buffer under the cap.  Per member, in doubles: noise, if its own (n) | residual, if
+// its own (n) | c (n) | w (n J) | z (n) | scan work space (W) | per-chunk sums and bad-pivot slots (3 nchunks) | results (3).
 struct BatchLayout {
   int64_t fixed, per_member, work;  // doubles
 };
@@ -1996,170 +2242,12 @@ BatchLayout batch_layout(int64_t n, int64_t nc, int64_t J, bool own_noise, bool 
   return l;
 }
 
-// one launch chain: members [0, nb) of the arrays given; shared noise / residual are on the device already
-int batch_chain(tgp_qsep* q, const BatchLayout& lay, int64_t cap, int64_t nb, const QModel* models_host, int64_t J,
-                const double* noise_host, int64_t noise_stride, const double* resid_host, int64_t resid_stride,
-                int32_t* info, double* out) {
-  hipStream_t st = q->ctx->stream;
-  const int64_t n = q->n, nc = q->nchunks, W = lay.work;
-  // the buffer is carved for `cap` members, whatever this chain holds: the layout depends on the call alone
-  QModel* models = reinterpret_cast<QModel*>(q->bat);
-  double* p = q->bat + BATCH_MAX_MEMBERS * MODEL_DOUBLES;
-  auto take = [&](int64_t shared, int64_t stride) {
-    double* r = p;
-    p += stride ? cap * stride : shared;
-    return r;
-  };
-  double* noise = take(n, noise_stride);
-  double* resid = take(n, resid_stride);
-  double* cbuf = take(0, n);
-  double* wbuf = take(0, n * J);
-  double* z = take(0, n);
-  double* work = take(0, W);
-  double* red = take(0, 2 * nc);
-  int64_t* bad = reinterpret_cast<int64_t*>(take(0, nc));
-  double* res = take(0, 3);
-  TGP_HIP_TRY(hipMemcpyAsync(models, models_host, size_t(nb) * sizeof(QModel), hipMemcpyHostToDevice, st));
-  if (noise_stride)
-    TGP_HIP_TRY(hipMemcpyAsync(noise, noise_host, size_t(nb * n) * sizeof(double), hipMemcpyHostToDevice, st));
-  if (resid_stride)
-    TGP_HIP_TRY(hipMemcpyAsync(resid, resid_host, size_t(nb * n) * sizeof(double), hipMemcpyHostToDevice, st));
-  double* prefix = nullptr;
-  TGP_TRY(launch_factor(q, models, nb, noise, noise_stride, work, W, cbuf, wbuf, red, 2 * nc, bad, &prefix));
-  TGP_TRY(launch_affine(q, TGP_QS_FWD, models, nb, cbuf, wbuf, 1, resid, resid_stride, work, W, z, red + nc, 2 * nc,
-                        &prefix));
-  // per member: (sum log c, sum z^2, first bad pivot), the third an int64 in a double's slot
-  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(red, red + nc, bad, res, reinterpret_cast<int64_t*>(res) + 2,
-                                           UniformSums{nc, nc, 2 * nc, nc}, 3);
-  TGP_HIP_TRY(hipGetLastError());
-  std::vector<double> got(size_t(3 * nb));
-  TGP_HIP_TRY(hipMemcpyAsync(got.data(), res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  TGP_HIP_TRY(hipStreamSynchronize(st));
-  for (int64_t b = 0; b < nb; ++b) member_value(&got[size_t(3 * b)], n, &info[b], &out[b]);
-  return TGP_OK;
-}
-
-// ---- sets of series -------------------------------------------------------------------------------------------------------
-// B series, each on its own coordinates, in launch chains of up to BATCH_MAX_MEMBERS members under the same
-// BATCH_SCRATCH_BYTES.  A chain's buffer holds what its own members need and no more, in doubles:
-//   fixed        BATCH_MAX_MEMBERS models
-//   by array     noise | residual | c | z (sum N_b each) | w (J sum N_b) | scan work space (sum W_b) | per-chunk sums of
-//                log c | of z^2 | bad-pivot slots (sum nchunks_b each) | results (3 per member)
-// with W_b = 256 x (the sizes of MAXLEV scan levels of series b, 1 beyond its own depth): the Riccati scan's 4
-// lane-blocks per element and level, the larger need of the chain's two scans.  Series b therefore needs
-//   need_b = N_b (4 + J) + W_b + 3 nchunks_b + 3.
-// The split (series_split): chains are filled in the order given; a chain ends at BATCH_MAX_MEMBERS members or before
-// the member whose need would take it past the cap.  A function of (N_0 .. N_{B-1}, J) alone.
-constexpr int64_t SERIES_BLOCKS = std::max(ScanRiccati::ESZ + ScanRiccati::PSZ, ScanAffine::ESZ + ScanAffine::PSZ);
-
-int64_t series_work(const QExtent& x) {
-  int64_t s = 0;
-  for (int l = 0; l < MAXLEV; ++l) s += x.lev[l];
-  return s * SERIES_BLOCKS * WAVE;
-}
-
-int64_t series_need(const QExtent& x, int64_t J) { return x.n * (4 + J) + series_work(x) + 3 * x.nchunks + 3; }
-
-// cuts the set into chains for state dimension J and makes the resident table say where each member lies in its chain
-int series_split(tgp_qsep_series* s, int32_t J) {
-  const tgp_qsep_series::Cut cut{1, J, 0, 0};
-  if (s->cut == cut) return TGP_OK;
-  const int64_t budget = BATCH_SCRATCH_BYTES / int64_t(sizeof(double)) - BATCH_MAX_MEMBERS * MODEL_DOUBLES;
-  for (int64_t b = 0; b < s->nseries; ++b)
-    TGP_ARG_CHECK(series_need(s->ext[size_t(b)], J) <= budget,
-                  "series %lld (n = %lld) needs %lld doubles of scratch and exceeds its cap of %lld bytes", (long long)b,
-                  (long long)s->ext[size_t(b)].n, (long long)series_need(s->ext[size_t(b)], J),
-                  (long long)BATCH_SCRATCH_BYTES);
-  s->cut = {};
-  s->chain0.assign(1, 0);
-  int64_t used = 0, count = 0, largest = 0, off = 0, work = 0, chunks = 0;
-  for (int64_t b = 0; b < s->nseries; ++b) {
-    QExtent& x = s->ext[size_t(b)];
-    const int64_t need = series_need(x, J);
-    if (count == BATCH_MAX_MEMBERS || used + need > budget) {
-      s->chain0.push_back(b);
-      used = count = off = work = chunks = 0;
-    }
-    x.off = off, x.work = work, x.chunks = chunks;
-    off += x.n, work += series_work(x), chunks += x.nchunks;
-    used += need, ++count;
-    largest = std::max(largest, used);
-  }
-  s->chain0.push_back(s->nseries);
-  s->buf_need = BATCH_MAX_MEMBERS * MODEL_DOUBLES + largest;
-  hipStream_t st = s->ctx->stream;
-  TGP_HIP_TRY(hipMemcpyAsync(s->tab, s->ext.data(), s->ext.size() * sizeof(QExtent), hipMemcpyHostToDevice, st));
-  TGP_HIP_TRY(hipStreamSynchronize(st));
-  s->cut = cut;
-  return TGP_OK;
-}
-
-// one launch chain: members [b0, b0 + nb) of the set; the host arrays are the concatenated ones
-int series_chain(tgp_qsep_series* s, int64_t b0, int64_t nb, const QModel* models_host, int64_t J,
-                 const double* noise_host, const double* resid_host, int32_t* info, double* out) {
-  hipStream_t st = s->ctx->stream;
-  const QExtent* mine = &s->ext[size_t(b0)];
-  int64_t N = 0, W = 0, C = 0, top[MAXLEV + 1] = {};
-  for (int64_t b = 0; b < nb; ++b) {
-    N += mine[b].n, W += series_work(mine[b]), C += mine[b].nchunks;
-    for (int l = 0; l <= MAXLEV; ++l) top[l] = std::max(top[l], mine[b].lev[l]);
-  }
-  int depth = 1;  // the deepest member's: the level sizes grow with the chunk count
-  while (top[depth - 1] > GROUP) ++depth;
-  QModel* models = reinterpret_cast<QModel*>(s->buf);
-  double* p = s->buf + BATCH_MAX_MEMBERS * MODEL_DOUBLES;
-  auto take = [&](int64_t len) {
-    double* r = p;
-    p += len;
-    return r;
-  };
-  double* noise = take(N);
-  double* resid = take(N);
-  double* cbuf = take(N);
-  double* wbuf = take(N * J);
-  double* z = take(N);
-  double* work = take(W);
-  double* logsum = take(C);
-  double* sumsq = take(C);
-  int64_t* bad = reinterpret_cast<int64_t*>(take(C));
-  double* res = take(3 * nb);
-  const int64_t at = s->offsets[size_t(b0)];
-  const double* t = s->t + at;
-  const QExtent* tab = s->tab + b0;
-  const TableExtent ext{tab};
-  TGP_HIP_TRY(hipMemcpyAsync(models, models_host, size_t(nb) * sizeof(QModel), hipMemcpyHostToDevice, st));
-  TGP_HIP_TRY(hipMemcpyAsync(noise, noise_host + at, size_t(N) * sizeof(double), hipMemcpyHostToDevice, st));
-  TGP_HIP_TRY(hipMemcpyAsync(resid, resid_host + at, size_t(N) * sizeof(double), hipMemcpyHostToDevice, st));
-  const dim3 grid(unsigned(blocks_for(top[0])), unsigned(nb));
-  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, t, noise, ext, work);
-  TGP_TRY(run_scan_table<ScanRiccati>(models, st, tab, nb, top, depth, work));
-  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, t, noise, ext, work, cbuf, wbuf, logsum, bad);
-  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, t, cbuf, wbuf, ext, 1, 1, resid, work);
-  TGP_TRY(run_scan_table<ScanAffine>(models, st, tab, nb, top, depth, work));
-  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, t, cbuf, wbuf, ext, 1, 1, work, resid, z, sumsq);
-  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(logsum, sumsq, bad, res, reinterpret_cast<int64_t*>(res) + 2, TableSums{tab, 1},
-                                           3);
-  TGP_HIP_TRY(hipGetLastError());
-  std::vector<double> got(size_t(3 * nb));
-  TGP_HIP_TRY(hipMemcpyAsync(got.data(), res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  TGP_HIP_TRY(hipStreamSynchronize(st));
-  for (int64_t b = 0; b < nb; ++b) member_value(&got[size_t(3 * b)], mine[b].n, &info[b], &out[b]);
-  return TGP_OK;
-}
-
-// ---- batches of gradients ---------------------------------------------------------------------------------------------
-// Value and gradient of up to BATCH_MAX_MEMBERS models in one launch chain, in the same batch buffer under the same
-// cap.  With P directions per member, D of them per pass, S the sum of the scan's level sizes, in doubles:
-//   fixed                 BATCH_MAX_MEMBERS models | BATCH_MAX_MEMBERS x GRAD_MAX_BATCH directions (one pass's) |
-//                         the noise, if shared (n) | the residual, if shared (n)
-//   per member            noise, if its own (n) | residual, if its own (n) | c (n) | w (n J) | z (n) | both primal scans'
-//                         chunk prefixes (2 x 64 nchunks) | scan work space (256 S; 384 S with the vectors: the
-//                         prediction scan's) | per-chunk sums of log c and z^2 (2 nchunks) | bad-pivot slots (nchunks) |
-//                         results (3 + 2 P) | with the vectors: alpha (n) | noise gradient (n)
-//   per member and direction of a pass
-//                         dc, dw (n (1 + J)) | scan work space (192 S) | per-chunk sums (2 nchunks)
-// The split (grad_split): as many members as fit with one direction each, then as many directions per pass as the rest
-// holds.  A function of (n, J, P, B, own or shared noise and residual, vectors or not) alone.
+// Value and gradient: with P directions per member and S the sum of the scan's level sizes, per member the above and
+// both primal scans' chunk prefixes (2 x 64 nchunks) | results (2 P) | with the vectors: alpha (n) | noise gradient (n),
+// the work space 384 S instead of 256 S; per member and direction of a pass dc, dw (n (1 + J)) | scan work space (192 S) |
+// per-chunk sums (2 nchunks).  The split (grad_split): as many members as fit with one direction each, then as many
+// directions per pass as the rest holds.  A function of (n, J, P, B, own or shared noise and residual, vectors or not)
+// alone.
 struct GradLayout {
   int64_t fixed, per_member, per_dir, work, twork;  // doubles; twork: the tangent scans' work space per direction
   int64_t members, dirs;                            // per chain, per pass; members == 0: one member does not fit
@@ -2176,7 +2264,7 @@ GradLayout grad_split(int64_t n, int64_t nc, int64_t J, int64_t P, int64_t B, bo
   l.per_member = (own_noise ? n : 0) + (own_resid ? n : 0) + n * (2 + J) + 2 * nc * WAVE + l.work + 3 * nc + 3 + 2 * P +
                  (vectors ? 2 * n : 0);
   l.per_dir = n * (1 + J) + l.twork + 2 * nc;
-  const int64_t budget = BATCH_SCRATCH_BYTES / int64_t(sizeof(double)) - l.fixed;
+  const int64_t budget = BATCH_BUDGET - l.fixed;
   const int64_t one = l.per_member + (P > 0 ? l.per_dir : 0);
   l.members = budget < one ? 0 : std::min<int64_t>({B, BATCH_MAX_MEMBERS, budget / one});
   l.dirs = 0;
@@ -2185,147 +2273,67 @@ GradLayout grad_split(int64_t n, int64_t nc, int64_t J, int64_t P, int64_t B, bo
   return l;
 }
 
-struct GradBatchArgs {
-  int64_t nl, J, ndir;
-  const double *noise, *resid;  // host; this chain's first member's when per member
-  int64_t noise_stride, resid_stride;
-  const double *dleaves, *dh, *dPinf;  // host, this chain's first member's
-  int32_t* info;
-  double *out, *dout, *gnoise, *alpha;  // host, this chain's first member's; the last two may be null
-};
-
-// one launch chain: members [0, nb) of the arrays given; shared noise / residual are on the device already.  One stream
-// synchronisation, at the end.
-int grad_batch_chain(tgp_qsep* q, const GradLayout& lay, int64_t nb, const QModel* models_host, const GradBatchArgs& a,
-                     int32_t* passes) {
+// The chains of one call on a batch: nb models in chains of m.cap members, in a buffer of `need` doubles that is carved
+// once, for m.cap members, so that a shared noise or residual goes up once and stays where every chain looks for it.
+int batch_chains(tgp_qsep* q, UniformMembers m, int64_t nb, int64_t need, const ChainCall& a, int32_t* nchains,
+                 int32_t* npasses) {
   hipStream_t st = q->ctx->stream;
-  const int64_t n = q->n, nc = q->nchunks, J = a.J, P = a.ndir, cap = lay.members, D = lay.dirs;
-  const int64_t W = lay.work, TW = D * lay.twork, KS = 2 * nc * WAVE;
-  const bool vectors = a.gnoise || a.alpha;
-  // the buffer is carved for `cap` members and D directions, whatever this chain holds
-  QModel* models = reinterpret_cast<QModel*>(q->bat);
-  double* p = q->bat + BATCH_MAX_MEMBERS * MODEL_DOUBLES;
-  QDir* dirs = reinterpret_cast<QDir*>(p);
-  p += BATCH_MAX_MEMBERS * GRAD_MAX_BATCH * DIR_DOUBLES;
-  auto take = [&](int64_t shared, int64_t stride) {
-    double* r = p;
-    p += stride ? cap * stride : shared;
-    return r;
-  };
-  double* noise = take(n, a.noise_stride);
-  double* resid = take(n, a.resid_stride);
-  double* cbuf = take(0, n);
-  double* wbuf = take(0, n * J);
-  double* z = take(0, n);
-  double* keep = take(0, KS);
-  double* work = take(0, W);
-  double* red = take(0, 2 * nc);
-  int64_t* bad = reinterpret_cast<int64_t*>(take(0, nc));
-  double* res = take(0, 3);
-  double* dres = take(0, 2 * P);
-  double* alpha = take(0, vectors ? n : 0);
-  double* gnoise = take(0, vectors ? n : 0);
-  double* tan = take(0, D * n * (1 + J));
-  double* twork = take(0, TW);
-  double* tred = take(0, D * 2 * nc);
-  TGP_HIP_TRY(hipMemcpyAsync(models, models_host, size_t(nb) * sizeof(QModel), hipMemcpyHostToDevice, st));
-  if (a.noise_stride)
-    TGP_HIP_TRY(hipMemcpyAsync(noise, a.noise, size_t(nb * n) * sizeof(double), hipMemcpyHostToDevice, st));
-  if (a.resid_stride)
-    TGP_HIP_TRY(hipMemcpyAsync(resid, a.resid, size_t(nb * n) * sizeof(double), hipMemcpyHostToDevice, st));
-  // the primal part, each scan's chunk prefixes set aside
-  const dim3 kgrid(unsigned(ceil_div(nc * WAVE, 256)), unsigned(nb));
-  double* prefix = nullptr;
-  TGP_TRY(launch_factor(q, models, nb, noise, a.noise_stride, work, W, cbuf, wbuf, red, 2 * nc, bad, &prefix));
-  qs_keep_rows<<<kgrid, 256, 0, st>>>(prefix, W, keep, KS, nc * WAVE);
-  TGP_TRY(launch_affine(q, TGP_QS_FWD, models, nb, cbuf, wbuf, 1, resid, a.resid_stride, work, W, z, red + nc, 2 * nc,
-                        &prefix));
-  qs_keep_rows<<<kgrid, 256, 0, st>>>(prefix, W, keep + nc * WAVE, KS, nc * WAVE);
-  // per member: (sum log c, sum z^2, first bad pivot), the third an int64 in a double's slot
-  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(red, red + nc, bad, res, reinterpret_cast<int64_t*>(res) + 2,
-                                           UniformSums{nc, nc, 2 * nc, nc}, 3);
-  TGP_HIP_TRY(hipGetLastError());
-  // direction passes: pass k's host directions (member-major) stay alive until the synchronisation below, its results
-  // land after those of the passes before it (2 nb d0 doubles)
-  std::vector<QDir> hd(size_t(nb * P));
-  for (int64_t d0 = 0; d0 < P; d0 += D, ++*passes) {
-    const int64_t nd = std::min<int64_t>(D, P - d0);
-    QDir* h = hd.data() + nb * d0;
-    for (int64_t b = 0; b < nb; ++b)
-      pack_dirs(h + b * nd, d0, nd, a.nl, J, a.dleaves + b * P * a.nl * 4, a.dh + b * P * J, a.dPinf + b * P * J * J);
-    TGP_HIP_TRY(hipMemcpyAsync(dirs, h, size_t(nb * nd) * sizeof(QDir), hipMemcpyHostToDevice, st));
-    TGP_TRY(launch_tangents(q, models, nb, dirs, nd, noise, a.noise_stride, cbuf, wbuf, resid, a.resid_stride, keep, KS,
-                            twork, TW, tan, tred, dres + 2 * nb * d0));
+  const int64_t n = q->n;
+  TGP_TRY(grow(&q->bat, &q->bat_elems, need));
+  const ChainArrays A = carve(m, q->bat, a);
+  if (!m.own_noise())
+    TGP_HIP_TRY(hipMemcpyAsync(A.noise, a.noise, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+  if (!m.own_resid())
+    TGP_HIP_TRY(hipMemcpyAsync(A.resid, a.resid, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+  int32_t chains = 0, passes = 0;
+  for (int64_t b0 = 0; b0 < nb; b0 += m.cap, ++chains) {
+    m.count = std::min<int64_t>(m.cap, nb - b0);
+    TGP_TRY(chain(m, st, q->bat, a.from(b0, b0 * n, b0 * m.noise_stride, b0 * m.y_stride), &passes));
   }
-  if (vectors) {
-    TGP_TRY(launch_affine(q, TGP_QS_BWD, models, nb, cbuf, wbuf, 1, z, n, work, W, alpha, nullptr, 0, &prefix));
-    if (a.alpha)
-      TGP_HIP_TRY(hipMemcpyAsync(a.alpha, alpha, size_t(nb * n) * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (a.gnoise) {
-      TGP_TRY(launch_invdiag(q, models, nb, cbuf, wbuf, alpha, work, W, gnoise));
-      TGP_HIP_TRY(hipMemcpyAsync(a.gnoise, gnoise, size_t(nb * n) * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-  }
-  std::vector<double> got(size_t(3 * nb)), dgot(size_t(2 * nb * P));
-  TGP_HIP_TRY(hipMemcpyAsync(got.data(), res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (P > 0) TGP_HIP_TRY(hipMemcpyAsync(dgot.data(), dres, dgot.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  TGP_HIP_TRY(hipStreamSynchronize(st));
-  for (int64_t b = 0; b < nb; ++b) {
-    int64_t first_bad;
-    memcpy(&first_bad, &got[size_t(3 * b + 2)], sizeof(first_bad));
-    a.info[b] = first_bad == INT64_MAX ? 0 : int32_t(first_bad + 1);
-    const bool failed = a.info[b] != 0;  // c and w are not a factor of anything: what ran on them is overwritten
-    a.out[b] = failed ? NAN : logprob_value(got[size_t(3 * b + 1)], got[size_t(3 * b)], n);
-    for (int64_t d0 = 0; d0 < P; d0 += D) {
-      const int64_t nd = std::min<int64_t>(D, P - d0);
-      for (int64_t d = 0; d < nd; ++d)
-        a.dout[b * P + d0 + d] = failed ? NAN : grad_value(&dgot[size_t(2 * (nb * d0 + b * nd + d))]);
-    }
-    for (int64_t i = 0; failed && i < n; ++i) {
-      if (a.gnoise) a.gnoise[b * n + i] = NAN;
-      if (a.alpha) a.alpha[b * n + i] = NAN;
-    }
-  }
+  if (nchains) *nchains = chains;
+  if (npasses) *npasses = passes;
   return TGP_OK;
 }
 
-// ---- sets of series: value and gradient --------------------------------------------------------------------------------
-// The set's chains with the gradient's arrays, every array the sum of what the chain's own members need.  With P
-// directions per member, d of them per pass, S4_b the sizes of series b's MAXLEV table levels summed, in doubles:
-//   fixed        BATCH_MAX_MEMBERS models | BATCH_MAX_MEMBERS x GRAD_MAX_BATCH directions (one pass's)
-//   member_b     noise | residual | c | z (N_b each) | w (N_b J) | both primal scans' chunk prefixes (2 x 64 nchunks_b) |
-//                scan work space (256 S4_b; 384 S4_b with the vectors: the prediction scan's) | per-chunk sums of log c |
-//                of z^2 | bad-pivot slots (nchunks_b each) | results (3 + 2 P) | with the vectors: alpha | noise gradient
-//                (N_b each)
-//   dir_b        per direction of a pass: dc, dw (N_b (1 + J)) | scan work space (192 S4_b) | per-chunk sums (2 nchunks_b)
-// The split (series_grad_split): chains are filled in the order given; a chain ends at BATCH_MAX_MEMBERS members or
-// before the member that would take sum (member_b + [P > 0] dir_b) past the cap less the fixed part.  Per chain,
-// d = min(P, GRAD_MAX_BATCH, (cap - fixed - sum member_b) / sum dir_b).  A function of (N_0 .. N_{B-1}, J, P, vectors
+// ---- sets of series: which members a chain holds -------------------------------------------------------------------------
+// Chains are filled in the order given (series_fill); a chain ends at BATCH_MAX_MEMBERS members or before the member
+// whose need would take it past the cap less the fixed part.  With S4_b the sizes of series b's MAXLEV table levels
+// summed (1 beyond its own depth), series b needs, in doubles,
+//   value          need_b = N_b (4 + J) + 256 S4_b + 3 nchunks_b + 3
+//   and gradient   member_b = need_b + 2 x 64 nchunks_b + 2 P, with the vectors + 2 N_b and 384 S4_b for 256 S4_b
+//                  dir_b    = N_b (1 + J) + 192 S4_b + 2 nchunks_b per direction of a pass
+// and value and gradient count sum (member_b + [P > 0] dir_b) against the cap; per chain,
+// D = min(P, GRAD_MAX_BATCH, (cap - fixed - sum member_b) / sum dir_b).  A function of (N_0 .. N_{B-1}, J, P, vectors
 // wanted or not) alone.
+constexpr int64_t SERIES_BLOCKS = std::max(ScanRiccati::ESZ + ScanRiccati::PSZ, ScanAffine::ESZ + ScanAffine::PSZ);
+
 int64_t series_levels(const QExtent& x) {
   int64_t s = 0;
   for (int l = 0; l < MAXLEV; ++l) s += x.lev[l];
   return s;
 }
-int64_t series_grad_work(const QExtent& x, bool vectors) {
+int64_t series_work(const QExtent& x, bool vectors) {
   const int64_t blocks = vectors ? std::max<int64_t>(SERIES_BLOCKS, ScanPred::ESZ + ScanPred::PSZ) : SERIES_BLOCKS;
   return series_levels(x) * blocks * WAVE;
 }
-int64_t series_grad_twork(const QExtent& x) { return series_levels(x) * (ScanCong::ESZ + ScanCong::PSZ) * WAVE; }
+int64_t series_twork(const QExtent& x) { return series_levels(x) * (ScanCong::ESZ + ScanCong::PSZ) * WAVE; }
+
+int64_t series_need(const QExtent& x, int64_t J) { return x.n * (4 + J) + series_work(x, false) + 3 * x.nchunks + 3; }
 int64_t series_grad_member(const QExtent& x, int64_t J, int64_t P, bool vectors) {
-  return x.n * (4 + J) + 2 * x.nchunks * WAVE + series_grad_work(x, vectors) + 3 * x.nchunks + 3 + 2 * P +
+  return x.n * (4 + J) + 2 * x.nchunks * WAVE + series_work(x, vectors) + 3 * x.nchunks + 3 + 2 * P +
          (vectors ? 2 * x.n : 0);
 }
-int64_t series_grad_dir(const QExtent& x, int64_t J) { return x.n * (1 + J) + series_grad_twork(x) + 2 * x.nchunks; }
+int64_t series_grad_dir(const QExtent& x, int64_t J) { return x.n * (1 + J) + series_twork(x) + 2 * x.nchunks; }
 
 constexpr int64_t SERIES_GRAD_FIXED = BATCH_MAX_MEMBERS * (MODEL_DOUBLES + GRAD_MAX_BATCH * DIR_DOUBLES);
 
-// cuts the set into chains for (J, P, vectors) and makes the resident table say where each member lies in its chain
-int series_grad_split(tgp_qsep_series* s, int32_t J, int32_t P, bool vectors) {
-  const tgp_qsep_series::Cut cut{2, J, P, int32_t(vectors)};
+// Cuts the set into chains for `cut` and makes the resident table say where each member lies in its chain.  member(x),
+// dir(x): what series x needs by itself and per direction of a pass; fixed: the fixed part of the buffer.
+template <class Member, class Dir>
+int series_fill(tgp_qsep_series* s, const tgp_qsep_series::Cut& cut, int64_t fixed, Member member, Dir dir) {
   if (s->cut == cut) return TGP_OK;
-  const int64_t budget = BATCH_SCRATCH_BYTES / int64_t(sizeof(double)) - SERIES_GRAD_FIXED;
-  auto one = [&](const QExtent& x) { return series_grad_member(x, J, P, vectors) + (P > 0 ? series_grad_dir(x, J) : 0); };
+  const int64_t budget = BATCH_BUDGET - fixed, P = cut.P;
+  auto one = [&](const QExtent& x) { return member(x) + (P > 0 ? dir(x) : 0); };
   for (int64_t b = 0; b < s->nseries; ++b)
     TGP_ARG_CHECK(one(s->ext[size_t(b)]) <= budget,
                   "series %lld (n = %lld) needs %lld doubles of scratch and exceeds its cap of %lld bytes", (long long)b,
@@ -2333,27 +2341,27 @@ int series_grad_split(tgp_qsep_series* s, int32_t J, int32_t P, bool vectors) {
   s->cut = {};
   s->chain0.assign(1, 0);
   s->chain_d.clear();
-  int64_t used = 0, count = 0, largest = 0, mem = 0, dir = 0, off = 0, work = 0, chunks = 0, twork = 0;
+  int64_t used = 0, count = 0, largest = 0, mem = 0, dsum = 0, off = 0, work = 0, chunks = 0, twork = 0;
   auto close = [&]() {  // the chain that ends here: its directions per pass and its need
-    const int64_t d = P > 0 ? std::min<int64_t>({int64_t(P), GRAD_MAX_BATCH, (budget - mem) / dir}) : 0;
+    const int64_t d = P > 0 ? std::min<int64_t>({P, GRAD_MAX_BATCH, (budget - mem) / dsum}) : 0;
     s->chain_d.push_back(d);
-    largest = std::max(largest, mem + d * dir);
+    largest = std::max(largest, mem + d * dsum);
   };
   for (int64_t b = 0; b < s->nseries; ++b) {
     QExtent& x = s->ext[size_t(b)];
     if (count == BATCH_MAX_MEMBERS || used + one(x) > budget) {
       close();
       s->chain0.push_back(b);
-      used = count = mem = dir = off = work = chunks = twork = 0;
+      used = count = mem = dsum = off = work = chunks = twork = 0;
     }
     x.off = off, x.work = work, x.chunks = chunks, x.keep = 2 * chunks * WAVE, x.twork = twork;
-    off += x.n, work += series_grad_work(x, vectors), chunks += x.nchunks, twork += series_grad_twork(x);
-    mem += series_grad_member(x, J, P, vectors), dir += series_grad_dir(x, J);
+    off += x.n, work += series_work(x, cut.vectors != 0), chunks += x.nchunks, twork += series_twork(x);
+    mem += member(x), dsum += dir(x);
     used += one(x), ++count;
   }
   close();
   s->chain0.push_back(s->nseries);
-  s->buf_need = SERIES_GRAD_FIXED + largest;
+  s->buf_need = fixed + largest;
   hipStream_t st = s->ctx->stream;
   TGP_HIP_TRY(hipMemcpyAsync(s->tab, s->ext.data(), s->ext.size() * sizeof(QExtent), hipMemcpyHostToDevice, st));
   TGP_HIP_TRY(hipStreamSynchronize(st));
@@ -2361,133 +2369,44 @@ int series_grad_split(tgp_qsep_series* s, int32_t J, int32_t P, bool vectors) {
   return TGP_OK;
 }
 
-struct SeriesGradArgs {
-  int64_t nl, J, ndir;
-  const double *noise, *resid;         // host, concatenated over the whole set
-  const double *dleaves, *dh, *dPinf;  // host, the set's first member's
-  int32_t* info;
-  double *out, *dout, *gnoise, *alpha;  // host, the set's first member's; the last two may be null
-};
+int series_split(tgp_qsep_series* s, int32_t J) {
+  return series_fill(s, {1, J, 0, 0}, BATCH_MAX_MEMBERS * MODEL_DOUBLES,
+                     [&](const QExtent& x) { return series_need(x, J); }, [](const QExtent&) { return int64_t(0); });
+}
 
-// one launch chain: members [b0, b0 + nb) of the set with D directions per pass.  One stream synchronisation, at the end.
-int series_grad_chain(tgp_qsep_series* s, int64_t b0, int64_t nb, int64_t D, const QModel* models_host,
-                      const SeriesGradArgs& a, int32_t* passes) {
-  hipStream_t st = s->ctx->stream;
-  const QExtent* mine = &s->ext[size_t(b0)];
-  const int64_t J = a.J, P = a.ndir;
-  const bool vectors = a.gnoise || a.alpha;
-  int64_t N = 0, W = 0, TW = 0, C = 0, top[MAXLEV + 1] = {};
+int series_grad_split(tgp_qsep_series* s, int32_t J, int32_t P, bool vectors) {
+  return series_fill(s, {2, J, P, int32_t(vectors)}, SERIES_GRAD_FIXED,
+                     [&](const QExtent& x) { return series_grad_member(x, J, P, vectors); },
+                     [&](const QExtent& x) { return series_grad_dir(x, J); });
+}
+
+// members [b0, b0 + nb) of the set as the chain the resident table was cut for, with D directions per pass
+TableMembers table_members(const tgp_qsep_series* s, int64_t b0, int64_t nb, int64_t D) {
+  TableMembers m{s->t + s->offsets[size_t(b0)], s->tab + b0, &s->ext[size_t(b0)], nb};
+  m.tot.members = nb;
   for (int64_t b = 0; b < nb; ++b) {
-    N += mine[b].n, W += series_grad_work(mine[b], vectors), TW += series_grad_twork(mine[b]), C += mine[b].nchunks;
-    for (int l = 0; l <= MAXLEV; ++l) top[l] = std::max(top[l], mine[b].lev[l]);
+    const QExtent& x = m.mine[b];
+    m.tot.points += x.n, m.tot.chunks += x.nchunks;
+    m.tot.work += series_work(x, s->cut.vectors != 0), m.tot.twork += D * series_twork(x);
+    for (int l = 0; l <= MAXLEV; ++l) m.top[l] = std::max(m.top[l], x.lev[l]);
   }
-  int depth = 1;  // the deepest member's: the level sizes grow with the chunk count
-  while (top[depth - 1] > GROUP) ++depth;
-  QModel* models = reinterpret_cast<QModel*>(s->buf);
-  double* p = s->buf + BATCH_MAX_MEMBERS * MODEL_DOUBLES;
-  QDir* dirs = reinterpret_cast<QDir*>(p);
-  p += BATCH_MAX_MEMBERS * GRAD_MAX_BATCH * DIR_DOUBLES;
-  auto take = [&](int64_t len) {
-    double* r = p;
-    p += len;
-    return r;
-  };
-  double* noise = take(N);
-  double* resid = take(N);
-  double* cbuf = take(N);
-  double* wbuf = take(N * J);
-  double* z = take(N);
-  double* keep = take(2 * C * WAVE);
-  double* work = take(W);
-  double* logsum = take(C);
-  double* sumsq = take(C);
-  int64_t* bad = reinterpret_cast<int64_t*>(take(C));
-  double* res = take(3 * nb);
-  double* dres = take(2 * P * nb);
-  double* alpha = take(vectors ? N : 0);
-  double* gnoise = take(vectors ? N : 0);
-  double* tan = take(D * N * (1 + J));
-  double* twork = take(D * TW);
-  double* tred = take(D * 2 * C);
-  const int64_t at = s->offsets[size_t(b0)];
-  const double* t = s->t + at;
-  const QExtent* tab = s->tab + b0;
-  const TableExtent ext{tab};
-  const TableGExtent gext{tab};
-  TGP_HIP_TRY(hipMemcpyAsync(models, models_host, size_t(nb) * sizeof(QModel), hipMemcpyHostToDevice, st));
-  TGP_HIP_TRY(hipMemcpyAsync(noise, a.noise + at, size_t(N) * sizeof(double), hipMemcpyHostToDevice, st));
-  TGP_HIP_TRY(hipMemcpyAsync(resid, a.resid + at, size_t(N) * sizeof(double), hipMemcpyHostToDevice, st));
-  // the primal part, each scan's chunk prefixes set aside
-  const dim3 grid(unsigned(blocks_for(top[0])), unsigned(nb));
-  const dim3 kgrid(unsigned(ceil_div(top[0] * WAVE, 256)), unsigned(nb));
-  qs_fold<<<grid, WAVE * WPB, 0, st>>>(models, t, noise, ext, work);
-  TGP_TRY(run_scan_table<ScanRiccati>(models, st, tab, nb, top, depth, work));
-  qs_emit<<<grid, WAVE * WPB, 0, st>>>(models, t, noise, ext, work, cbuf, wbuf, logsum, bad);
-  qs_keep_table<<<kgrid, 256, 0, st>>>(tab, work, ScanRiccati::ESZ, keep, 0);
-  qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, t, cbuf, wbuf, ext, 1, 1, resid, work);
-  TGP_TRY(run_scan_table<ScanAffine>(models, st, tab, nb, top, depth, work));
-  qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_FWD, models, t, cbuf, wbuf, ext, 1, 1, work, resid, z, sumsq);
-  qs_keep_table<<<kgrid, 256, 0, st>>>(tab, work, ScanAffine::ESZ, keep, 1);
-  qs_finish<<<unsigned(nb), WAVE, 0, st>>>(logsum, sumsq, bad, res, reinterpret_cast<int64_t*>(res) + 2,
-                                           TableSums{tab, 1}, 3);
-  TGP_HIP_TRY(hipGetLastError());
-  // direction passes, as in grad_batch_chain: pass k's host directions (member-major) stay alive until the
-  // synchronisation below, its results land after those of the passes before it (2 nb d0 doubles)
-  std::vector<QDir> hd(size_t(nb * P));
-  for (int64_t d0 = 0; d0 < P; d0 += D, ++*passes) {
-    const int64_t nd = std::min<int64_t>(D, P - d0);
-    QDir* h = hd.data() + nb * d0;
-    for (int64_t b = 0; b < nb; ++b)
-      pack_dirs(h + b * nd, d0, nd, a.nl, J, a.dleaves + (b0 + b) * P * a.nl * 4, a.dh + (b0 + b) * P * J,
-                a.dPinf + (b0 + b) * P * J * J);
-    TGP_HIP_TRY(hipMemcpyAsync(dirs, h, size_t(nb * nd) * sizeof(QDir), hipMemcpyHostToDevice, st));
-    const dim3 tgrid(unsigned(blocks_for(top[0])), unsigned(nd), unsigned(nb));
-    double *dcb = tan, *dwb = tan + nd * N, *dsum = tred, *dsum2 = tred + nd * C;
-    qs_gfac_fold<<<tgrid, WAVE * WPB, 0, st>>>(models, dirs, t, noise, gext, keep, twork);
-    TGP_TRY(run_scan_table<ScanCong>(models, st, tab, nb, top, depth, twork, nd));
-    qs_gfac_emit<<<tgrid, WAVE * WPB, 0, st>>>(models, dirs, t, noise, gext, keep, twork, dcb, dwb, dsum);
-    qs_gsol<<<tgrid, WAVE * WPB, 0, st>>>(models, dirs, t, cbuf, wbuf, dcb, dwb, resid, gext, keep, nullptr, twork,
-                                          nullptr);
-    TGP_TRY(run_scan_table<ScanAffine>(models, st, tab, nb, top, depth, twork, nd));
-    qs_gsol<<<tgrid, WAVE * WPB, 0, st>>>(models, dirs, t, cbuf, wbuf, dcb, dwb, resid, gext, keep, twork, nullptr,
-                                          dsum2);
-    // block b nd + d: (member b, direction d)'s two sums
-    qs_finish<<<unsigned(nb * nd), WAVE, 0, st>>>(dsum, dsum2, nullptr, dres + 2 * nb * d0, nullptr, TableSums{tab, nd},
-                                                  2);
-    TGP_HIP_TRY(hipGetLastError());
+  while (m.top[m.depth - 1] > GROUP) ++m.depth;
+  return m;
+}
+
+// the chains of one call on a set, after its split
+int series_chains(tgp_qsep_series* s, const ChainCall& a, int32_t* nchains, int32_t* npasses) {
+  TGP_TRY(grow(&s->buf, &s->buf_elems, s->buf_need));
+  const size_t chains = s->chain0.size() - 1;
+  int32_t passes = 0;
+  for (size_t k = 0; k < chains; ++k) {
+    const int64_t b0 = s->chain0[k], at = s->offsets[size_t(b0)];
+    ChainCall c = a.from(b0, at, at, at);
+    c.D = s->chain_d[k];
+    TGP_TRY(chain(table_members(s, b0, s->chain0[k + 1] - b0, c.D), s->ctx->stream, s->buf, c, &passes));
   }
-  if (vectors) {
-    qs_aff_fold<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_BWD, models, t, cbuf, wbuf, ext, 1, 1, z, work);
-    TGP_TRY(run_scan_table<ScanAffine>(models, st, tab, nb, top, depth, work));
-    qs_aff_emit<<<grid, WAVE * WPB, 0, st>>>(TGP_QS_BWD, models, t, cbuf, wbuf, ext, 1, 1, work, z, alpha, nullptr);
-    if (a.alpha)
-      TGP_HIP_TRY(hipMemcpyAsync(a.alpha + at, alpha, size_t(N) * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (a.gnoise) {
-      qs_pred_fold<<<grid, WAVE * WPB, 0, st>>>(1, 0, 1, models, t, cbuf, wbuf, nullptr, gext, work);
-      TGP_TRY(run_scan_table<ScanPred>(models, st, tab, nb, top, depth, work));
-      qs_invdiag_emit<<<grid, WAVE * WPB, 0, st>>>(models, t, cbuf, wbuf, alpha, gext, work, gnoise);
-      TGP_HIP_TRY(hipMemcpyAsync(a.gnoise + at, gnoise, size_t(N) * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    TGP_HIP_TRY(hipGetLastError());
-  }
-  std::vector<double> got(size_t(3 * nb)), dgot(size_t(2 * nb * P));
-  TGP_HIP_TRY(hipMemcpyAsync(got.data(), res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (P > 0) TGP_HIP_TRY(hipMemcpyAsync(dgot.data(), dres, dgot.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  TGP_HIP_TRY(hipStreamSynchronize(st));
-  for (int64_t b = 0; b < nb; ++b) {
-    const int64_t g = b0 + b, n = mine[b].n, lo = s->offsets[size_t(g)];
-    member_value(&got[size_t(3 * b)], n, &a.info[g], &a.out[g]);
-    const bool failed = a.info[g] != 0;  // c and w are not a factor of anything: what ran on them is overwritten
-    for (int64_t d0 = 0; d0 < P; d0 += D) {
-      const int64_t nd = std::min<int64_t>(D, P - d0);
-      for (int64_t d = 0; d < nd; ++d)
-        a.dout[g * P + d0 + d] = failed ? NAN : grad_value(&dgot[size_t(2 * (nb * d0 + b * nd + d))]);
-    }
-    for (int64_t i = 0; failed && i < n; ++i) {
-      if (a.gnoise) a.gnoise[lo + i] = NAN;
-      if (a.alpha) a.alpha[lo + i] = NAN;
-    }
-  }
+  if (nchains) *nchains = int32_t(chains);
+  if (npasses) *npasses = passes;
   return TGP_OK;
 }
 
@@ -2685,6 +2604,11 @@ int predict_mean(tgp_qsep* q, int64_t nrhs, const double* v_host, int v_is_alpha
   std::unique_lock<std::recursive_mutex> _tgp_lock((q)->ctx->mu);                     \
   TGP_HIP_TRY(hipSetDevice((q)->ctx->device))
 
+// in the two constructors: a failed HIP call ends with `fail`, which destroys the half-built handle
+#define Q_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) {                \
+    set_error("%s failed: %s", #expr, hipGetErrorString(_e));                          \
+    return fail(_e == hipErrorOutOfMemory ? TGP_E_NOMEM : TGP_E_HIP); } } while (0)
+
 }  // namespace
 
 extern "C" {
@@ -2701,9 +2625,6 @@ int tgp_qsep_create(tgp_ctx* ctx, int64_t n, const double* t_host, tgp_qsep** ou
   q->lc = chunk_length(n);
   q->nchunks = ceil_div(n, q->lc);
   auto fail = [&](int code) { tgp_qsep_destroy(q); return code; };
-#define Q_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) {                \
-    set_error("%s failed: %s", #expr, hipGetErrorString(_e));                          \
-    return fail(_e == hipErrorOutOfMemory ? TGP_E_NOMEM : TGP_E_HIP); } } while (0)
   Q_TRY(hipMalloc(&q->model, sizeof(QModel)));
   Q_TRY(hipMalloc(&q->t, size_t(n) * sizeof(double)));
   Q_TRY(hipMalloc(&q->noise, size_t(n) * sizeof(double)));
@@ -2713,7 +2634,6 @@ int tgp_qsep_create(tgp_ctx* ctx, int64_t n, const double* t_host, tgp_qsep** ou
   Q_TRY(hipMalloc(&q->gvec, sizeof(q->host_g)));
   Q_TRY(hipMemcpyAsync(q->t, t_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   Q_TRY(hipStreamSynchronize(ctx->stream));
-#undef Q_TRY
   if (int s = grow(&q->red, &q->red_elems, 2 * q->nchunks + 2); s < 0) return fail(s);
   *out = q;
   return TGP_OK;
@@ -2811,35 +2731,19 @@ int tgp_qsep_logprob_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_
                 (long long)noise_stride);
   TGP_ARG_CHECK(resid_stride == 0 || resid_stride == n, "the residual stride must be 0 (shared) or n (got %lld)",
                 (long long)resid_stride);
-  std::vector<QModel> models(size_t(nb), QModel{});
-  for (int64_t b = 0; b < nb; ++b)
-    TGP_TRY(pack_model(&models[size_t(b)], leaves + b * nleaves * 5, nleaves, state_map, J, hvec + b * J,
-                       Pinf + b * J * J));
+  std::vector<QModel> models;
+  TGP_TRY(pack_models(&models, nb, leaves, nleaves, state_map, J, hvec, Pinf));
   const BatchLayout lay = batch_layout(n, nc, J, noise_stride != 0, resid_stride != 0);
-  const int64_t budget = BATCH_SCRATCH_BYTES / int64_t(sizeof(double)) - lay.fixed;
+  const int64_t budget = BATCH_BUDGET - lay.fixed;
   TGP_ARG_CHECK(budget >= lay.per_member,
                 "the batch's scratch for one model (%lld doubles, %lld shared) exceeds its cap of %lld bytes",
                 (long long)lay.per_member, (long long)lay.fixed, (long long)BATCH_SCRATCH_BYTES);
   const int64_t cap = std::min<int64_t>({int64_t(nb), BATCH_MAX_MEMBERS, budget / lay.per_member});
-  TGP_TRY(grow(&q->bat, &q->bat_elems, lay.fixed + cap * lay.per_member));
-  hipStream_t st = q->ctx->stream;
-  double* shared = q->bat + BATCH_MAX_MEMBERS * MODEL_DOUBLES;
-  if (!noise_stride) {
-    TGP_HIP_TRY(hipMemcpyAsync(shared, noise_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
-    shared += n;
-  } else {
-    shared += cap * n;
-  }
-  if (!resid_stride)
-    TGP_HIP_TRY(hipMemcpyAsync(shared, resid_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
-  int32_t chains = 0;
-  for (int64_t b0 = 0; b0 < nb; b0 += cap, ++chains) {
-    const int64_t cnt = std::min<int64_t>(cap, nb - b0);
-    TGP_TRY(batch_chain(q, lay, cap, cnt, models.data() + b0, J, noise_host + b0 * noise_stride, noise_stride,
-                        resid_host + b0 * resid_stride, resid_stride, info + b0, out + b0));
-  }
-  if (nchains) *nchains = chains;
-  return TGP_OK;
+  const UniformMembers m{q->t, n, q->lc, nc, 0, cap, noise_stride, resid_stride, lay.work, 0};
+  ChainCall a{};
+  a.nl = nleaves, a.J = J, a.models = models.data(), a.noise = noise_host, a.resid = resid_host;
+  a.info = info, a.out = out;
+  return batch_chains(q, m, nb, lay.fixed + cap * lay.per_member, a, nchains, nullptr);
 }
 
 int tgp_qsep_grad_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_t nleaves, const int32_t* state_map,
@@ -2861,10 +2765,8 @@ int tgp_qsep_grad_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_t n
                 (long long)noise_stride);
   TGP_ARG_CHECK(resid_stride == 0 || resid_stride == n, "the residual stride must be 0 (shared) or n (got %lld)",
                 (long long)resid_stride);
-  std::vector<QModel> models(size_t(nb), QModel{});
-  for (int64_t b = 0; b < nb; ++b)
-    TGP_TRY(pack_model(&models[size_t(b)], leaves + b * nleaves * 5, nleaves, state_map, J, hvec + b * J,
-                       Pinf + b * J * J));
+  std::vector<QModel> models;
+  TGP_TRY(pack_models(&models, nb, leaves, nleaves, state_map, J, hvec, Pinf));
   const bool vectors = gnoise_host || alpha_host;
   const GradLayout lay = grad_split(n, nc, J, ndir, nb, noise_stride != 0, resid_stride != 0, vectors);
   TGP_ARG_CHECK(lay.members > 0,
@@ -2872,37 +2774,14 @@ int tgp_qsep_grad_batch(tgp_qsep* q, int32_t nb, const double* leaves, int32_t n
                 "exceeds its cap of %lld bytes",
                 (long long)lay.per_member, (long long)lay.per_dir, (long long)lay.fixed,
                 (long long)BATCH_SCRATCH_BYTES);
-  const int64_t cap = lay.members;
-  TGP_TRY(grow(&q->bat, &q->bat_elems, lay.fixed + cap * (lay.per_member + lay.dirs * lay.per_dir)));
-  hipStream_t st = q->ctx->stream;
-  double* shared = q->bat + BATCH_MAX_MEMBERS * (MODEL_DOUBLES + GRAD_MAX_BATCH * DIR_DOUBLES);
-  if (!noise_stride) {
-    TGP_HIP_TRY(hipMemcpyAsync(shared, noise_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
-    shared += n;
-  } else {
-    shared += cap * n;
-  }
-  if (!resid_stride)
-    TGP_HIP_TRY(hipMemcpyAsync(shared, resid_host, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
-  int32_t chains = 0, passes = 0;
-  const int64_t P = ndir;
-  for (int64_t b0 = 0; b0 < nb; b0 += cap, ++chains) {
-    const int64_t cnt = std::min<int64_t>(cap, nb - b0);
-    GradBatchArgs a;
-    a.nl = nleaves, a.J = J, a.ndir = P;
-    a.noise = noise_host + b0 * noise_stride, a.noise_stride = noise_stride;
-    a.resid = resid_host + b0 * resid_stride, a.resid_stride = resid_stride;
-    a.dleaves = P ? dleaves + b0 * P * nleaves * 4 : nullptr;
-    a.dh = P ? dh + b0 * P * J : nullptr;
-    a.dPinf = P ? dPinf + b0 * P * J * J : nullptr;
-    a.info = info + b0, a.out = out + b0, a.dout = P ? dout + b0 * P : nullptr;
-    a.gnoise = gnoise_host ? gnoise_host + b0 * n : nullptr;
-    a.alpha = alpha_host ? alpha_host + b0 * n : nullptr;
-    TGP_TRY(grad_batch_chain(q, lay, cnt, models.data() + b0, a, &passes));
-  }
-  if (nchains) *nchains = chains;
-  if (npasses) *npasses = passes;
-  return TGP_OK;
+  const int64_t cap = lay.members, P = ndir;
+  const UniformMembers m{q->t, n, q->lc, nc, 0, cap, noise_stride, resid_stride, lay.work, lay.dirs * lay.twork};
+  ChainCall a{};
+  a.grad = true, a.nl = nleaves, a.J = J, a.P = P, a.D = lay.dirs;
+  a.models = models.data(), a.noise = noise_host, a.resid = resid_host;
+  if (P > 0) a.dleaves = dleaves, a.dh = dh, a.dPinf = dPinf, a.dout = dout;
+  a.info = info, a.out = out, a.gnoise = gnoise_host, a.alpha = alpha_host;
+  return batch_chains(q, m, nb, lay.fixed + cap * (lay.per_member + lay.dirs * lay.per_dir), a, nchains, npasses);
 }
 
 int tgp_qsep_series_create(tgp_ctx* ctx, int32_t nseries, const int64_t* offsets, const double* t_concat,
@@ -2935,15 +2814,11 @@ int tgp_qsep_series_create(tgp_ctx* ctx, int32_t nseries, const int64_t* offsets
   s->offsets.assign(offsets, offsets + nseries + 1);
   s->ext = std::move(ext);
   auto fail = [&](int code) { tgp_qsep_series_destroy(s); return code; };
-#define Q_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) {                \
-    set_error("%s failed: %s", #expr, hipGetErrorString(_e));                          \
-    return fail(_e == hipErrorOutOfMemory ? TGP_E_NOMEM : TGP_E_HIP); } } while (0)
   const size_t total = size_t(offsets[nseries]);
   Q_TRY(hipMalloc(&s->t, total * sizeof(double)));
   Q_TRY(hipMalloc(&s->tab, size_t(nseries) * sizeof(QExtent)));
   Q_TRY(hipMemcpyAsync(s->t, t_concat, total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   Q_TRY(hipStreamSynchronize(ctx->stream));
-#undef Q_TRY
   *out = s;
   return TGP_OK;
 }
@@ -2968,20 +2843,13 @@ int tgp_qsep_series_logprob(tgp_qsep_series* s, const double* leaves, int32_t nl
   if (nchains) *nchains = 0;
   TGP_ARG_CHECK(leaves && state_map && hvec && Pinf, "null model array");
   TGP_ARG_CHECK(noise_concat && resid_concat && info && out, "null argument");
-  const int64_t nb = s->nseries;
-  std::vector<QModel> models(size_t(nb), QModel{});
-  for (int64_t b = 0; b < nb; ++b)
-    TGP_TRY(pack_model(&models[size_t(b)], leaves + b * nleaves * 5, nleaves, state_map, J, hvec + b * J,
-                       Pinf + b * J * J));
+  std::vector<QModel> models;
+  TGP_TRY(pack_models(&models, s->nseries, leaves, nleaves, state_map, J, hvec, Pinf));
   TGP_TRY(series_split(s, J));
-  TGP_TRY(grow(&s->buf, &s->buf_elems, s->buf_need));
-  const size_t chains = s->chain0.size() - 1;
-  for (size_t k = 0; k < chains; ++k) {
-    const int64_t b0 = s->chain0[k], cnt = s->chain0[k + 1] - b0;
-    TGP_TRY(series_chain(s, b0, cnt, models.data() + b0, J, noise_concat, resid_concat, info + b0, out + b0));
-  }
-  if (nchains) *nchains = int32_t(chains);
-  return TGP_OK;
+  ChainCall a{};
+  a.nl = nleaves, a.J = J, a.models = models.data(), a.noise = noise_concat, a.resid = resid_concat;
+  a.info = info, a.out = out;
+  return series_chains(s, a, nchains, nullptr);
 }
 
 int tgp_qsep_series_grad(tgp_qsep_series* s, const double* leaves, int32_t nleaves, const int32_t* state_map,
@@ -2996,25 +2864,15 @@ int tgp_qsep_series_grad(tgp_qsep_series* s, const double* leaves, int32_t nleav
   TGP_ARG_CHECK(leaves && state_map && hvec && Pinf, "null model array");
   TGP_ARG_CHECK(noise_concat && resid_concat && info && out, "null argument");
   TGP_ARG_CHECK(ndir == 0 || (dleaves && dh && dPinf && dout), "null direction array");
-  const int64_t nb = s->nseries;
-  std::vector<QModel> models(size_t(nb), QModel{});
-  for (int64_t b = 0; b < nb; ++b)
-    TGP_TRY(pack_model(&models[size_t(b)], leaves + b * nleaves * 5, nleaves, state_map, J, hvec + b * J,
-                       Pinf + b * J * J));
+  std::vector<QModel> models;
+  TGP_TRY(pack_models(&models, s->nseries, leaves, nleaves, state_map, J, hvec, Pinf));
   TGP_TRY(series_grad_split(s, J, ndir, gnoise_concat || alpha_concat));
-  TGP_TRY(grow(&s->buf, &s->buf_elems, s->buf_need));
-  const SeriesGradArgs a{nleaves,       J,     ndir, noise_concat, resid_concat,  dleaves,
-                         dh,            dPinf, info, out,          dout,          gnoise_concat,
-                         alpha_concat};
-  const size_t chains = s->chain0.size() - 1;
-  int32_t passes = 0;
-  for (size_t k = 0; k < chains; ++k) {
-    const int64_t b0 = s->chain0[k], cnt = s->chain0[k + 1] - b0;
-    TGP_TRY(series_grad_chain(s, b0, cnt, s->chain_d[k], models.data() + b0, a, &passes));
-  }
-  if (nchains) *nchains = int32_t(chains);
-  if (npasses) *npasses = passes;
-  return TGP_OK;
+  ChainCall a{};
+  a.grad = true, a.nl = nleaves, a.J = J, a.P = ndir;  // D: each chain's own
+  a.models = models.data(), a.noise = noise_concat, a.resid = resid_concat;
+  a.dleaves = dleaves, a.dh = dh, a.dPinf = dPinf, a.dout = dout;
+  a.info = info, a.out = out, a.gnoise = gnoise_concat, a.alpha = alpha_concat;
+  return series_chains(s, a, nchains, npasses);
 }
 
 int tgp_qsep_normalization(tgp_qsep* q, double* out) {
