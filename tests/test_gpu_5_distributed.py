@@ -74,6 +74,35 @@ def test_covariance_argument_and_dense_noise_through_the_hip_driver(pg, n, nb):
     gp.solver.close(); gp2.solver.close()
 
 
+@pytest.mark.parametrize("n,nb", [(1900, 512), (2000, 256)])
+def test_block_column_factor_of_a_known_integer_factor_is_exact(pg, n, nb):
+    """K = L0 L0^T from tests/_chol_exact.py's family X (integer L0, 128 x 128 diagonal blocks p I with p a power of two)
+    through `covariance=`: every pivot, reciprocal and Schur complement of the block-column driver is exact, so the factor
+    is L0 and L0^-1 (L0 w) is w, bit for bit, with every tile of every block column weighted."""
+    import _chol_exact as cx
+    from tinygp_amd import kernels
+    from tinygp_amd.distributed import BlockCyclicCholesky
+
+    L0 = cx.factor(n, "X")
+    w, r = cx.rhs(L0)
+    s = BlockCyclicCholesky(_k(kernels), np.arange(n, dtype=np.float64), np.zeros(n), nb=nb, dist=pg, covariance=cx.matrix(L0))
+    try:
+        got = s.log_probability(r)
+        assert s.info == 0
+        np.testing.assert_allclose(got, cx.loglik(L0, w), rtol=1e-11)  # (only the order of the N equal log p terms is inexact)
+        L = np.zeros((n, n))
+        for l in range(len(s.owned)):
+            j0 = s.owned[l] * nb
+            col = s.ops.column(l, s.rows(s.owned[l]))
+            rows, cols = min(n - j0, col.shape[0]), min(nb, n - j0)
+            L[j0:j0 + rows, j0:j0 + cols] = col[:rows, :cols]
+        cx.check_exact(np.tril(L), L0)  # (above the diagonal the block columns keep K, like LAPACK)
+        z = s.solve_triangular(r)
+        assert np.array_equal(z, w), (int((z != w).sum()), int(np.argmax(z != w)))
+    finally:
+        s.close()
+
+
 @pytest.mark.parametrize("n,nb,dtype,rtol", [(2000, 256, np.float64, 1e-8), (3000, 512, np.float64, 1e-8),
                                               (5000, 1024, np.float64, 1e-8), (1500, 128, np.float32, 5e-4)])
 def test_block_cyclic_hip_single_rank(pg, n, nb, dtype, rtol):
