@@ -412,6 +412,34 @@ int tgp_small_predict(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int3
                       const double* noise_host, const double* resid_host, const double* Xt_host, int64_t xt_rows,
                       const int64_t* xt_off, const int32_t* m, const tgp_kop* pred_progs, const int32_t* pred_prog_off,
                       const int64_t* out_off, int32_t* info_host, double* out_host, double* mean_host, double* var_host);
+/* The same members conditioned on their data at test points of their own, with the JOINT posterior: what the
+ * reference's users get from jax.vmap over gp.condition(y, X_test, diag=tau) and its .gp.loc, .gp.covariance and
+ * .gp.sample (gp.py:140-223, 273-311; solvers/direct.py:75-95).  The test points ride as further columns of the
+ * member's matrix, so n[b] + m[b] <= TGP_SMALL_MAX_N.  The arguments of tgp_small_predict up to pred_prog_off, and
+ *   test_diag_host / tvec_off   member b's m[b] values added to the diagonal of its conditional covariance
+ *   mean_off / mean_host        member b's m[b] conditional means k*^T K^-1 r go to the entries at mean_off[b]
+ *   cov_off / cov_host          member b's m[b] x m[b] covariance k** + diag(tau) - k*^T K^-1 k*, row-major and exactly
+ *                               symmetric, goes to the m[b]^2 entries at cov_off[b]; cov_host (and cov_off) may be
+ *                               NULL: no covariance is written or copied
+ *   ndraw                       nb counts S_b >= 0 of joint draws
+ *   xi_host / xi_off            member b's S_b x m[b] standard normals, draw-major, at xi_off[b]
+ *   samples_host                mean + chol(covariance) xi_s per draw, at the offsets and in the shape of xi_host; may be
+ *                               NULL iff every S_b = 0 (then xi_host too)
+ *   info_host / out_host        as for tgp_small_logprob; the values have its bits
+ *   cond_info_host              per member 0, or the 1-based index of the first pivot of the covariance's factorisation
+ *                               that is not > 0: that member's draws are NaN, its value, mean and covariance stand
+ * A member whose data block fails (info != 0) has NaN everywhere.  A member's outputs depend on that member's data
+ * alone, a draw's on its member and its own normals.
+ * TGP_E_ARG as for tgp_small_predict, and for n[b] + m[b] > TGP_SMALL_MAX_N, a negative S or offset, xi_host or
+ * samples_host NULL with some S_b > 0; the member is named. */
+int tgp_small_condition(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off, const int64_t* x_off,
+                        const int32_t* n, int32_t d, const double* X_host, int64_t x_rows, const int64_t* vec_off,
+                        const double* noise_host, const double* resid_host, const double* Xt_host, int64_t xt_rows,
+                        const int64_t* xt_off, const int32_t* m, const tgp_kop* pred_progs, const int32_t* pred_prog_off,
+                        const double* test_diag_host, const int64_t* tvec_off, const int64_t* mean_off, double* mean_host,
+                        const int64_t* cov_off, double* cov_host, const int32_t* ndraw, const double* xi_host,
+                        const int64_t* xi_off, double* samples_host, int32_t* info_host, int32_t* cond_info_host,
+                        double* out_host);
 
 /* ---- block-cyclic column Cholesky over the GPUs of one node (BASELINE configs 4 / 5) ----------
  * The reference has NO multi-device code; these entry points are one RANK's share

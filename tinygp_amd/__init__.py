@@ -17,6 +17,8 @@ from tinygp_amd.solvers.quasisep import log_probability_series as log_probabilit
 from tinygp_amd.solvers.quasisep import log_probability_and_grad_series as log_probability_and_grad_series
 from tinygp_amd.solvers.small import log_probability_and_grad_datasets as log_probability_and_grad_datasets
 from tinygp_amd.solvers.small import log_probability_datasets as log_probability_datasets
+from tinygp_amd.solvers.small import condition_datasets as condition_datasets
 from tinygp_amd.solvers.small import predict_datasets as predict_datasets
+from tinygp_amd.solvers.small import sample_conditional_datasets as sample_conditional_datasets
 
 __version__ = "0.1.0"

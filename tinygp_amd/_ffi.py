@@ -103,6 +103,9 @@ SIGNATURES = {
                                _pdbl, _pdbl, _pdbl, _pdbl],
     "tgp_small_predict": [_vp, _i32, _vp, _pi32, _pi64, _pi32, _i32, _vp, _i64, _pi64, _vp, _vp, _vp, _i64, _pi64, _pi32,
                           _vp, _pi32, _pi64, _pi32, _pdbl, _pdbl, _pdbl],
+    "tgp_small_condition": [_vp, _i32, _vp, _pi32, _pi64, _pi32, _i32, _vp, _i64, _pi64, _vp, _vp, _vp, _i64, _pi64,
+                            _pi32, _vp, _pi32, _vp, _pi64, _pi64, _pdbl, _pi64, _pdbl, _pi32, _vp, _pi64, _pdbl, _pi32,
+                            _pi32, _pdbl],
     "tgp_trace_factor": [_i64, C.c_char_p, _i32, _pi64, _i64, _pi64],
     "tgp_chain_stamps": [_vp, _pi64, _i64, _pi64],
     "tgp_chain_task": [_i64, _i64, _i64, _i64, _i64, _pi32, _pi64],

@@ -1,5 +1,5 @@
 // small.hip -- batches of SMALL dense problems, one workgroup each (tgp_small_logprob, tgp_small_logprob_grad,
-// tgp_small_predict).
+// tgp_small_predict, tgp_small_condition).
 //
 // The dense path of chol.hip pads every matrix to 128-row tiles and pays a handle, uploads, a launch chain and a host
 // join per evaluation: at N <= 192 that is all overhead.  Here a workgroup of 256 threads owns a whole member: it
@@ -29,6 +29,11 @@
 // then stay in LDS, read-only, and every wave walks test points of its own without another barrier: the cross
 // covariances of a point in registers, the mean as their product with alpha, the variance by a forward substitution
 // against L inside the wave.
+//
+// The conditional covariance and joint draws (small_condition_kernel) carry the m test points as further COLUMNS of
+// the same trapezoid, P = n + m columns and the residual in row P: the first n steps of the one elimination leave the
+// Schur complement Sigma* = k** + diag(tau) - A^T A in the trailing triangle and -mu* in row P behind it, a second
+// phase of the same steps on that triangle is its Cholesky factor, and a draw is a triangular product per wave.
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -67,6 +72,16 @@ struct SmallPredRow {
 };
 static_assert(sizeof(SmallPredRow) == 64, "the staging buffer is carved in 8-byte units");
 
+// one table row of a conditioning launch: a member with its m test points as columns n .. n + m - 1.  The member's
+// fields as in SmallRow; xt_off in rows of the launch's Xt; tvec_off into the launch's test diagonal and means (m
+// entries); cov_off into its covariances (m^2 entries); xi_off into its normals and samples (S m entries, draw-major);
+// pred_prog: the program of the rows >= n, or -1 for the member's own; S: the draws asked for
+struct SmallCondRow {
+  int64_t x_off, noise_off, resid_off, xt_off, tvec_off, cov_off, xi_off;
+  int32_t n, d, prog, pred_prog, m, S;
+};
+static_assert(sizeof(SmallCondRow) == 80, "the staging buffer is carved in 8-byte units");
+
 // test points a wave carries through the forward substitution at once (one LDS read of l_ip feeds this many FMAs)
 #ifndef TGP_SMALL_PRED_T
 #define TGP_SMALL_PRED_T 4
@@ -83,22 +98,37 @@ __device__ __forceinline__ int col_off(int j, int n) { return j * (n + 1) - j * 
 
 // Steps 1 - 4 of a member: assemble the trapezoid [K + diag(noise); r^T] in A, factor it there.  Returns 0, or the
 // 1-based index of the first pivot that is not > 0 -- the same number in every thread of the workgroup.
+// COND (small_condition_kernel): the trapezoid has P = n + m columns and its residual in row P,
+//   [ k(X, X) + diag(noise)            .            ]   rows 0 .. n - 1
+//   [ pk(X*, X)          pk(X*, X*) + diag(tau)     ]   rows n .. P - 1
+//   [ r^T                           0^T             ]   row P
+// and the SAME n elimination steps run over all P columns and P + 1 rows: entry (i, j) with i, j < n and row P in the
+// first n columns receive the operations of the plain form in its order (the value's bits do not change), the
+// trailing triangle becomes the Schur complement and row P behind column n becomes -mu*.
+template <bool COND = false>
 __device__ __forceinline__ int small_assemble_factor(double* A, const KProg& kp, const double* x, const double* nz,
-                                                     const double* rs, int n, int d) {
+                                                     const double* rs, int n, int d, const KProg* pk = nullptr,
+                                                     const double* xt = nullptr, const double* tau = nullptr,
+                                                     int m = 0) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int P = COND ? n + m : n;
 
-  // 1 + 2: wave w assembles columns w, w + 4, ..; lane l their rows j + l, j + l + 64, ..; row n is the residual
-  for (int j = wave; j < n; j += SMALL_WAVES) {
-    double* col = A + col_off(j, n);
-    for (int i = j + lane; i <= n; i += 64) {
+  // 1 + 2: wave w assembles columns w, w + 4, ..; lane l their rows j + l, j + l + 64, ..; row P is the residual
+  for (int j = wave; j < P; j += SMALL_WAVES) {
+    double* col = A + col_off(j, P);
+    const bool tj = COND && j >= n;
+    const double* b = tj ? xt + int64_t(j - n) * d : x + int64_t(j) * d;
+    for (int i = j + lane; i <= P; i += 64) {
       double v;
-      if (i == n) {
-        v = rs[j];
+      if (i == P) {
+        v = tj ? 0.0 : rs[j];
       } else {
+        const bool ti = COND && i >= n;
+        const double* a = ti ? xt + int64_t(i - n) * d : x + int64_t(i) * d;
         double r1, r2, r3;
-        pair_dist<double, 2, 0>(x + int64_t(i) * d, x + int64_t(j) * d, d, r1, r2, r3);
-        v = eval_kprog<double, 2>(kp, r1, r2, r3);
-        if (i == j) v += nz[j];  // noise.py:77-78 fused, as in kmat_kernel
+        pair_dist<double, 2, 0>(a, b, d, r1, r2, r3);
+        v = eval_kprog<double, 2>(ti ? *pk : kp, r1, r2, r3);
+        if (i == j) v += tj ? tau[j - n] : nz[j];  // noise.py:77-78 fused, as in kmat_kernel
       }
       col[i - j] = v;
     }
@@ -109,7 +139,7 @@ __device__ __forceinline__ int small_assemble_factor(double* A, const KProg& kp,
   // leave is the workgroup's, no barrier sits under divergent control flow.
   int fail = 0;
   for (int p = 0; p < n; ++p) {
-    double* cp = A + col_off(p, n);
+    double* cp = A + col_off(p, P);
     const double pivot = cp[0];
     if (!(pivot > 0.0)) {
       fail = p + 1;
@@ -117,12 +147,12 @@ __device__ __forceinline__ int small_assemble_factor(double* A, const KProg& kp,
     }
     // (the diagonal word keeps the pivot L_pp^2: a thread may still be reading it while the column is scaled)
     const double lpp = sqrt(pivot);
-    for (int i = p + 1 + int(threadIdx.x); i <= n; i += SMALL_THREADS) cp[i - p] = cp[i - p] / lpp;
+    for (int i = p + 1 + int(threadIdx.x); i <= P; i += SMALL_THREADS) cp[i - p] = cp[i - p] / lpp;
     __syncthreads();
-    for (int j = p + 1 + wave; j < n; j += SMALL_WAVES) {
-      double* col = A + col_off(j, n);
+    for (int j = p + 1 + wave; j < P; j += SMALL_WAVES) {
+      double* col = A + col_off(j, P);
       const double ljp = cp[j - p];
-      for (int i = j + lane; i <= n; i += 64) col[i - j] = __builtin_fma(-cp[i - p], ljp, col[i - j]);
+      for (int i = j + lane; i <= P; i += 64) col[i - j] = __builtin_fma(-cp[i - p], ljp, col[i - j]);
     }
     __syncthreads();
   }
@@ -130,14 +160,16 @@ __device__ __forceinline__ int small_assemble_factor(double* A, const KProg& kp,
 }
 
 // Steps 5 + 6: the value from the factored trapezoid (the pivots on the diagonal, z in row n), written by thread 0 to
-// entry `slot` of out and info (a negative slot: computed, not written -- a later chunk of a prediction).
+// entry `slot` of out and info (a negative slot: computed, not written -- a later chunk of a prediction).  P: the
+// columns of the trapezoid (n, or n + m for small_condition_kernel: the value comes from the first n columns alone).
 __device__ __forceinline__ void small_write_value(const double* A, double (&red)[2][SMALL_THREADS], int n, int fail,
-                                                  double* __restrict__ out, int32_t* __restrict__ info, int64_t slot) {
+                                                  double* __restrict__ out, int32_t* __restrict__ info, int64_t slot,
+                                                  int P) {
   // 5: sum log L_pp and sum z_p^2 (one term per thread: n < 256), a fixed tree
   double sl = 0.0, sz = 0.0;
   if (fail == 0 && int(threadIdx.x) < n) {
-    const double* cp = A + col_off(int(threadIdx.x), n);
-    const double z = cp[n - int(threadIdx.x)];
+    const double* cp = A + col_off(int(threadIdx.x), P);
+    const double z = cp[P - int(threadIdx.x)];
     sl = log(sqrt(cp[0]));
     sz = z * z;
   }
@@ -191,7 +223,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_logprob_kernel(const Smal
   const KProg& kp = progs[row.prog];
   const int n = row.n, d = row.d;
   const int fail = small_assemble_factor(A, kp, X + row.x_off * d, noise + row.noise_off, resid + row.resid_off, n, d);
-  small_write_value(A, red, n, fail, out, info, blockIdx.x);
+  small_write_value(A, red, n, fail, out, info, blockIdx.x, n);
 }
 
 // Value AND gradient of one member.  After the value (the text above):
@@ -233,7 +265,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_grad_kernel(const SmallRo
   double* gd = grad_dims + int64_t(blockIdx.x) * d;
 
   const int fail = small_assemble_factor(A, kp, x, noise + row.noise_off, resid + row.resid_off, n, d);
-  small_write_value(A, red, n, fail, out, info, blockIdx.x);
+  small_write_value(A, red, n, fail, out, info, blockIdx.x, n);
   if (fail) {  // the workgroup's decision: NaN in every gradient of this member
     const double nan = __builtin_nan("");
     for (int t = tid; t < 2 * kp.n; t += SMALL_THREADS) gp[t] = nan;
@@ -382,7 +414,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_predict_kernel(const Smal
   double* pv = var_out ? var_out + row.out_off : nullptr;
 
   const int fail = small_assemble_factor(A, kp, x, noise + row.noise_off, resid + row.resid_off, n, d);
-  small_write_value(A, red, n, fail, out, info, row.slot);
+  small_write_value(A, red, n, fail, out, info, row.slot, n);
   if (fail) {  // the workgroup's decision: NaN in every prediction of this row
     const double nan = __builtin_nan("");
     for (int t = tid; t < m; t += SMALL_THREADS) {
@@ -479,6 +511,137 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_predict_kernel(const Smal
   }
 }
 
+// Value, conditional mean, conditional covariance and joint draws of one member at its m test points.
+//   1 - 6  small_assemble_factor<true> and the value: phase 1 of the elimination, p = 0 .. n - 1 over P = n + m columns
+//          and rows <= P.  The trailing triangle then holds Sigma* = pk(X*, X*) + diag(tau) - A^T A, A = L11^-1 K*, and
+//          row P behind column n holds -mu* (it started from 0 and took -z_p l_{n+i,p} for p = 0 .. n - 1).
+//   C1     mu*_i is the negation of that word; Sigma* goes out as a full row-major m x m matrix, both halves from the
+//          one LDS word (when the launch asks for covariances).
+//   C2     only with S > 0 -- phase 2, the same steps for p = n .. P - 1 on rows < P (row P keeps -mu*): the Cholesky
+//          of Sigma*.  The first pivot that is not > 0 gives cond_info = p - n + 1 and NaN draws; value, mean and
+//          covariance are out already.
+//   C3     the diagonal words of the trailing block become L_pp, once, behind one barrier.
+//   C4     L22 and mu* are read-only, no barrier follows: wave w takes the draws s = w, w + 4, ..; lane l holds rows
+//          i = l, l + 64, l + 128 of f in registers, starting from mu*_i, and for k = 0 .. m - 1 in that order takes
+//          f_i <- fma(L22[i, k], xi[s, k], f_i) for its rows i >= k (column k from LDS, consecutive rows; xi[s, k]
+//          wave-uniform from global memory).  A draw's bits depend on its member and its own normals alone.
+// Every barrier sits under control flow that depends on n, m, S, the program and the two `fail` values alone.
+__global__ __launch_bounds__(SMALL_THREADS) void small_condition_kernel(const SmallCondRow* __restrict__ rows,
+                                                                          const KProg* __restrict__ progs,
+                                                                          const double* __restrict__ X,
+                                                                          const double* __restrict__ noise,
+                                                                          const double* __restrict__ resid,
+                                                                          const double* __restrict__ Xt,
+                                                                          const double* __restrict__ tdiag,
+                                                                          const double* __restrict__ xi,
+                                                                          double* __restrict__ out,
+                                                                          int32_t* __restrict__ info,
+                                                                          int32_t* __restrict__ cond_info,
+                                                                          double* __restrict__ mean_out,
+                                                                          double* __restrict__ cov_out,
+                                                                          double* __restrict__ samples) {
+  extern __shared__ __attribute__((aligned(16))) double A[];  // the packed trapezoid of P columns
+  __shared__ double red[2][SMALL_THREADS];
+  const SmallCondRow row = rows[blockIdx.x];
+  const KProg& kp = progs[row.prog];
+  const KProg& pk = progs[row.pred_prog >= 0 ? row.pred_prog : row.prog];
+  const int n = row.n, d = row.d, m = row.m, S = row.S, P = n + m;
+  const int tid = threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double* pm = mean_out + row.tvec_off;
+  double* pc = cov_out ? cov_out + row.cov_off : nullptr;
+  double* ps = samples + row.xi_off;  // (never dereferenced with S = 0)
+  const double nan = __builtin_nan("");
+
+  const int fail = small_assemble_factor<true>(A, kp, X + row.x_off * d, noise + row.noise_off, resid + row.resid_off,
+                                               n, d, &pk, Xt + row.xt_off * d, tdiag + row.tvec_off, m);
+  small_write_value(A, red, n, fail, out, info, blockIdx.x, P);
+  if (fail) {  // the workgroup's decision: NaN in every output of this member
+    for (int t = tid; t < m; t += SMALL_THREADS) pm[t] = nan;
+    if (pc)
+      for (int t = tid; t < m * m; t += SMALL_THREADS) pc[t] = nan;
+    for (int64_t t = tid; t < int64_t(S) * m; t += SMALL_THREADS) ps[t] = nan;
+    if (tid == 0) cond_info[blockIdx.x] = 0;
+    return;
+  }
+
+  // C1 (the last barrier of phase 1 lies behind; nothing is written to A before the barrier below)
+  for (int t = tid; t < m; t += SMALL_THREADS) pm[t] = -A[col_off(n + t, P) + m - t];
+  if (pc) {
+    for (int j = wave; j < m; j += SMALL_WAVES) {
+      const double* col = A + col_off(n + j, P);
+      for (int i = j + lane; i < m; i += 64) {
+        const double v = col[i - j];
+        pc[int64_t(i) * m + j] = v;
+        pc[int64_t(j) * m + i] = v;
+      }
+    }
+  }
+  if (S == 0) {
+    if (tid == 0) cond_info[blockIdx.x] = 0;
+    return;
+  }
+  __syncthreads();
+
+  // C2
+  int fail2 = 0;
+  for (int p = n; p < P; ++p) {
+    double* cp = A + col_off(p, P);
+    const double pivot = cp[0];
+    if (!(pivot > 0.0)) {
+      fail2 = p - n + 1;
+      break;
+    }
+    const double lpp = sqrt(pivot);
+    for (int i = p + 1 + tid; i < P; i += SMALL_THREADS) cp[i - p] = cp[i - p] / lpp;
+    __syncthreads();
+    for (int j = p + 1 + wave; j < P; j += SMALL_WAVES) {
+      double* col = A + col_off(j, P);
+      const double ljp = cp[j - p];
+      for (int i = j + lane; i < P; i += 64) col[i - j] = __builtin_fma(-cp[i - p], ljp, col[i - j]);
+    }
+    __syncthreads();
+  }
+  if (tid == 0) cond_info[blockIdx.x] = fail2;
+  if (fail2) {  // the workgroup's decision: NaN in every draw of this member
+    for (int64_t t = tid; t < int64_t(S) * m; t += SMALL_THREADS) ps[t] = nan;
+    return;
+  }
+
+  // C3
+  if (tid < m) A[col_off(n + tid, P)] = sqrt(A[col_off(n + tid, P)]);
+  __syncthreads();
+
+  // C4
+  constexpr int R = SMALL_PRED_ROWS;
+  const double* px = xi + row.xi_off;
+  double mu[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = lane + 64 * r;
+    mu[r] = i < m ? -A[col_off(n + i, P) + m - i] : 0.0;
+  }
+  for (int s = wave; s < S; s += SMALL_WAVES) {
+    const double* z = px + int64_t(s) * m;
+    double f[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) f[r] = mu[r];
+    for (int k = 0; k < m; ++k) {
+      const double* ck = A + col_off(n + k, P);
+      const double zk = z[k];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int i = lane + 64 * r;
+        if (i >= k && i < m) f[r] = __builtin_fma(ck[i - k], zk, f[r]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int i = lane + 64 * r;
+      if (i < m) ps[int64_t(s) * m + i] = f[r];
+    }
+  }
+}
+
 // the gradient's host outputs (tgp_small_logprob_grad); `on` is false for the value alone
 struct SmallGradOut {
   bool on = false;
@@ -502,8 +665,24 @@ struct SmallPredIn {
   double* var = nullptr;
 };
 
+// the conditioning's host arguments beside the prediction's (tgp_small_condition: SmallPredIn carries the test
+// points, the second programs, and the means with mean_off as out_off; var stays null); null for the other three
+struct SmallCondIn {
+  const double* tdiag = nullptr;
+  const int64_t* tvec_off = nullptr;
+  const int64_t* cov_off = nullptr;
+  double* cov = nullptr;
+  const int32_t* ndraw = nullptr;
+  const double* xi = nullptr;
+  const int64_t* xi_off = nullptr;
+  double* samples = nullptr;
+  int32_t* cond_info = nullptr;
+};
+
 // what members [b0, b1) need in the staging buffer, and where
 struct SmallLaunch {
+  int64_t cov_doubles = 0, xi_doubles = 0;  // a conditioning's covariances and normals (= samples); its max_n is the
+                                            // largest n + m, its out_doubles the test diagonal (= means)
   int64_t b0 = 0, b1 = 0, max_n = 0;
   int64_t x_doubles = 0, vec_doubles = 0, ops = 0;
   int64_t pred_rows = 0, pred_progs = 0, xt_doubles = 0, out_doubles = 0;  // a prediction's table rows, second
@@ -531,13 +710,29 @@ int64_t pred_launch_bytes(int64_t nb, int64_t rows, int64_t pred_progs, int64_t 
          (x_doubles + 2 * vec_doubles + xt_doubles) * 8 + nb * 8 + round_up(nb * 4, 8) + out_doubles * (var ? 16 : 8);
 }
 
+// a conditioning launch: table rows (one per member) | programs, the second ones behind the members' | X | noise |
+// residual | test points | test diagonal | normals | values | info | cond_info | means (| covariances) | samples
+int64_t cond_launch_bytes(int64_t nb, int64_t pred_progs, int64_t x_doubles, int64_t vec_doubles, int64_t xt_doubles,
+                          int64_t out_doubles, int64_t cov_doubles, int64_t xi_doubles, bool cov) {
+  return nb * int64_t(sizeof(SmallCondRow)) + (nb + pred_progs) * int64_t(sizeof(KProg)) +
+         (x_doubles + 2 * vec_doubles + xt_doubles + 2 * out_doubles + (cov ? cov_doubles : 0) + 2 * xi_doubles) * 8 +
+         nb * 8 + 2 * round_up(nb * 4, 8);
+}
+
 int64_t pred_chunks(int64_t m) { return m <= 0 ? 1 : (m + TGP_SMALL_PRED_CHUNK - 1) / TGP_SMALL_PRED_CHUNK; }
 
 // enqueues every launch; the host buffers in `launches` must outlive the join
 int small_enqueue(tgp_ctx* ctx, std::vector<SmallLaunch>& launches, int32_t d, const int32_t* prog_off,
-                  int32_t* info_host, double* out_host, const SmallGradOut& g, const SmallPredIn* p) {
+                  int32_t* info_host, double* out_host, const SmallGradOut& g, const SmallPredIn* p,
+                  const SmallCondIn* c) {
   hipStream_t st = ctx->stream;
-  if (p && !ctx->small_pred_lds_raised) {
+  if (c && !ctx->small_cond_lds_raised) {
+    TGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(small_condition_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    int(small_lds_doubles(TGP_SMALL_MAX_N) * 8)));
+    ctx->small_cond_lds_raised = true;
+  }
+  if (p && !c && !ctx->small_pred_lds_raised) {
     TGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(small_predict_kernel<SMALL_PRED_T>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize,
                                     int(small_lds_doubles(TGP_SMALL_MAX_N) * 8)));
@@ -557,7 +752,9 @@ int small_enqueue(tgp_ctx* ctx, std::vector<SmallLaunch>& launches, int32_t d, c
   }
   int64_t need = 0;
   for (const SmallLaunch& l : launches)
-    need = std::max(need, p ? pred_launch_bytes(l.b1 - l.b0, l.pred_rows, l.pred_progs, l.x_doubles, l.vec_doubles,
+    need = std::max(need, c ? cond_launch_bytes(l.b1 - l.b0, l.pred_progs, l.x_doubles, l.vec_doubles, l.xt_doubles,
+                                                l.out_doubles, l.cov_doubles, l.xi_doubles, c->cov != nullptr)
+                          : p ? pred_launch_bytes(l.b1 - l.b0, l.pred_rows, l.pred_progs, l.x_doubles, l.vec_doubles,
                                                 l.xt_doubles, l.out_doubles, p->var != nullptr)
                             : launch_bytes(l.b1 - l.b0, l.x_doubles, l.vec_doubles,
                                            grad_doubles(g.on, l.b1 - l.b0, l.ops, l.vec_doubles, d)));
@@ -565,6 +762,34 @@ int small_enqueue(tgp_ctx* ctx, std::vector<SmallLaunch>& launches, int32_t d, c
   for (SmallLaunch& l : launches) {
     const int64_t nb = l.b1 - l.b0;
     char* base = static_cast<char*>(ctx->d_work);
+    if (c) {
+      const SmallCondRow* crows = reinterpret_cast<const SmallCondRow*>(base);
+      const KProg* progs = reinterpret_cast<const KProg*>(base + nb * sizeof(SmallCondRow));
+      const double* X = reinterpret_cast<const double*>(progs + nb + l.pred_progs);
+      const double* noise = X + l.x_doubles;
+      const double* resid = noise + l.vec_doubles;
+      const double* Xt = resid + l.vec_doubles;
+      const double* tdiag = Xt + l.xt_doubles;
+      const double* xi = tdiag + l.out_doubles;
+      double* out = const_cast<double*>(xi) + l.xi_doubles;
+      int32_t* info = reinterpret_cast<int32_t*>(out + nb);
+      int32_t* cinfo = info + round_up(nb * 4, 8) / 4;
+      double* mean = out + nb + 2 * (round_up(nb * 4, 8) / 8);
+      double* cov = c->cov ? mean + l.out_doubles : nullptr;
+      double* samples = mean + l.out_doubles + (c->cov ? l.cov_doubles : 0);
+      TGP_HIP_TRY(hipMemcpyAsync(base, l.host.data(), l.host.size(), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(small_condition_kernel, dim3(unsigned(nb)), dim3(SMALL_THREADS),
+                         size_t(small_lds_doubles(l.max_n) * 8), st, crows, progs, X, noise, resid, Xt, tdiag, xi, out,
+                         info, cinfo, mean, cov, samples);
+      TGP_HIP_TRY(hipGetLastError());
+      l.back.resize(size_t(l.out_doubles + (c->cov ? l.cov_doubles : 0) + l.xi_doubles));
+      if (!l.back.empty())
+        TGP_HIP_TRY(hipMemcpyAsync(l.back.data(), mean, l.back.size() * 8, hipMemcpyDeviceToHost, st));
+      TGP_HIP_TRY(hipMemcpyAsync(out_host + l.b0, out, size_t(nb) * 8, hipMemcpyDeviceToHost, st));
+      TGP_HIP_TRY(hipMemcpyAsync(info_host + l.b0, info, size_t(nb) * 4, hipMemcpyDeviceToHost, st));
+      TGP_HIP_TRY(hipMemcpyAsync(c->cond_info + l.b0, cinfo, size_t(nb) * 4, hipMemcpyDeviceToHost, st));
+      continue;
+    }
     if (p) {
       const SmallPredRow* prows = reinterpret_cast<const SmallPredRow*>(base);
       const KProg* progs = reinterpret_cast<const KProg*>(base + l.pred_rows * sizeof(SmallPredRow));
@@ -628,7 +853,7 @@ int small_enqueue(tgp_ctx* ctx, std::vector<SmallLaunch>& launches, int32_t d, c
 int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off, const int64_t* x_off,
                const int32_t* n, int32_t d, const double* X_host, int64_t x_rows, const int64_t* vec_off,
                const double* noise_host, const double* resid_host, int32_t* info_host, double* out_host,
-               const SmallGradOut& g, const SmallPredIn* p = nullptr) {
+               const SmallGradOut& g, const SmallPredIn* p = nullptr, const SmallCondIn* c = nullptr) {
   TGP_ARG_CHECK(ctx != nullptr, "null context");
   TGP_ARG_CHECK(nb >= 0, "negative number of members (%d)", nb);
   if (nb == 0) return TGP_OK;
@@ -636,7 +861,8 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
   TGP_HIP_TRY(hipSetDevice(ctx->device));
   TGP_ARG_CHECK(progs && prog_off && x_off && n && X_host && vec_off && noise_host && resid_host && info_host && out_host &&
                     (!g.on || g.params) && (!p || (p->xt_off && p->m && p->out_off && p->mean && (p->Xt || p->xt_rows == 0) &&
-                                                   (!p->progs == !p->prog_off))),
+                                                   (!p->progs == !p->prog_off))) &&
+                    (!c || (c->tdiag && c->tvec_off && c->ndraw && c->xi_off && c->cond_info && (!c->cov || c->cov_off))),
                 "null argument");
   TGP_ARG_CHECK(d >= 1 && d <= TGP_MAX_DIM, "the input dimension must be 1 .. %d (got %d)", TGP_MAX_DIM, d);
   TGP_ARG_CHECK(x_rows >= 0, "negative number of coordinate rows (%lld)", (long long)x_rows);
@@ -665,6 +891,16 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
                   (long long)(p->xt_off[b] + p->m[b]), (long long)p->xt_rows);
     TGP_ARG_CHECK(p->out_off[b] >= 0, "member %lld: negative offset into the predictions (%lld)", (long long)b,
                   (long long)p->out_off[b]);
+    if (c) {
+      TGP_ARG_CHECK(int64_t(n[b]) + p->m[b] <= TGP_SMALL_MAX_N,
+                    "member %lld: data and test points together must be at most %d (got %d + %d)", (long long)b,
+                    TGP_SMALL_MAX_N, n[b], p->m[b]);
+      TGP_ARG_CHECK(c->ndraw[b] >= 0, "member %lld: negative number of draws (%d)", (long long)b, c->ndraw[b]);
+      TGP_ARG_CHECK(c->tvec_off[b] >= 0 && c->xi_off[b] >= 0 && (!c->cov || c->cov_off[b] >= 0),
+                    "member %lld: negative offset into the test diagonal, the covariances or the normals", (long long)b);
+      TGP_ARG_CHECK(c->ndraw[b] == 0 || (c->xi && c->samples),
+                    "member %lld: %d draws are asked for, but xi_host or samples_host is null", (long long)b, c->ndraw[b]);
+    }
     if (p->progs) {
       TGP_ARG_CHECK(p->prog_off[b] >= 0 && p->prog_off[b + 1] >= p->prog_off[b],
                     "member %lld: negative prediction program extent", (long long)b);
@@ -688,6 +924,7 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
     std::map<std::pair<int64_t, int32_t>, int64_t> seen_t;  // (xt_off, m) -> first row in the launch's Xt
     std::vector<SmallRow> rows;
     std::vector<SmallPredRow> prows;
+    std::vector<SmallCondRow> crows;
     std::vector<KProg> lpks;
     int64_t b = b0;
     for (; b < nb; ++b) {
@@ -695,7 +932,23 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
       const bool fresh = seen.find(key) == seen.end();
       const int64_t xd = l.x_doubles + (fresh ? int64_t(n[b]) * d : 0), vd = l.vec_doubles + n[b];
       const int64_t ops = int64_t(prog_off[b + 1]) - prog_off[b0];
-      if (p) {  // the member's chunks, second program, test points (staged once per (offset, count)) and outputs
+      if (c) {  // one row per member: its second program, test points, test diagonal, normals and outputs
+        const int64_t mb = p->m[b], sb = c->ndraw[b];
+        const auto key_t = std::make_pair(p->xt_off[b], p->m[b]);
+        const bool fresh_t = mb > 0 && seen_t.find(key_t) == seen_t.end();
+        const int64_t np = l.pred_progs + has_pk[size_t(b)];
+        const int64_t td = l.xt_doubles + (fresh_t ? mb * d : 0), od = l.out_doubles + mb;
+        const int64_t cd = l.cov_doubles + mb * mb, zd = l.xi_doubles + sb * mb;
+        if (b > b0 && cond_launch_bytes(b - b0 + 1, np, xd, vd, td, od, cd, zd, c->cov != nullptr) > SMALL_STAGE_BYTES) break;
+        if (fresh) seen[key] = l.x_doubles / d;
+        if (fresh_t) seen_t[key_t] = l.xt_doubles / d;
+        crows.push_back(SmallCondRow{seen[key], l.vec_doubles, l.vec_doubles, mb > 0 ? seen_t[key_t] : 0, l.out_doubles,
+                                     l.cov_doubles, l.xi_doubles, n[b], d, int32_t(b - b0),
+                                     has_pk[size_t(b)] ? int32_t(l.pred_progs) : -1, int32_t(mb), int32_t(sb)});
+        if (has_pk[size_t(b)]) lpks.push_back(pks[size_t(b)]);
+        l.pred_progs = np, l.xt_doubles = td, l.out_doubles = od, l.cov_doubles = cd, l.xi_doubles = zd;
+        l.max_n = std::max<int64_t>(l.max_n, n[b] + mb);
+      } else if (p) {  // the member's chunks, second program, test points (staged once per (offset, count)) and outputs
         const auto key_t = std::make_pair(p->xt_off[b], p->m[b]);
         const bool fresh_t = p->m[b] > 0 && seen_t.find(key_t) == seen_t.end();
         const int64_t nr = l.pred_rows + pred_chunks(p->m[b]), np = l.pred_progs + has_pk[size_t(b)];
@@ -720,17 +973,23 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
       rows.push_back(SmallRow{seen[key], l.vec_doubles, l.vec_doubles, 2 * (int64_t(prog_off[b]) - prog_off[b0]), n[b], d,
                               int32_t(b - b0), int32_t(g.want_dims && g.want_dims[b] ? 1 : 0)});
       l.x_doubles = xd, l.vec_doubles = vd, l.ops = ops;
-      l.max_n = std::max<int64_t>(l.max_n, n[b]);
+      if (!c) l.max_n = std::max<int64_t>(l.max_n, n[b]);
     }
     l.b1 = b;
     const int64_t cnt = b - b0;
     for (SmallPredRow& r : prows)  // the second programs follow the launch's cnt member programs
       if (r.pred_prog >= 0) r.pred_prog += int32_t(cnt);
-    const int64_t table = p ? l.pred_rows * int64_t(sizeof(SmallPredRow)) : cnt * int64_t(sizeof(SmallRow));
+    for (SmallCondRow& r : crows)
+      if (r.pred_prog >= 0) r.pred_prog += int32_t(cnt);
+    const int64_t table = c   ? cnt * int64_t(sizeof(SmallCondRow))
+                          : p ? l.pred_rows * int64_t(sizeof(SmallPredRow))
+                              : cnt * int64_t(sizeof(SmallRow));
     l.host.resize(size_t(table + (cnt + l.pred_progs) * int64_t(sizeof(KProg)) +
-                         (l.x_doubles + 2 * l.vec_doubles + l.xt_doubles) * 8));
+                         (l.x_doubles + 2 * l.vec_doubles + l.xt_doubles + (c ? l.out_doubles + l.xi_doubles : 0)) * 8));
     char* w = l.host.data();
-    if (p) {
+    if (c) {
+      std::memcpy(w, crows.data(), size_t(table));
+    } else if (p) {
       std::memcpy(w, prows.data(), size_t(table));
     } else {
       std::memcpy(w, rows.data(), size_t(table));
@@ -752,12 +1011,19 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
       const SmallRow& r = rows[size_t(m)];
       std::memcpy(nzs + r.noise_off, noise_host + vec_off[b0 + m], size_t(r.n) * 8);
       std::memcpy(rss + r.resid_off, resid_host + vec_off[b0 + m], size_t(r.n) * 8);
+      if (c) {  // the test diagonal and the normals follow the test points
+        const SmallCondRow& cr = crows[size_t(m)];
+        double* tds = xts + l.xt_doubles;
+        std::memcpy(tds + cr.tvec_off, c->tdiag + c->tvec_off[b0 + m], size_t(cr.m) * 8);
+        if (int64_t(cr.S) * cr.m > 0)
+          std::memcpy(tds + l.out_doubles + cr.xi_off, c->xi + c->xi_off[b0 + m], size_t(int64_t(cr.S) * cr.m) * 8);
+      }
     }
     launches.push_back(std::move(l));
     b0 = b;
   }
   // one host join, on every path: the host buffers above are read by the copies that were enqueued
-  const int status = small_enqueue(ctx, launches, d, prog_off, info_host, out_host, g, p);
+  const int status = small_enqueue(ctx, launches, d, prog_off, info_host, out_host, g, p, c);
   const hipError_t joined = hipStreamSynchronize(ctx->stream);
   TGP_TRY(status);
   TGP_HIP_TRY(joined);
@@ -765,6 +1031,19 @@ int small_call(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* pr
   for (const SmallLaunch& l : launches) {
     if (l.back.empty()) continue;
     int64_t at = 0;
+    if (c) {  // means | covariances | samples go to the caller's offsets
+      const double* covs = l.back.data() + l.out_doubles;
+      const double* smp = covs + (c->cov ? l.cov_doubles : 0);
+      int64_t cat = 0, sat = 0;
+      for (int64_t b = l.b0; b < l.b1; ++b) {
+        const int64_t mb = p->m[b], sm = int64_t(c->ndraw[b]) * mb;
+        std::memcpy(p->mean + p->out_off[b], l.back.data() + at, size_t(mb) * 8);
+        if (c->cov) std::memcpy(c->cov + c->cov_off[b], covs + cat, size_t(mb * mb) * 8);
+        if (sm > 0) std::memcpy(c->samples + c->xi_off[b], smp + sat, size_t(sm) * 8);
+        at += mb, cat += mb * mb, sat += sm;
+      }
+      continue;
+    }
     if (p) {  // the predictions go to the caller's offsets
       for (int64_t b = l.b0; b < l.b1; at += p->m[b], ++b) {
         std::memcpy(p->mean + p->out_off[b], l.back.data() + at, size_t(p->m[b]) * 8);
@@ -830,4 +1109,36 @@ extern "C" int tgp_small_predict(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs,
   p.var = var_host;
   return small_call(ctx, nb, progs, prog_off, x_off, n, d, X_host, x_rows, vec_off, noise_host, resid_host, info_host,
                     out_host, SmallGradOut{}, &p);
+}
+
+extern "C" int tgp_small_condition(tgp_ctx* ctx, int32_t nb, const tgp_kop* progs, const int32_t* prog_off,
+                                   const int64_t* x_off, const int32_t* n, int32_t d, const double* X_host,
+                                   int64_t x_rows, const int64_t* vec_off, const double* noise_host,
+                                   const double* resid_host, const double* Xt_host, int64_t xt_rows,
+                                   const int64_t* xt_off, const int32_t* m, const tgp_kop* pred_progs,
+                                   const int32_t* pred_prog_off, const double* test_diag_host, const int64_t* tvec_off,
+                                   const int64_t* mean_off, double* mean_host, const int64_t* cov_off, double* cov_host,
+                                   const int32_t* ndraw, const double* xi_host, const int64_t* xi_off,
+                                   double* samples_host, int32_t* info_host, int32_t* cond_info_host, double* out_host) {
+  SmallPredIn p;
+  p.Xt = Xt_host;
+  p.xt_rows = xt_rows;
+  p.xt_off = xt_off;
+  p.m = m;
+  p.progs = pred_progs;
+  p.prog_off = pred_prog_off;
+  p.out_off = mean_off;
+  p.mean = mean_host;
+  SmallCondIn c;
+  c.tdiag = test_diag_host;
+  c.tvec_off = tvec_off;
+  c.cov_off = cov_off;
+  c.cov = cov_host;
+  c.ndraw = ndraw;
+  c.xi = xi_host;
+  c.xi_off = xi_off;
+  c.samples = samples_host;
+  c.cond_info = cond_info_host;
+  return small_call(ctx, nb, progs, prog_off, x_off, n, d, X_host, x_rows, vec_off, noise_host, resid_host, info_host,
+                    out_host, SmallGradOut{}, &p, &c);
 }

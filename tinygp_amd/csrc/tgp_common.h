@@ -249,6 +249,7 @@ struct tgp_ctx {
   bool small_lds_raised = false;  // small.hip: the one-workgroup kernel's dynamic-LDS limit has been raised on this device
   bool small_grad_lds_raised = false;  // the same for small.hip's gradient kernel
   bool small_pred_lds_raised = false;  // the same for small.hip's prediction kernel
+  bool small_cond_lds_raised = false;  // the same for small.hip's conditioning kernel
   size_t work_bytes = 0;
   // profiling (option "profile"): event pairs around trailing-update launches
   std::vector<hipEvent_t> ev_pool;

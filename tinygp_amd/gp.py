@@ -255,6 +255,64 @@ class GaussianProcess:
             return mu
         return mu, np.asarray(var + _default_diag(self.mean), dtype=self.dtype)
 
+    def _condition_batch(self, y, kernels, X_test, diags, means, diag, include_mean, xi, return_cov):
+        """``(means, covariances or None, draws (B, R, M) or None)`` of B models at one set of test points, the mean
+        function and the default jitter added: the body of :meth:`condition_batch` and
+        :meth:`sample_conditional_batch`."""
+        fused = getattr(self.solver, "condition_batch", None)
+        if fused is None:
+            raise NotImplementedError(f"{type(self.solver).__name__} has no condition_batch: batches of joint "
+                                      "posteriors are evaluated by DirectSolver (the dense path); a kernels.quasisep "
+                                      "model draws through QuasisepSolver's sample_conditional")
+        kernels = list(kernels)
+        nb = len(kernels)
+        resid, noise = self._batch_inputs(y, nb, diags, means)
+        tau = _default_diag(self.mean) if diag is None else diag
+        _, mu, cov, draws = fused(kernels, resid, X_test, noise, test_diag=tau, xi=xi, return_cov=return_cov)
+        if include_mean:
+            shift = None
+            if means is None:
+                shift = (self.loc if X_test is None else
+                         _eval_mean(self.mean_function, X_test, _device.num_points(X_test), self.dtype))
+            elif np.ndim(means) == 1:
+                shift = np.asarray(means, dtype=self.dtype)[:, None]
+            if shift is not None:
+                mu = mu + shift
+                if draws is not None:  # (B, R, M): a member's constant, or the mean function at the M points
+                    draws = draws + (shift[:, None] if np.ndim(shift) == 2 else shift)
+        return (np.asarray(mu, dtype=self.dtype), None if cov is None else np.asarray(cov, dtype=self.dtype),
+                None if draws is None else np.asarray(draws, dtype=self.dtype))
+
+    def condition_batch(self, y, kernels, X_test=None, *, diags=None, means=None, diag=None, include_mean: bool = True):
+        """:meth:`condition` of ``y`` under B models that share this GP's coordinates, at one shared set of test
+        points, evaluated together: ``(means (B, M), covariances (B, M, M))``; row b is the ``gp.loc`` and
+        ``gp.covariance`` of ``GaussianProcess(kernels[b], X, diag=diags[b], mean=means[b]).condition(y, X_test,
+        diag=diag)``, held to the project's posterior bar against that call.  ``kernels``, ``diags``, ``means`` and
+        ``include_mean`` as in :meth:`predict_batch`; ``diag``: what is added to the diagonal of every covariance, a
+        scalar or (M,), ``None`` for the default jitter of :meth:`condition`.  Needs a solver with ``condition_batch``
+        (:class:`tinygp_amd.solvers.DirectSolver`: with N + M up to ``TGP_SMALL_MAX_N`` a workgroup conditions a whole
+        member in LDS, ``csrc/small.hip``; above it the members are evaluated one by one).  Data sets with points of
+        their own: :func:`tinygp_amd.condition_datasets`."""
+        mu, cov, _ = self._condition_batch(y, kernels, X_test, diags, means, diag, include_mean, None, True)
+        return mu, cov
+
+    def sample_conditional_batch(self, y, kernels, X_test=None, *, key, shape=None, diags=None, means=None, diag=None,
+                                 include_mean: bool = True):
+        """Joint posterior draws under B models that share this GP's coordinates, at one shared set of test points,
+        evaluated together: what ``condition(y, X_test, diag=diag).gp.sample(key, shape)`` draws from for every member
+        (Thompson sampling over a candidate set under every member of an ensemble).  Arguments as in
+        :meth:`condition_batch`; ``key``: an int seed or a ``numpy.random.Generator``, as in :meth:`sample` -- the
+        standard normals (B, R, M), R the product of ``shape``, are drawn from it.  Returns (B,) + shape + (M,); no
+        covariance crosses the bus.  A member whose covariance does not factor has NaN draws.  Needs a solver with
+        ``condition_batch``.  Data sets with points of their own: :func:`tinygp_amd.sample_conditional_datasets`."""
+        rng = key if isinstance(key, np.random.Generator) else np.random.default_rng(key)
+        shape = () if shape is None else tuple(shape)
+        kernels = list(kernels)
+        M = self.num_data if X_test is None else _device.num_points(X_test)
+        xi = rng.standard_normal((len(kernels), int(np.prod(shape, dtype=np.int64)), M))
+        _, _, draws = self._condition_batch(y, kernels, X_test, diags, means, diag, include_mean, xi, False)
+        return draws.reshape((len(kernels),) + shape + (M,))
+
     def _batch_inputs(self, y, nb, diags, means):
         """``(resid, noise)`` of a batch of nb models: the arguments of the solver's batch methods."""
         n = self.num_data

@@ -528,6 +528,100 @@ class DirectSolver(Solver):
         out = (values, mu, var)
         return out + (info,) if return_info else out
 
+    def condition_batch(self, kernels, resid, X_test=None, noise=None, *, test_diag=None, xi=None,
+                        return_cov: bool = True, return_info: bool = False):
+        """B models over this solver's coordinates conditioned on their residuals, with the JOINT posterior at ONE set
+        of test points, evaluated together on the device (``tgp_small_condition``, ``csrc/small.hip``: the test points
+        ride as further columns of the member's matrix through the one elimination in LDS).  ``kernels``, ``resid``,
+        ``noise`` and ``X_test`` as in :meth:`predict_batch`.  ``test_diag``: ``None`` (nothing is added: the raw Schur
+        complement, as :meth:`predict_batch` returns raw variances), a scalar, (M,) or (B, M), added to the diagonal of
+        every covariance.  ``xi``: ``None``, or standard normals (R, M) shared or (B, R, M): R joint draws per member.
+
+        Returns ``(values (B,), means (B, M), covariances (B, M, M) or None, samples (B, R, M) or None)``:
+        ``K(X_test, X) K^-1 r``, ``K(X_test, X_test) + diag(test_diag) - K(X_test, X) K^-1 K(X, X_test)`` -- what
+        :meth:`conditional_mean` and :meth:`condition` of a solver built with that member's kernel and noise give,
+        without mean function -- and ``mean + L xi_s`` with L the Cholesky factor of that covariance.  Without
+        ``return_cov`` no covariance crosses the bus.  With ``return_info``, ``(info, cond_info)`` follow:
+        ``cond_info[b]`` is 0 or the 1-based index of the first pivot of the covariance's factorisation that is not
+        > 0; that member's draws are then NaN.  A failed or non-finite member gives ``-inf`` and NaN everywhere.  fp32
+        inputs are computed in fp64 and returned as fp32.
+
+        The values have the bits of :meth:`log_probability_batch`.  The routing is that of :meth:`predict_batch` with
+        the cap on N + M, all members batched or none; otherwise every member is evaluated on a fresh single
+        :class:`DirectSolver` and its draws come from LAPACK on the host.  ``kernels.quasisep`` members raise
+        ``NotImplementedError``."""
+        from tinygp_amd.solvers import small
+
+        kernels = list(kernels)
+        nb = len(kernels)
+        Xt = self.X if X_test is None else X_test
+        M = _device.num_points(Xt)
+        small.reject_quasisep(kernels)
+
+        def rows(a, what):  # (N,) shared or (B, N) one per member -> (B, N)
+            a = np.asarray(a)
+            if a.shape not in ((self.n,), (nb, self.n)):
+                raise ValueError(f"{what} must have shape ({self.n},) or ({nb}, {self.n}); got {a.shape}")
+            return np.broadcast_to(a, (nb, self.n))
+
+        r = rows(resid, "resid")
+        d = None if noise is None else rows(noise, "noise")
+        tau = np.zeros(()) if test_diag is None else np.asarray(test_diag, dtype=self.dtype).astype(np.float64)
+        if tau.shape not in ((), (M,), (nb, M)):
+            raise ValueError(f"test_diag must be a scalar or have shape ({M},) or ({nb}, {M}); got {tau.shape}")
+        tau = np.broadcast_to(tau, (nb, M))
+        z = None
+        if xi is not None:
+            z = np.asarray(xi, dtype=np.float64)
+            if not ((z.ndim == 2 and z.shape[1] == M) or (z.ndim == 3 and z.shape[0] == nb and z.shape[2] == M)):
+                raise ValueError(f"xi must have shape (R, {M}) or ({nb}, R, {M}); got {z.shape}")
+            z = np.broadcast_to(z, (nb,) + z.shape[-2:])
+        R = 0 if z is None else z.shape[1]
+        values, info, cinfo = np.empty(nb), np.zeros(nb, dtype=np.int32), np.zeros(nb, dtype=np.int32)
+        mu = np.empty((nb, M))
+        cov = np.empty((nb, M, M)) if return_cov else None
+        smp = np.empty((nb, R, M)) if z is not None else None
+        lowered = [small.lower_member(k, self.X) for k in kernels]
+        tests = None
+        if nb and self.n + M <= small.MAX_N and small.batch_route(
+                self.n, d is not None or isinstance(self.noise, Diagonal), lowered):
+            tests = [small.lower_test(k, None, self.X, X_test, low) for k, low in zip(kernels, lowered)]
+            if any(t is None for t in tests):
+                tests = None
+        if tests is not None:
+            members = [(low[0], low[1], self._noise_diag if d is None else d[b], r[b]) for b, low in enumerate(lowered)]
+            pc = small.pack_condition(members, [t[0] for t in tests], list(tau), None,
+                                      None if z is None else list(z))
+            values, info, cinfo, flat, flat_cov, flat_smp = small.run_packed_condition(self._ctx, pc, return_cov)
+            mu = flat.reshape(nb, M)
+            cov = flat_cov.reshape(nb, M, M) if return_cov else None
+            smp = flat_smp.reshape(nb, R, M) if z is not None else None
+        else:  # the single calls, member by member: the interface does not change with N
+            for b, kernel in enumerate(kernels):
+                nz = self.noise if d is None else Diagonal(diag=np.asarray(d[b], dtype=self.dtype))
+                single = DirectSolver(kernel, self.X, nz, ctx=self._ctx)
+                try:
+                    alpha, values[b] = single.alpha(np.asarray(r[b], dtype=self.dtype))
+                    info[b] = single.info
+                    mu[b] = single.conditional_mean(kernel, Xt, alpha)
+                    if return_cov or z is not None:
+                        c = single.condition(kernel, X_test, Diagonal(diag=np.asarray(tau[b], dtype=self.dtype)))
+                        if return_cov:
+                            cov[b] = c
+                        if z is not None:
+                            smp[b], cinfo[b] = small.host_draws(mu[b], c, z[b])
+                finally:
+                    single.close()
+        bad = (info != 0) | ~np.isfinite(values)
+        values = np.where(bad, -np.inf, values).astype(self.dtype, copy=False)
+        mu = np.where(bad[:, None], np.nan, mu).astype(self.dtype, copy=False)
+        if return_cov:
+            cov = np.where(bad[:, None, None], np.nan, cov).astype(self.dtype, copy=False)
+        if z is not None:
+            smp = np.where(bad[:, None, None], np.nan, smp).astype(self.dtype, copy=False)
+        out = (values, mu, cov, smp)
+        return out + (info, cinfo) if return_info else out
+
     def log_probability_and_grad(self, resid):
         """``(log_probability, grads)`` with ``grads = {"kernel": [...], "noise_diag": (N,),
         "mean": (N,), "transform": ...}``: derivatives with respect to ``kernel.parameters()`` (same order), to

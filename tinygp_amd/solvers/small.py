@@ -1,5 +1,5 @@
 """Batches of small dense GPs in one launch (``tgp_small_logprob``, ``tgp_small_logprob_grad``, ``tgp_small_predict``,
-``csrc/small.hip``): one
+``tgp_small_condition``, ``csrc/small.hip``): one
 workgroup owns a whole member -- it assembles ``K + diag(noise)`` in LDS, factors it there, solves and reduces, and for
 the gradient inverts in place and weighs every derivative -- where the single dense path pays a handle, uploads, a
 launch chain and a host join per evaluation.
@@ -12,7 +12,9 @@ with points of their own.  ``DirectSolver.log_probability_batch`` is built on th
 (:func:`member_gradient`), :func:`log_probability_and_grad_datasets` and ``DirectSolver.log_probability_and_grad_batch``.  The prediction's side:
 :func:`pack_predict` (test points, second programs and output offsets beside the members), :func:`predict_rows` and
 :func:`predict_launch_bytes` (the table rows and the staging bytes the C side makes of them),
-:func:`run_packed_predict`, :func:`predict_datasets` and ``DirectSolver.predict_batch``.
+:func:`run_packed_predict`, :func:`predict_datasets` and ``DirectSolver.predict_batch``.  The joint posterior's side
+(``tgp_small_condition``): :func:`pack_condition`, :func:`condition_launch_bytes`, :func:`run_packed_condition`,
+:func:`condition_datasets`, :func:`sample_conditional_datasets` and ``DirectSolver.condition_batch``.
 """
 
 from __future__ import annotations
@@ -26,7 +28,9 @@ from tinygp_amd import _device, _ffi
 __all__ = ["MAX_N", "KOP_DTYPE", "Packed", "lower_member", "pack_members", "batched_route", "batch_route", "run_packed",
            "run_packed_grad", "member_gradient", "failed_gradient", "log_probability_datasets",
            "log_probability_and_grad_datasets", "PRED_CHUNK", "PackedPredict", "pack_predict", "predict_rows",
-           "predict_launch_bytes", "run_packed_predict", "predict_datasets"]
+           "predict_launch_bytes", "run_packed_predict", "predict_datasets", "PackedCondition", "condition_route",
+           "pack_condition", "condition_launch_bytes", "run_packed_condition", "host_draws", "condition_datasets",
+           "sample_conditional_datasets"]
 
 MAX_N = _ffi.SMALL_MAX_N  # TGP_SMALL_MAX_N: the largest member a workgroup holds in LDS
 PRED_CHUNK = _ffi.SMALL_PRED_CHUNK  # TGP_SMALL_PRED_CHUNK: the test points one workgroup takes
@@ -516,6 +520,32 @@ def jitter(dtype):
     return np.sqrt(np.finfo(np.dtype(dtype)).eps)
 
 
+def added_means(members, raw_means, X_tests, test_means, include_mean):
+    """What ``include_mean`` adds to member b's predictions, a list of (m_b,) float64 arrays: a scalar ``means[b]``
+    itself; for a vector ``means[b]`` -- it enters the residual only -- ``test_means[b]``, a scalar or (m_b,), which
+    ``include_mean`` then requires.  A ``ValueError`` names the data set."""
+    added = [None] * len(members)
+    for b, (kernel, X, y, diag, mean) in enumerate(members):
+        m = len(y) if X_tests[b] is None else _device.num_points(X_tests[b])
+        if mean is None or np.ndim(raw_means[b]) == 0:
+            if test_means[b] is not None:
+                raise ValueError(f"test_means[{b}] is given, but means[{b}] of data set {b} is not a vector: a scalar "
+                                 "mean is added to the predictions by itself")
+            added[b] = np.zeros(m) if mean is None else np.full(m, np.asarray(raw_means[b], dtype=np.float64))
+        else:
+            if test_means[b] is None:
+                if include_mean:
+                    raise ValueError(f"means[{b}] of data set {b} is a vector: the mean at its test points must be given "
+                                     f"as test_means[{b}] (a scalar or ({m},)), or include_mean=False")
+                added[b] = np.zeros(m)
+            else:
+                t = np.asarray(test_means[b], dtype=np.float64)
+                if t.shape not in ((), (m,)):
+                    raise ValueError(f"test_means[{b}] must have shape ({m},) or be a scalar for data set {b}; got {t.shape}")
+                added[b] = np.broadcast_to(t, (m,))
+    return added
+
+
 def predict_datasets(kernels, Xs, ys, X_tests, *, diags, means=None, test_means=None, predict_kernels=None,
                      return_var: bool = True, include_mean: bool = True, return_info: bool = False, ctx=None):
     """Condition B dense GPs on their data and predict at test points, each with points, length, noise and test points
@@ -558,25 +588,7 @@ def predict_datasets(kernels, Xs, ys, X_tests, *, diags, means=None, test_means=
     reject_quasisep(k for k in predict_kernels if k is not None)
     values, info = np.empty(nb), np.zeros(nb, dtype=np.int32)
     out_means, out_vars = [None] * nb, [None] * nb
-    added = [None] * nb  # what include_mean adds to member b's predictions
-    for b, (kernel, X, y, diag, mean) in enumerate(members):
-        m = len(y) if X_tests[b] is None else _device.num_points(X_tests[b])
-        if mean is None or np.ndim(raw_means[b]) == 0:
-            if test_means[b] is not None:
-                raise ValueError(f"test_means[{b}] is given, but means[{b}] of data set {b} is not a vector: a scalar "
-                                 "mean is added to the predictions by itself")
-            added[b] = np.zeros(m) if mean is None else np.full(m, np.asarray(raw_means[b], dtype=np.float64))
-        else:
-            if test_means[b] is None:
-                if include_mean:
-                    raise ValueError(f"means[{b}] of data set {b} is a vector: the mean at its test points must be given "
-                                     f"as test_means[{b}] (a scalar or ({m},)), or include_mean=False")
-                added[b] = np.zeros(m)
-            else:
-                t = np.asarray(test_means[b], dtype=np.float64)
-                if t.shape not in ((), (m,)):
-                    raise ValueError(f"test_means[{b}] must have shape ({m},) or be a scalar for data set {b}; got {t.shape}")
-                added[b] = np.broadcast_to(t, (m,))
+    added = added_means(members, raw_means, X_tests, test_means, include_mean)
     batched, tests, seconds, where = [], [], [], []
     for b, (kernel, X, y, diag, mean) in enumerate(members):
         lowered = lower_member(kernel, X)
@@ -630,6 +642,300 @@ def _single_predict(kernel, X, y, diag, mean, X_test, predict_kernel, return_var
         return float(value), int(gp.solver.info), np.asarray(cond.loc), var
     finally:
         gp.solver.close()
+
+
+# ---- conditional covariance and joint draws ----------------------------------------------------------------------------
+class PackedCondition(NamedTuple):
+    """The host arrays of one ``tgp_small_condition`` call beside those of ``tgp_small_predict`` (``pp.out_off`` is where
+    a member's means go, and its test diagonal comes from)."""
+
+    pp: PackedPredict
+    tdiag: np.ndarray    # (sum m,) float64, member b's at pp.out_off[b]
+    cov_off: np.ndarray  # (B,) int64, into the covariances: m_0^2 + .. + m_{b-1}^2
+    ndraw: np.ndarray    # (B,) int32, the draws S_b
+    xi: np.ndarray       # (sum S m,) float64, member b's (S_b, m_b) draw-major at xi_off[b]
+    xi_off: np.ndarray   # (B,) int64, into the normals and the samples
+
+
+def condition_route(n: int, m: int, lowered) -> bool:
+    """Whether a member of ``n`` points and ``m`` test points goes into the conditioning launches: the test points ride
+    as columns of the member's matrix, so the cap of :func:`batched_route` holds for n + m."""
+    return batched_route(n, lowered) and n + m <= MAX_N
+
+
+def pack_condition(members, tests, tdiags, pred_progs=None, xis=None, labels=None) -> PackedCondition:
+    """:func:`pack_predict` of ``members`` and ``tests`` plus ``tdiags[b]``, the (m_b,) values added to the diagonal
+    of member b's conditional covariance, and ``xis[b]``, ``None`` or its (S_b, m_b) standard normals.  A
+    ``ValueError`` names the member whose vectors do not fit or whose n + m is above the cap."""
+    pp = pack_predict(members, tests, pred_progs, labels)
+    nb = len(pp.m)
+    labels = [f"member {b}" for b in range(nb)] if labels is None else list(labels)
+    tdiags = list(tdiags)
+    xis = [None] * nb if xis is None else list(xis)
+    if len(tdiags) != nb or len(xis) != nb:
+        raise ValueError(f"tdiags and xis must hold one entry per member ({nb}); got {len(tdiags)} and {len(xis)}")
+    tds, zs, ndraw, xi_off = [], [], [], []
+    total = 0
+    for b in range(nb):
+        n, m = int(pp.packed.n[b]), int(pp.m[b])
+        if n + m > MAX_N:
+            raise ValueError(f"{labels[b]}: the conditioning launches hold at most {MAX_N} data and test points per "
+                             f"member (got {n} + {m})")
+        t = np.asarray(tdiags[b], dtype=np.float64)
+        if t.shape != (m,):
+            raise ValueError(f"{labels[b]}: its test diagonal must have shape ({m},); got {t.shape}")
+        tds.append(t)
+        z = np.empty((0, m)) if xis[b] is None else np.asarray(xis[b], dtype=np.float64)
+        if z.ndim != 2 or z.shape[1] != m:
+            raise ValueError(f"{labels[b]}: its normals must have shape (S, {m}); got {z.shape}")
+        ndraw.append(z.shape[0])
+        xi_off.append(total)
+        zs.append(z.reshape(-1))
+        total += z.size
+    cov_off = np.concatenate([[0], np.cumsum(pp.m.astype(np.int64) ** 2)[:-1]]).astype(np.int64)
+    return PackedCondition(pp, np.concatenate(tds), cov_off, np.array(ndraw, dtype=np.int32), np.concatenate(zs),
+                           np.array(xi_off, dtype=np.int64))
+
+
+def condition_launch_bytes(pc: PackedCondition, cov: bool = True) -> int:
+    """The staging bytes of ``pc`` as ONE launch (``cond_launch_bytes`` of small.hip): table rows of 80 bytes, one per
+    member, the programs (``KPROG_BYTES`` each) with the second ones behind the members', coordinates, noise, residual,
+    test points, test diagonal, normals, values, info, cond_info, means, covariances (when asked) and samples.  The C
+    side ends a launch before the member that would take this past ``STAGE_BYTES``."""
+    pp = pc.pp
+    nb, d = len(pp.packed.n), pp.packed.d
+    second = 0 if pp.pred_prog_off is None else int(np.count_nonzero(np.diff(pp.pred_prog_off)))
+    x_doubles = sum(n * d for _, n in {(int(o), int(n)) for o, n in zip(pp.packed.x_off, pp.packed.n)})
+    xt_doubles = sum(m * d for _, m in {(int(o), int(m)) for o, m in zip(pp.xt_off, pp.m) if m > 0})
+    vec, outs = int(pp.packed.n.sum()), int(pp.m.sum())
+    covs = int((pp.m.astype(np.int64) ** 2).sum()) if cov else 0
+    draws = int((pc.ndraw.astype(np.int64) * pp.m).sum())
+    return (nb * 80 + (nb + second) * _ffi.KPROG_BYTES + (x_doubles + 2 * vec + xt_doubles + 2 * outs + covs + 2 * draws) * 8
+            + nb * 8 + 2 * (-(-nb * 4 // 8) * 8))
+
+
+def run_packed_condition(ctx, pc: PackedCondition, return_cov: bool = True):
+    """One ``tgp_small_condition`` call: ``(values (B,), info (B,) int32, cond_info (B,) int32, means (sum m,),
+    covariances (sum m^2,) or None, samples (sum S m,))``, float64; member b's sit at ``pc.pp.out_off[b]``,
+    ``pc.cov_off[b]`` and ``pc.xi_off[b]``.  Without ``return_cov`` no covariance is written or copied.  A member with
+    ``info != 0`` has NaN everywhere, one with ``cond_info != 0`` NaN draws only."""
+    pp, packed = pc.pp, pc.pp.packed
+    nb, total = len(packed.n), int(pp.m.sum())
+    info, cinfo, out = np.zeros(nb, dtype=np.int32), np.zeros(nb, dtype=np.int32), np.empty(nb)
+    mean = np.empty(max(total, 1))
+    ncov = int((pp.m.astype(np.int64) ** 2).sum())
+    cov = np.empty(max(ncov, 1)) if return_cov else None
+    draws = bool(pc.ndraw.any())
+    xi = np.ascontiguousarray(pc.xi) if pc.xi.size else np.zeros(1)
+    samples = np.empty(max(pc.xi.size, 1)) if draws else None
+    tdiag = pc.tdiag if pc.tdiag.size else np.zeros(1)
+    _ffi.check(_ffi.lib().tgp_small_condition(
+        ctx.handle, nb, _ffi.ptr(packed.progs), packed.prog_off.ctypes.data_as(_ffi._pi32),
+        packed.x_off.ctypes.data_as(_ffi._pi64), packed.n.ctypes.data_as(_ffi._pi32), packed.d, _ffi.ptr(packed.X),
+        packed.X.shape[0], packed.vec_off.ctypes.data_as(_ffi._pi64), _ffi.ptr(packed.noise), _ffi.ptr(packed.resid),
+        _ffi.ptr(pp.Xt) if pp.Xt.shape[0] else None, pp.Xt.shape[0], pp.xt_off.ctypes.data_as(_ffi._pi64),
+        pp.m.ctypes.data_as(_ffi._pi32), None if pp.pred_progs is None else _ffi.ptr(pp.pred_progs),
+        None if pp.pred_prog_off is None else pp.pred_prog_off.ctypes.data_as(_ffi._pi32), _ffi.ptr(tdiag),
+        pp.out_off.ctypes.data_as(_ffi._pi64), pp.out_off.ctypes.data_as(_ffi._pi64), mean.ctypes.data_as(_ffi._pdbl),
+        pc.cov_off.ctypes.data_as(_ffi._pi64) if return_cov else None,
+        cov.ctypes.data_as(_ffi._pdbl) if return_cov else None, pc.ndraw.ctypes.data_as(_ffi._pi32),
+        _ffi.ptr(xi) if draws else None, pc.xi_off.ctypes.data_as(_ffi._pi64),
+        samples.ctypes.data_as(_ffi._pdbl) if draws else None, info.ctypes.data_as(_ffi._pi32),
+        cinfo.ctypes.data_as(_ffi._pi32), out.ctypes.data_as(_ffi._pdbl)), "tgp_small_condition")
+    return (out, info, cinfo, mean[:total], None if cov is None else cov[:ncov],
+            samples[:pc.xi.size] if draws else np.empty(0))
+
+
+def host_draws(loc, cov, xi):
+    """``(loc + L xi_s for every row s of xi (S, m), cond_info)`` with L from LAPACK's ``dpotrf`` of ``cov`` on the
+    host: the draws of a member on the single path.  ``cond_info``: 0, or the 1-based order of the first leading minor
+    that is not positive definite; the draws are then NaN."""
+    from scipy.linalg import lapack
+
+    xi = np.asarray(xi, dtype=np.float64)
+    if xi.shape[1] == 0 or xi.shape[0] == 0:
+        return np.empty(xi.shape), 0
+    cov = np.asarray(cov, dtype=np.float64)
+    if not np.all(np.isfinite(cov)):
+        return np.full(xi.shape, np.nan), 0
+    L, bad = lapack.dpotrf(cov, lower=1, clean=1)
+    if bad != 0:
+        return np.full(xi.shape, np.nan), int(bad)
+    return np.asarray(loc, dtype=np.float64) + xi @ L.T, 0
+
+
+def _single_condition(kernel, X, y, diag, mean, X_test, test_diag, predict_kernel, xi, ctx):
+    """One data set on the single dense path: ``GaussianProcess(kernel, X, diag=diag).condition(y - mean, X_test,
+    diag=test_diag, kernel=predict_kernel)`` itself -- the mean enters through the residual, the caller adds it -- its
+    solver closed behind it: ``(value, info, cond_info, means, covariance, draws (S, m) or None)``; the draws are
+    :func:`host_draws` of that call's own mean and covariance."""
+    from tinygp_amd.gp import GaussianProcess
+    from tinygp_amd.solvers.direct import DirectSolver
+
+    kwargs = {} if ctx is None else {"ctx": ctx}
+    gp = GaussianProcess(kernel, X, diag=diag, solver=DirectSolver, **({} if mean is None else {"mean_value": mean}),
+                         **kwargs)
+    try:
+        value, cond = gp.condition(y, X if X_test is None else X_test, diag=test_diag, kernel=predict_kernel,
+                                   include_mean=False)
+        loc = np.asarray(cond.loc)
+        cov = np.asarray(cond.covariance) if len(loc) else np.empty((0, 0), dtype=loc.dtype)
+        draws, cinfo = (None, 0) if xi is None else host_draws(loc, cov, xi)
+        return float(value), int(gp.solver.info), cinfo, loc, cov, draws
+    finally:
+        gp.solver.close()
+
+
+def _condition_sets(kernels, Xs, ys, X_tests, diags, means, test_means, test_diags, predict_kernels, include_mean,
+                    xis, want_cov, ctx):
+    """The body of :func:`condition_datasets` and :func:`sample_conditional_datasets`: ``(values, info, cond_info,
+    means, covariances or None, draws or None)``; ``xis``: ``None`` or a callable ``(b, m_b) -> (S, m_b)`` asked
+    member by member in the caller's order."""
+    members = check_datasets(kernels, Xs, ys, diags, means)
+    nb = len(members)
+
+    def entries(values, what):
+        values = [None] * nb if values is None else list(values)
+        if len(values) != nb:
+            raise ValueError(f"{what} must hold one entry per data set ({nb}); got {len(values)}")
+        return values
+
+    X_tests, test_means = entries(X_tests, "X_tests"), entries(test_means, "test_means")
+    predict_kernels, raw_means = entries(predict_kernels, "predict_kernels"), entries(means, "means")
+    test_diags = entries(test_diags, "test_diags")
+    reject_quasisep(m[0] for m in members)
+    reject_quasisep(k for k in predict_kernels if k is not None)
+    added = added_means(members, raw_means, X_tests, test_means, include_mean)
+    taus, draws_in = [None] * nb, [None] * nb
+    for b, (kernel, X, y, diag, mean) in enumerate(members):
+        m = len(added[b])
+        t = np.asarray(jitter(y.dtype) if test_diags[b] is None else test_diags[b], dtype=np.float64)
+        if t.shape not in ((), (m,)):
+            raise ValueError(f"test_diags[{b}] must have shape ({m},) or be a scalar for data set {b}; got {t.shape}")
+        taus[b] = np.broadcast_to(t.astype(y.dtype).astype(np.float64), (m,))  # (rounded as condition(diag=) rounds it)
+        if xis is not None:
+            z = np.asarray(xis(b, m), dtype=np.float64)
+            if z.ndim != 2 or z.shape[1] != m:
+                raise ValueError(f"xi[{b}] must have shape (R, {m}) for data set {b}; got {z.shape}")
+            draws_in[b] = z
+    values, info, cinfo = np.empty(nb), np.zeros(nb, dtype=np.int32), np.zeros(nb, dtype=np.int32)
+    out_means, out_covs, out_draws = [None] * nb, [None] * nb, [None] * nb
+    batched, tests, seconds, where = [], [], [], []
+    for b, (kernel, X, y, diag, mean) in enumerate(members):
+        lowered = lower_member(kernel, X)
+        test = None
+        if condition_route(len(y), len(added[b]), lowered) and (not batched
+                                                               or lowered[1].shape[1] == batched[0][1].shape[1]):
+            test = lower_test(kernel, predict_kernels[b], X, X_tests[b], lowered)
+        if test is not None:
+            batched.append((lowered[0], lowered[1], diag, y if mean is None else y - mean))
+            tests.append(test[0])
+            seconds.append(test[1])
+            where.append(b)
+        else:
+            (values[b], info[b], cinfo[b], out_means[b], out_covs[b],
+             out_draws[b]) = _single_condition(kernel, X, y, diag, mean, X_tests[b], taus[b], predict_kernels[b],
+                                               draws_in[b], ctx)
+    if batched:
+        pc = pack_condition(batched, tests, [taus[b] for b in where], seconds, [draws_in[b] for b in where],
+                            labels=[f"data set {b}" for b in where])
+        vals, infos, cinfos, mu, cov, smp = run_packed_condition(_ffi.default_ctx() if ctx is None else ctx, pc,
+                                                                 want_cov)
+        for k, b in enumerate(where):
+            at, m, s = int(pc.pp.out_off[k]), int(pc.pp.m[k]), int(pc.ndraw[k])
+            values[b], info[b], cinfo[b] = vals[k], infos[k], cinfos[k]
+            out_means[b] = mu[at:at + m]
+            if want_cov:
+                out_covs[b] = cov[int(pc.cov_off[k]):int(pc.cov_off[k]) + m * m].reshape(m, m)
+            if xis is not None:
+                out_draws[b] = smp[int(pc.xi_off[k]):int(pc.xi_off[k]) + s * m].reshape(s, m)
+    bad = (info != 0) | ~np.isfinite(values)
+    values[bad] = -np.inf
+    for b in range(nb):
+        dt = members[b][2].dtype
+        shift = added[b] if include_mean else 0.0
+        mu = np.asarray(out_means[b], dtype=np.float64) + shift
+        out_means[b] = np.full(len(mu), np.nan, dtype=dt) if bad[b] else mu.astype(dt)
+        if want_cov:
+            c = np.asarray(out_covs[b], dtype=np.float64)
+            out_covs[b] = np.full(c.shape, np.nan, dtype=dt) if bad[b] else c.astype(dt)
+        if xis is not None:
+            f = np.asarray(out_draws[b], dtype=np.float64) + shift
+            out_draws[b] = np.full(f.shape, np.nan, dtype=dt) if bad[b] else f.astype(dt)
+    return values, info, cinfo, out_means, (out_covs if want_cov else None), (out_draws if xis is not None else None)
+
+
+def condition_datasets(kernels, Xs, ys, X_tests, *, diags, means=None, test_means=None, test_diags=None,
+                       predict_kernels=None, include_mean: bool = True, return_info: bool = False, ctx=None):
+    """Condition B dense GPs on their data and return the JOINT posterior at test points, each with points, length,
+    noise and test points of its own, in one call (the reference's ``jax.vmap`` over the function that builds the GP
+    and reads ``condition(y, X_test).gp``): batch acquisition in Bayesian optimisation, restarts compared on held-out
+    points with their correlations.
+
+    Arguments as in :func:`predict_datasets`, and ``test_diags[b]``: ``None``, a scalar or (m_b,), what is added to
+    the diagonal of the covariance; ``None`` is the default jitter of ``condition``, :func:`jitter` of the data set's
+    dtype.
+
+    Returns ``(values (B,) float64, means, covariances)``: lists of B arrays (m_b,) and (m_b, m_b) in the dtype of
+    that data set's coordinates, each covariance exactly symmetric; with ``return_info`` the B ``info`` values come
+    fourth.  A failed or non-finite member gives ``-inf`` and NaN everywhere.
+
+    Member b is ``GaussianProcess(kernels[b], Xs[b], diag=diags[b], mean=means[b]).condition(ys[b], X_tests[b],
+    diag=test_diags[b], kernel=predict_kernels[b])``: its ``log_probability``, ``gp.loc`` and ``gp.covariance``, held
+    to the project's posterior bar against that call.  Data sets whose data and test points TOGETHER number at most
+    ``TGP_SMALL_MAX_N`` and that the device can lower run in the batched launches (``tgp_small_condition``: one
+    workgroup per data set, fp64, the test points as further columns of the one elimination; the value has the bits of
+    :func:`log_probability_datasets`, and a member's outputs depend on its own data alone).  Larger ones, any the
+    device cannot lower (``kernels.Custom``, more than 16 dimensions, pytree inputs) and a ``predict_kernels[b]`` under
+    another input transform than the model's are that very call, one by one.  ``kernels.quasisep`` models belong to
+    ``QuasisepSolver``."""
+    values, info, _, mu, cov, _ = _condition_sets(kernels, Xs, ys, X_tests, diags, means, test_means, test_diags,
+                                                  predict_kernels, include_mean, None, True, ctx)
+    return (values, mu, cov, info) if return_info else (values, mu, cov)
+
+
+def sample_conditional_datasets(kernels, Xs, ys, X_tests, *, key, shape=None, diags, means=None, test_means=None,
+                                test_diags=None, predict_kernels=None, include_mean: bool = True, xi=None,
+                                return_info: bool = False, ctx=None):
+    """Joint posterior draws of B dense GPs at test points of their own, in one call: what
+    ``condition(ys[b], X_tests[b], diag=test_diags[b]).gp.sample(key, shape)`` draws from for every member (Thompson
+    sampling over a candidate set, posterior draws of many short light curves after a fit).  Arguments as in
+    :func:`condition_datasets`.
+
+    ``key``: an int seed or a ``numpy.random.Generator``, as in ``GaussianProcess.sample``; member b's normals are
+    ``rng.standard_normal((R, m_b))`` with R the product of ``shape``, drawn in member order.  ``xi``: a list of
+    (R, m_b) arrays that replaces the draw (``key`` is then not used).  Returns ``(values (B,), samples)`` with
+    ``samples[b]`` of shape ``shape + (m_b,)`` in that data set's dtype: ``mean + L xi_s`` with L the Cholesky factor
+    of the conditional covariance, ``test_diags[b]`` included.  With ``return_info``, ``(info, cond_info)`` follow:
+    ``cond_info[b]`` is 0, or the 1-based index of the first pivot of that factorisation that is not > 0 -- member b's
+    draws are then NaN, its value stands.  A failed data block (``info != 0``) gives ``-inf`` and NaN draws.
+
+    The routing is that of :func:`condition_datasets`; no covariance crosses the bus.  On the single path the draws are
+    that call's ``gp.loc + L xi_s`` with L from LAPACK on the host (:func:`host_draws`).  A draw's bits depend on its
+    data set and its own normals alone."""
+    shape = () if shape is None else tuple(shape)
+    R = int(np.prod(shape, dtype=np.int64))
+    if xi is None:
+        rng = key if isinstance(key, np.random.Generator) else np.random.default_rng(key)
+
+        def normals(b, m):
+            return rng.standard_normal((R, m))
+    else:
+        xi = list(xi)
+
+        def normals(b, m):
+            if b >= len(xi):
+                raise ValueError(f"xi must hold one entry per data set; got {len(xi)}")
+            z = np.asarray(xi[b])
+            if z.shape != (R, m):
+                raise ValueError(f"xi[{b}] must have shape ({R}, {m}) for data set {b}: R is the product of shape "
+                                 f"{shape}; got {z.shape}")
+            return z
+
+    values, info, cinfo, _, _, draws = _condition_sets(kernels, Xs, ys, X_tests, diags, means, test_means, test_diags,
+                                                       predict_kernels, include_mean, normals, False, ctx)
+    samples = [f.reshape(shape + (f.shape[1],)) for f in draws]
+    return (values, samples, info, cinfo) if return_info else (values, samples)
 
 
 def single_gradient(solver, resid, vectors: bool):
