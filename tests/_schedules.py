@@ -1,6 +1,12 @@
 """Schedule option sets of the Cholesky's panel chain, shared by the GPU tests that run the factorisation under each
 (test_gpu_0_kernels.py::test_panel_chain_variants_agree: the factor; test_gpu_8_fused_schedules.py: the fused
-log-likelihood).  Context options by name (tgp_ctx_set_option); library defaults for the others."""
+log-likelihood).  Context options by name (tgp_ctx_set_option); library defaults for the others.  And the schedule's
+dry run under such a set (tgp_trace_factor), which needs no GPU."""
+import ctypes as C
+
+import numpy as np
+
+from tinygp_amd import _ffi
 
 PANEL_CHAIN_VARIANTS = [
     dict(chain_kernel=0, fused_step=1, gate_split=0), dict(chain_kernel=0, fused_step=1, gate_split=1),
@@ -34,3 +40,15 @@ PANEL_CHAIN_VARIANTS = [
 
 def option_id(opts):
     return "-".join(f"{k}{v}" for k, v in opts.items()) or "defaults"
+
+
+def trace_options(n_pad, opts, fused):
+    """The records of tgp_trace_factor with exactly these context options (library defaults for the others)."""
+    lib = _ffi.load_library()
+    cap = 48 * (n_pad // 128) + 256
+    out = np.zeros(cap * 10, dtype=np.int64)
+    n = C.c_int64()
+    text = ",".join(f"{k}={v}" for k, v in opts.items())
+    st = lib.tgp_trace_factor(n_pad, text.encode(), fused, out.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n))
+    assert st == 0, lib.tgp_last_error()
+    return out[: n.value * 10].reshape(-1, 10).tolist()

@@ -13,12 +13,10 @@ chain's forward-substitution tasks leave and the evaluation's scalars ('Z',).  A
 sum that no earlier record of the same trace wrote is a STALE read (a value left by an earlier
 evaluation), and exactly one record writes the scalars.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from tinygp_amd import _ffi
+from _schedules import trace_options
 
 NSTREAMS = 5
 EV_G1, EV_G2 = 7, 8  # split gate: column block 1 / column blocks 2.. of the next panel
@@ -36,18 +34,6 @@ def trace(n_pad, nb=1024, lookahead=1, first_split=5, first_small=1100, fused=1,
     opts["chain_kernel"] = 0  # (the library's default is the persistent chain: its configurations say so)
     opts.update(more)
     return trace_options(n_pad, opts, fused & 1)
-
-
-def trace_options(n_pad, opts, fused):
-    """The records of tgp_trace_factor with exactly these context options (library defaults for the others)."""
-    lib = _ffi.load_library()
-    cap = 48 * (n_pad // 128) + 256
-    out = np.zeros(cap * 10, dtype=np.int64)
-    n = C.c_int64()
-    text = ",".join(f"{k}={v}" for k, v in opts.items())
-    st = lib.tgp_trace_factor(n_pad, text.encode(), fused, out.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n))
-    assert st == 0, lib.tgp_last_error()
-    return out[: n.value * 10].reshape(-1, 10).tolist()
 
 
 def accesses(rec, T, part=None):
