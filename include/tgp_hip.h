@@ -828,6 +828,31 @@ int tgp_qsep_series_grad(tgp_qsep_series* set, const double* leaves, int32_t nle
                          const double* resid_concat, int32_t ndir, const double* dleaves, const double* dh,
                          const double* dPinf, int32_t* info, double* out, double* dout, double* gnoise_concat,
                          double* alpha_concat, int32_t* nchains, int32_t* npasses);
+/* Value and prediction (as tgp_qsep_factor_logprob, then tgp_qsep_predict with the residual) of every series of the set
+ * under a model of its own, evaluated together.  Models, noise_concat and resid_concat as in tgp_qsep_series_logprob.
+ * Series b predicts at the test_offsets[b + 1] - test_offsets[b] points [test_offsets[b], test_offsets[b + 1]) of
+ * xtest_concat (test_offsets: nseries + 1 values from 0, non-decreasing; a series may bring none), in any order and
+ * anywhere relative to its data; its means and variances (of the latent process: no noise added) land at the same
+ * places of mean_concat and var_concat (either may be NULL and its half of the work is then skipped; both NULL is the
+ * value alone).  at_data (nseries flags, or NULL): a series whose flag is set predicts at its own data -- its count must
+ * be its length, its part of xtest_concat is not read and nothing goes up for it.  info, out: as the value call's.  A
+ * series' value, info and every mean and variance have the bits of tgp_qsep_factor_logprob and tgp_qsep_predict on a
+ * handle created on that series alone, whatever nseries, its position, the other series' lengths and test points and
+ * the split.  A non-positive pivot sets that series' info, gives NaN in its value, means and variances and changes no
+ * other series by a bit.  A launch chain (one upload each of the models, noise, residual and test points, which the
+ * host has sorted by value per series, one download, one stream synchronisation) holds at most 64 series and at most
+ * 1 GiB of device scratch; chains are filled in the order given ("Batches of series: prediction",
+ * states the layout and the rule, a function of the lengths, the test-point counts, J and which outputs are wanted),
+ * and *nchains (may be NULL) reports how many ran.  The resident table is re-cut and uploaded whenever the call, J, the
+ * outputs wanted or any series' number of test points differs from the previous call's.  Argument errors: null arrays
+ * (xtest_concat only where a series brings test points of its own), test_offsets that do not start at 0 or that
+ * decrease, at_data set for a series whose count is not its length, and a series that exceeds the cap alone, raised
+ * before anything is allocated. */
+int tgp_qsep_series_predict(tgp_qsep_series* set, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                            int32_t J, const double* hvec, const double* Pinf, const double* noise_concat,
+                            const double* resid_concat, const int64_t* test_offsets, const double* xtest_concat,
+                            const int32_t* at_data, int32_t* info, double* value, double* mean_concat,
+                            double* var_concat, int32_t* nchains);
 
 #ifdef __cplusplus
 }

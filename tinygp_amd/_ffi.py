@@ -182,6 +182,7 @@ SIGNATURES = {
     "tgp_qsep_series_logprob": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _pi32],
     "tgp_qsep_series_grad": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _pi32, _pi32],
+    "tgp_qsep_series_predict": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi32],
 }
 
 

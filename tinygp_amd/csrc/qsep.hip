@@ -34,12 +34,15 @@
 // has the bits of its single call.  The gradient's kernels take the same member axis (see "gradient" below).
 // Sets of series: the same kernels, instantiated over an extent policy ("extents" below), serve members that each have
 // a series of their own -- their own slice of t, length, chunk length, chunk count and scan depth -- from a device table.
-// The gradient's kernels take the same two kinds of extent, so a set of series has value and gradient in one launch chain.
+// The gradient's kernels take the same two kinds of extent, so a set of series has value and gradient in one launch chain;
+// so does the prediction's emit pass (qs_pred_emit over UniformPExtent / TablePExtent, the members' test points in a
+// small table of their own, QTest), so a set predicts at every member's own test points in one chain as well.
 #include "tgp_common.h"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
@@ -777,18 +780,45 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_aff_emit(int op, const QModel* 
 // pass leaves (q^T F, q^T D q, e) per test point and term in `pt` (PT doubles each), the backward pass finishes both outputs.
 constexpr int PT = 2 + QJ;
 
-// idx[m] = (number of t_n <= x_m) - 1: the interval of x_m, -1 before the first point (NaN lands there too)
-__global__ void qs_pred_locate(const double* __restrict__ t, int64_t n, const double* __restrict__ x, int64_t m,
-                               int64_t* __restrict__ idx) {
-  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (j >= m) return;
-  const double xv = x[j];
+// (number of t_n <= x) - 1: the interval of x, -1 before the first point (NaN lands there too)
+__device__ __forceinline__ int64_t interval_of(const double* __restrict__ t, int64_t n, double xv) {
   int64_t lo = 0, hi = n;
   while (lo < hi) {
     const int64_t mid = lo + (hi - lo) / 2;
     if (t[mid] <= xv) lo = mid + 1; else hi = mid;
   }
-  idx[j] = lo - 1;
+  return lo - 1;
+}
+
+// idx[m]: the interval of x_m
+__global__ void qs_pred_locate(const double* __restrict__ t, int64_t n, const double* __restrict__ x, int64_t m,
+                               int64_t* __restrict__ idx) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  idx[j] = interval_of(t, n, x[j]);
+}
+
+// Sets of series: the test points of one prediction call, one QTest per member of the chain (a small table that goes up
+// with every chain: test points change from call to call, so they are not part of the resident QExtent).  A member's
+// xt, sidx, order, pt, mean and var lie `off` entries (pt: PT times that) into the chain's concatenated arrays; inside
+// its slice every index is local.  own: the test points are the member's own data (m == its n), nothing was uploaded.
+struct QTest {
+  int64_t off, m, own;
+};
+
+// The locate kernel for the members of an extent table (blockIdx.y): sorted position j of member b holds its test point
+// order[j] (sorted by value on the host, NaN first), so sidx comes out non-decreasing.  A member at its own data is
+// qs_pred_identity's route: the data are sorted already, the order is the identity and is written here.
+__global__ void qs_pred_locate_table(const QExtent* __restrict__ tab, const QTest* __restrict__ tests,
+                                     const double* __restrict__ t, const double* __restrict__ x,
+                                     int64_t* __restrict__ order, int64_t* __restrict__ sidx) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  const QTest& T = tests[blockIdx.y];
+  if (j >= T.m) return;
+  const QExtent& e = tab[blockIdx.y];
+  t += e.off, order += T.off, sidx += T.off;
+  if (T.own) order[j] = j;
+  sidx[j] = interval_of(t, e.n, T.own ? t[j] : x[T.off + order[j]]);
 }
 
 // the test points are the sorted data themselves: their intervals are already non-decreasing, the order is the identity
@@ -933,24 +963,57 @@ __device__ __forceinline__ void pred_serve_bwd(const QModel& m, const double* __
   }
 }
 
-// sidx: the test points' interval indices, sorted; order: the test point at each sorted position; gv: the nterms
-// test-side vectors; pt: mt x nterms x PT; mean, var: nterms x mt
+// What the emit pass knows of the member it serves: its series (a GMember whose `pre` is where its chunk prefixes lie from
+// the prefix pointer) and its test points -- mt of them, `at` entries into xt, sidx, order, mean and var (pt: PT times
+// that per term); its model and, a model's doubles apart like it, its test-side vectors are number `model` of theirs (the
+// single call: 0 whatever the block, so that its model pointer stays the kernel's argument); own: the test points are
+// the member's t.
+struct PMember {
+  GMember g;
+  int64_t at, mt, model;
+  bool own;
+};
+struct UniformPExtent {  // the single call: one series, mt test points, every pointer the member's own
+  int64_t n, lc, nchunks, mt;
+  __device__ __forceinline__ PMember operator()(int64_t) const {
+    return {{n, lc, nchunks, 0, 0, 0, 0, 0, 0, 0, 0, 0}, 0, mt, 0, false};
+  }
+};
+struct TablePExtent {  // sets of series: the pointers are the bases of the chain's arrays, gv the first model's h (one term)
+  const QExtent* tab;
+  const QTest* tests;
+  __device__ __forceinline__ PMember operator()(int64_t mem) const {
+    const QTest& x = tests[mem];
+    return {TableGExtent{tab}(mem, 0, ScanPred::ESZ), x.off, x.m, mem, x.own != 0};
+  }
+};
+
+// Member blockIdx.y (the single call: member 0 of one).  sidx: the test points' interval indices, sorted; order: the test
+// point at each sorted position; gv: the nterms test-side vectors; pt: mt x nterms x PT; mean, var: nterms x mt
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_pred_emit(int dir, int want_mean, int want_var,
                                                            const QModel* __restrict__ mp, const double* __restrict__ t,
                                                            const double* __restrict__ cbuf,
                                                            const double* __restrict__ wbuf,
-                                                           const double* __restrict__ alpha, int64_t n, int64_t lc,
-                                                           int64_t nchunks, const double* __restrict__ prefix,
+                                                           const double* __restrict__ alpha, E ext,
+                                                           const double* __restrict__ prefix,
                                                            const double* __restrict__ xt,
                                                            const int64_t* __restrict__ sidx,
-                                                           const int64_t* __restrict__ order, int64_t mt,
+                                                           const int64_t* __restrict__ order,
                                                            const double* __restrict__ gv, int nterms,
                                                            double* __restrict__ pt, double* __restrict__ mean,
                                                            double* __restrict__ var) {
   const Lane L;
-  if (L.wave >= nchunks) return;
-  const QModel& m = *mp;
+  const PMember T = ext(blockIdx.y);
+  if (L.wave >= T.g.nchunks) return;
+  const int64_t n = T.g.n, lc = T.g.lc, nchunks = T.g.nchunks, mt = T.mt;
+  const QModel& m = mp[T.model];
   const int J = m.J, r = L.r, c = L.c;
+  t += T.g.t, cbuf += T.g.fac, wbuf += T.g.fac * J, prefix += T.g.pre;
+  if (alpha) alpha += T.g.fac;
+  xt = T.own ? t : xt + T.at;
+  sidx += T.at, order += T.at, gv += T.model * int64_t(sizeof(QModel) / sizeof(double));
+  pt += T.at * nterms * PT, mean += T.at * nterms, var += T.at * nterms;
   const double Pl = m.P[L.lane];
   const double Ph_r = Xh(m, Pl, r);
   const int64_t ptsz = int64_t(nterms) * PT;
@@ -1282,11 +1345,7 @@ __global__ void qs_smp_locate(const double* __restrict__ t, int64_t n, const dou
   const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (j >= m) return;
   const double xv = x[order[j]];
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (t[mid] <= xv) lo = mid + 1; else hi = mid;
-  }
+  const int64_t lo = interval_of(t, n, xv) + 1;
   sidx[j] = lo - 1;
   if (gt) gt[lo + j] = xv, gp[lo + j] = n + order[j];
 }
@@ -1539,11 +1598,16 @@ struct tgp_qsep_series {
   std::vector<QExtent> ext;      // the table's host copy; series_fill sets the offsets inside a chain
   std::vector<int64_t> chain0;   // the split the table was cut for: every chain's first member, then nseries
   std::vector<int64_t> chain_d;  // gradient: every chain's directions per pass
-  // what the resident table's chains were cut for: the call (0: none yet, 1: value, 2: value and gradient), the state
-  // dimension, the directions per member and whether the vectors were wanted (the last two: gradient only)
+  // what the resident table's chains were cut for: the call (0: none yet, 1: value, 2: value and gradient, 3: value and
+  // prediction), the state dimension, the directions per member and whether the vectors were wanted (gradient only;
+  // prediction: 1, its scan shares the primal work space), and for a prediction what was wanted (1: mean, 2: variance)
+  // and every member's number of test points
   struct Cut {
-    int32_t call = 0, J = 0, P = 0, vectors = 0;
-    bool operator==(const Cut& o) const { return call == o.call && J == o.J && P == o.P && vectors == o.vectors; }
+    int32_t call = 0, J = 0, P = 0, vectors = 0, want = 0;
+    std::vector<int64_t> tests;
+    bool operator==(const Cut& o) const {
+      return call == o.call && J == o.J && P == o.P && vectors == o.vectors && want == o.want && tests == o.tests;
+    }
   } cut;
   int64_t buf_need = 0;          // what the largest of those chains needs, in doubles
   double* t = nullptr;
@@ -1962,8 +2026,8 @@ int predict(tgp_qsep* q, const double* v_host, int v_is_alpha, int64_t m, const 
     double* prefix = nullptr;
     TGP_TRY(run_scan<ScanPred>(q->model, st, nc, 1, q->work, &prefix));
     qs_pred_emit<<<blocks_for(nc), WAVE * WPB, 0, st>>>(dir, want_mean, want_var, q->model, q->t, q->c, q->w, alpha,
-                                                        n, q->lc, nc, prefix, xt, sidx, order, m, gv, nterms, pt,
-                                                        mean, var);
+                                                        UniformPExtent{n, q->lc, nc, m}, prefix, xt, sidx, order, gv,
+                                                        nterms, pt, mean, var);
   }
   TGP_HIP_TRY(hipGetLastError());
   const size_t out_bytes = size_t(m) * size_t(nterms) * sizeof(double);
@@ -2066,7 +2130,8 @@ __attribute__((noinline)) void member_value(const double* got, int64_t n, int32_
 
 // ---- launch chains: many models over one series, or a set of series -----------------------------------------------------
 // A launch chain evaluates up to BATCH_MAX_MEMBERS members in one sequence of launches with one synchronisation, in a
-// buffer of at most BATCH_SCRATCH_BYTES: the value (log-probability) of each, or its value and gradient.  Who the members
+// buffer of at most BATCH_SCRATCH_BYTES: the value (log-probability) of each, its value and gradient, or (sets of series)
+// its value and the conditional mean and variance at test points of its own.  Who the members
 // are is a UniformMembers (models of a batch over the handle's series) or a TableMembers (series of a set); the sequence
 // is written once (chain).  The buffer, in doubles, with the totals over the members it is carved for (Totals: N points,
 // C chunks, W primal and T tangent scan work space, B members), P directions per member and D of them per pass:
@@ -2076,8 +2141,10 @@ __attribute__((noinline)) void member_value(const double* got, int64_t n, int32_
 //   and gradient   both primal scans' chunk prefixes (2 x 64 C, before the work space) | results (2 P B) | with the
 //                  vectors: alpha | noise gradient (N each) | dc, dw (D N (1 + J)) | tangent scan work space (T) |
 //                  per-chunk tangent sums (2 D C)
+//   and prediction (sets of series; M test points in the chain) with the mean: alpha (N) | the members' QTest table (3 B) |
+//                  xt | sidx | order (M each) | pt (PT M) | with the mean: means (M) | with the variance: variances (M)
 // W holds the largest of the scans that share it (Riccati and affine: 4 lane-blocks per element and level; with the
-// vectors the prediction's: 6), T the congruence scan's (3 per direction).
+// vectors or a prediction the prediction's: 6), T the congruence scan's (3 per direction).
 constexpr int64_t BATCH_MAX_MEMBERS = 64;
 constexpr int64_t BATCH_SCRATCH_BYTES = int64_t(1) << 30;
 static_assert(sizeof(QModel) % sizeof(double) == 0, "models are laid out in a buffer of doubles");
@@ -2094,7 +2161,17 @@ struct ChainCall {
   const double *dleaves, *dh, *dPinf;  // P per member
   int32_t* info;
   double *out, *dout, *gnoise, *alpha;  // the last two may be null
+  // value and prediction (sets of series): member b's test points are [test_offsets[b], test_offsets[b + 1]) - test_offsets[0]
+  // of xtest, mean and var (either may be null); at_data[b] (the array may be null): they are its own data, xtest is not read
+  const int64_t* test_offsets;
+  const double* xtest;
+  const int32_t* at_data;
+  double *mean, *var;
   bool vectors() const { return gnoise || alpha; }
+  bool predicts() const { return test_offsets && (mean || var); }
+  // how many test points its first k members hold, and whether alpha is made on the device
+  int64_t tests(int64_t k) const { return test_offsets ? test_offsets[k] - test_offsets[0] : 0; }
+  bool needs_alpha() const { return vectors() || (predicts() && mean); }
 
   // the same call from member b0 on, whose points start `at`, whose noise and residual noise_at and resid_at doubles in
   ChainCall from(int64_t b0, int64_t at, int64_t noise_at, int64_t resid_at) const {
@@ -2104,6 +2181,9 @@ struct ChainCall {
     c.dleaves = adv(dleaves, b0 * P * nl * 4), c.dh = adv(dh, b0 * P * J), c.dPinf = adv(dPinf, b0 * P * J * J);
     c.info += b0, c.out += b0, c.dout = adv(dout, b0 * P);
     c.gnoise = adv(gnoise, at), c.alpha = adv(alpha, at);
+    const int64_t tests_at = tests(b0);
+    c.test_offsets = adv(test_offsets, b0), c.at_data = adv(at_data, b0);
+    c.xtest = adv(xtest, tests_at), c.mean = adv(mean, tests_at), c.var = adv(var, tests_at);
     return c;
   }
 };
@@ -2114,6 +2194,10 @@ struct ChainArrays {
   double *noise, *resid, *c, *w, *z, *keep, *work, *logsum, *sumsq;
   int64_t* bad;
   double *res, *dres, *alpha, *gnoise, *tan, *twork, *tred;
+  // prediction: the members' QTest table, then per test point of the chain xt | sidx | order | pt (PT) | mean | var
+  QTest* tests;
+  double *xt, *pt, *mean, *var;
+  int64_t *sidx, *order;
 };
 
 // the chain's buffer, carved for the members it has room for
@@ -2121,6 +2205,8 @@ template <class M>
 ChainArrays carve(const M& m, double* buf, const ChainCall& a) {
   const Totals r = m.room();
   const int64_t J = a.J, vec = a.vectors() ? r.points : 0;
+  const bool pred = a.predicts();
+  const int64_t mt = pred ? a.tests(r.members) : 0;  // a predicting chain's buffer is carved for the members it holds
   double* p = buf;
   auto take = [&](int64_t len) {
     double* got = p;
@@ -2137,8 +2223,12 @@ ChainArrays carve(const M& m, double* buf, const ChainCall& a) {
   A.work = take(r.work);
   A.logsum = take(r.chunks), A.sumsq = take(r.chunks), A.bad = reinterpret_cast<int64_t*>(take(r.chunks));
   A.res = take(3 * r.members), A.dres = take(2 * a.P * r.members);
-  A.alpha = take(vec), A.gnoise = take(vec);
+  A.alpha = take(a.needs_alpha() ? r.points : 0), A.gnoise = take(vec);
   A.tan = take(a.D * r.points * (1 + J)), A.twork = take(r.twork), A.tred = take(a.D * 2 * r.chunks);
+  static_assert(sizeof(QTest) == 3 * sizeof(double), "a member's test points are three slots of the buffer");
+  A.tests = reinterpret_cast<QTest*>(take(pred ? 3 * r.members : 0));
+  A.xt = take(mt), A.sidx = reinterpret_cast<int64_t*>(take(mt)), A.order = reinterpret_cast<int64_t*>(take(mt));
+  A.pt = take(mt * PT), A.mean = take(a.mean ? mt : 0), A.var = take(a.var ? mt : 0);
   return A;
 }
 
@@ -2164,10 +2254,77 @@ int chain_value(const M& m, hipStream_t st, const ChainArrays& A, const ChainCal
   return TGP_OK;
 }
 
+// What a predicting chain sends up besides the value's arrays; alive until the chain's synchronisation
+struct TestUpload {
+  std::vector<QTest> tests;
+  std::vector<int64_t> order;
+};
+
+// The prediction part of a chain of series, after its value part and (with the mean) alpha: the members' QTest table and
+// test points go up -- each member's sorted by value here (stable, NaN first: place_test_points' order), those at their
+// own data not at all -- qs_pred_locate_table finds the intervals, then per direction qs_pred_fold, the prediction's scan
+// and qs_pred_emit, as the single predict() runs them; means and variances come down with the chain's other results.
+int chain_predict(const TableMembers& m, hipStream_t st, const ChainArrays& A, const ChainCall& a, TestUpload* up) {
+  const int64_t nb = m.count, mt = a.tests(nb);
+  const int want_mean = a.mean != nullptr, want_var = a.var != nullptr;
+  up->tests.resize(size_t(nb));
+  up->order.resize(size_t(mt));
+  int64_t most = 0;
+  for (int64_t b = 0; b < nb; ++b) {
+    const int64_t at = a.tests(b), cnt = a.tests(b + 1) - at;
+    const bool own = a.at_data && a.at_data[b];
+    up->tests[size_t(b)] = {at, cnt, own};
+    most = std::max(most, cnt);
+    if (own || cnt == 0) continue;
+    int64_t* o = up->order.data() + at;
+    const double* x = a.xtest + at;
+    for (int64_t j = 0; j < cnt; ++j) o[j] = j;
+    std::stable_sort(o, o + cnt, [&](int64_t p, int64_t q) { return sort_key(x[p]) < sort_key(x[q]); });
+  }
+  TGP_HIP_TRY(hipMemcpyAsync(A.tests, up->tests.data(), size_t(nb) * sizeof(QTest), hipMemcpyHostToDevice, st));
+  if (most == 0) return TGP_OK;
+  for (int64_t b = 0; b < nb;) {  // one copy per run of members that brought test points
+    if (up->tests[size_t(b)].own) { ++b; continue; }
+    int64_t e = b;
+    while (e < nb && !up->tests[size_t(e)].own) ++e;
+    const int64_t at = a.tests(b), len = a.tests(e) - at;
+    if (len > 0) {
+      TGP_HIP_TRY(hipMemcpyAsync(A.xt + at, a.xtest + at, size_t(len) * sizeof(double), hipMemcpyHostToDevice, st));
+      TGP_HIP_TRY(hipMemcpyAsync(A.order + at, up->order.data() + at, size_t(len) * sizeof(int64_t),
+                                 hipMemcpyHostToDevice, st));
+    }
+    b = e;
+  }
+  qs_pred_locate_table<<<dim3(unsigned(ceil_div(most, 256)), unsigned(nb)), 256, 0, st>>>(m.tab, A.tests, m.t, A.xt,
+                                                                                          A.order, A.sidx);
+  const dim3 grid(unsigned(blocks_for(m.chunks())), unsigned(nb));
+  const double* alpha = want_mean ? A.alpha : nullptr;
+  const double* gv = reinterpret_cast<const double*>(A.models) + offsetof(QModel, h) / sizeof(double);
+  for (int dir = 0; dir < 2; ++dir) {
+    qs_pred_fold<<<grid, WAVE * WPB, 0, st>>>(dir, want_mean, want_var, A.models, m.t, A.c, A.w, alpha, m.gext(false),
+                                              A.work);
+    double* prefix = nullptr;
+    TGP_TRY(m.template scan<ScanPred>(st, A.models, A.work, 1, false, &prefix));
+    qs_pred_emit<<<grid, WAVE * WPB, 0, st>>>(dir, want_mean, want_var, A.models, m.t, A.c, A.w, alpha,
+                                              TablePExtent{m.tab, A.tests}, prefix, A.xt, A.sidx, A.order, gv, 1, A.pt,
+                                              A.mean, A.var);
+  }
+  TGP_HIP_TRY(hipGetLastError());
+  if (want_mean) TGP_HIP_TRY(hipMemcpyAsync(a.mean, A.mean, size_t(mt) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (want_var) TGP_HIP_TRY(hipMemcpyAsync(a.var, A.var, size_t(mt) * sizeof(double), hipMemcpyDeviceToHost, st));
+  return TGP_OK;
+}
+
+// batches of models over one series do not predict: no entry point sets their call's test points
+int chain_predict(const UniformMembers&, hipStream_t, const ChainArrays&, const ChainCall&, TestUpload*) {
+  return TGP_OK;
+}
+
 // One launch chain over the members m in `buf`: the value part; value and gradient: the direction passes, then, with
-// the vectors, the backward solve and the noise gradient; one stream synchronisation; the results decoded into the
-// call's host arrays.  A failed member gets NaN for everything but its info: its c and w are not a factor of anything,
-// and what ran on them is overwritten.
+// the vectors, the backward solve and the noise gradient; value and prediction: the backward solve when the mean is
+// wanted, then chain_predict; one stream synchronisation; the results decoded into the call's host arrays.  A failed
+// member gets NaN for everything but its info: its c and w are not a factor of anything, and what ran on them is
+// overwritten.
 template <class M>
 int chain(const M& m, hipStream_t st, double* buf, const ChainCall& a, int32_t* passes) {
   const ChainArrays A = carve(m, buf, a);
@@ -2186,9 +2343,13 @@ int chain(const M& m, hipStream_t st, double* buf, const ChainCall& a, int32_t* 
     TGP_TRY(launch_tangents(m, st, A.models, A.dirs, nd, A.noise, A.c, A.w, A.resid, A.keep, A.twork, A.tan, A.tred,
                             A.dres + 2 * nb * d0));
   }
-  if (a.vectors()) {
+  TestUpload up;
+  if (a.needs_alpha()) {
     double* prefix = nullptr;
     TGP_TRY(launch_affine(m.own_rhs(), st, TGP_QS_BWD, A.models, A.c, A.w, 1, A.z, A.work, A.alpha, nullptr, &prefix));
+  }
+  if (a.predicts()) TGP_TRY(chain_predict(m, st, A, a, &up));
+  if (a.vectors()) {
     if (a.alpha)
       TGP_HIP_TRY(hipMemcpyAsync(a.alpha, A.alpha, size_t(h.points) * sizeof(double), hipMemcpyDeviceToHost, st));
     if (a.gnoise) {
@@ -2212,6 +2373,10 @@ int chain(const M& m, hipStream_t st, double* buf, const ChainCall& a, int32_t* 
     for (int64_t i = 0; failed && i < n; ++i) {
       if (a.gnoise) a.gnoise[lo + i] = NAN;
       if (a.alpha) a.alpha[lo + i] = NAN;
+    }
+    for (int64_t j = a.tests(b); failed && j < a.tests(b + 1); ++j) {  // as predict_guard answers for the single call
+      if (a.mean) a.mean[j] = NAN;
+      if (a.var) a.var[j] = NAN;
     }
   }
   return TGP_OK;
@@ -2378,6 +2543,28 @@ int series_grad_split(tgp_qsep_series* s, int32_t J, int32_t P, bool vectors) {
   return series_fill(s, {2, J, P, int32_t(vectors)}, SERIES_GRAD_FIXED,
                      [&](const QExtent& x) { return series_grad_member(x, J, P, vectors); },
                      [&](const QExtent& x) { return series_grad_dir(x, J); });
+}
+
+// Value and prediction: series b with M_b test points needs, in doubles, what the value takes with the prediction scan's
+// work space (384 S4_b for 256 S4_b), its QTest entry (3), with the mean alpha (N_b), and per test point xt, sidx, order
+// (1 each), pt (PT), with the mean its mean, with the variance its variance (1 each):
+//   pred_b = N_b (4 + J) + 384 S4_b + 3 nchunks_b + 6 + [mean] N_b + M_b (3 + PT + [mean] + [var])
+// A member at its own data counts its M_b = N_b like any other.  A function of (N_b, M_b, J, mean and variance wanted
+// or not) alone; the chains are the value's fill over it.
+int64_t series_predict_need(const QExtent& x, int64_t J, int64_t mt, bool want_mean, bool want_var) {
+  return x.n * (4 + J) + series_work(x, true) + 3 * x.nchunks + 6 + (want_mean ? x.n : 0) +
+         mt * (3 + PT + (want_mean ? 1 : 0) + (want_var ? 1 : 0));
+}
+
+int series_predict_split(tgp_qsep_series* s, int32_t J, bool want_mean, bool want_var, const int64_t* test_offsets) {
+  tgp_qsep_series::Cut cut{3, J, 0, 1, int32_t(want_mean) + 2 * int32_t(want_var), {}};
+  cut.tests.resize(size_t(s->nseries));
+  for (int64_t b = 0; b < s->nseries; ++b) cut.tests[size_t(b)] = test_offsets[b + 1] - test_offsets[b];
+  const QExtent* first = s->ext.data();  // series_fill hands the set's own extents over: x is series x - first
+  auto need = [&](const QExtent& x) {
+    return series_predict_need(x, J, cut.tests[size_t(&x - first)], want_mean, want_var);
+  };
+  return series_fill(s, cut, BATCH_MAX_MEMBERS * MODEL_DOUBLES, need, [](const QExtent&) { return int64_t(0); });
 }
 
 // members [b0, b0 + nb) of the set as the chain the resident table was cut for, with D directions per pass
@@ -2873,6 +3060,37 @@ int tgp_qsep_series_grad(tgp_qsep_series* s, const double* leaves, int32_t nleav
   a.dleaves = dleaves, a.dh = dh, a.dPinf = dPinf, a.dout = dout;
   a.info = info, a.out = out, a.gnoise = gnoise_concat, a.alpha = alpha_concat;
   return series_chains(s, a, nchains, npasses);
+}
+
+int tgp_qsep_series_predict(tgp_qsep_series* s, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                            int32_t J, const double* hvec, const double* Pinf, const double* noise_concat,
+                            const double* resid_concat, const int64_t* test_offsets, const double* xtest_concat,
+                            const int32_t* at_data, int32_t* info, double* out, double* mean_concat,
+                            double* var_concat, int32_t* nchains) {
+  QS_GUARD(s);
+  if (nchains) *nchains = 0;
+  TGP_ARG_CHECK(leaves && state_map && hvec && Pinf, "null model array");
+  TGP_ARG_CHECK(noise_concat && resid_concat && info && out, "null argument");
+  TGP_ARG_CHECK(test_offsets != nullptr, "null test offsets");
+  TGP_ARG_CHECK(test_offsets[0] == 0, "the test offsets start at 0 (got %lld)", (long long)test_offsets[0]);
+  for (int64_t b = 0; b < s->nseries; ++b) {
+    const int64_t cnt = test_offsets[b + 1] - test_offsets[b], n = s->ext[size_t(b)].n;
+    TGP_ARG_CHECK(cnt >= 0, "the test offsets must not decrease (series %lld: %lld after %lld)", (long long)b,
+                  (long long)test_offsets[b + 1], (long long)test_offsets[b]);
+    const bool own = at_data && at_data[b];
+    TGP_ARG_CHECK(!own || cnt == n, "series %lld predicts at its own %lld data points: its count of test points must "
+                  "be that (got %lld)", (long long)b, (long long)n, (long long)cnt);
+    TGP_ARG_CHECK(own || cnt == 0 || xtest_concat, "null test points (series %lld brings %lld)", (long long)b,
+                  (long long)cnt);
+  }
+  std::vector<QModel> models;
+  TGP_TRY(pack_models(&models, s->nseries, leaves, nleaves, state_map, J, hvec, Pinf));
+  TGP_TRY(series_predict_split(s, J, mean_concat != nullptr, var_concat != nullptr, test_offsets));
+  ChainCall a{};
+  a.nl = nleaves, a.J = J, a.models = models.data(), a.noise = noise_concat, a.resid = resid_concat;
+  a.info = info, a.out = out;
+  a.test_offsets = test_offsets, a.xtest = xtest_concat, a.at_data = at_data, a.mean = mean_concat, a.var = var_concat;
+  return series_chains(s, a, nchains, nullptr);
 }
 
 int tgp_qsep_normalization(tgp_qsep* q, double* out) {

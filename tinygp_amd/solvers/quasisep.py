@@ -10,7 +10,8 @@ posterior draws by Matheron's rule (``sample_conditional``; O(N + M) per draw),
 the gradient of the log-probability (``value_and_grad``; O(N) per parameter) and the log-probabilities of many
 hyper-parameter sets over the one series in one launch chain (``log_probability_batch``; with their gradients:
 ``value_and_grad_batch``).  :class:`QuasisepSeriesSet` evaluates many series, each on coordinates of its own, in one
-launch chain (``tgp_qsep_series_logprob``; with their gradients: ``tgp_qsep_series_grad``).  Nothing
+launch chain (``tgp_qsep_series_logprob``; with their gradients: ``tgp_qsep_series_grad``; with predictions at test
+points of their own: ``tgp_qsep_series_predict``).  Nothing
 of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
 reference); the full conditional covariance and conditioning on another kernel keep the reference's dense route.
 
@@ -590,6 +591,71 @@ def pack_series_tangents(lengths, kernels):
     return pack_batch_tangents(kernels)
 
 
+def pack_series_tests(lengths, X_tests):
+    """The test points of ``tgp_qsep_series_predict`` for series of the given lengths: ``(test_offsets (B + 1,) int64,
+    xtest (sum m_b,) float64, at_data (B,) int32)``.  ``X_tests[b]``: (m_b,) or (m_b, 1), in any order, m_b = 0
+    allowed; ``None`` predicts at the series' own points: its flag is set, its count is N_b and its part of ``xtest``
+    stays zero (the device reads the resident coordinates instead).  A wrong count or shape raises ``ValueError``
+    naming the series."""
+    from tinygp_amd.kernels.quasisep import _coords
+
+    nb = len(lengths)
+    X_tests = list(X_tests)
+    if len(X_tests) != nb:
+        raise ValueError(f"X_tests must hold one entry per series ({nb}); got {len(X_tests)}")
+    points, at_data = [], np.zeros(nb, dtype=np.int32)
+    for b, X in enumerate(X_tests):
+        if X is None:
+            at_data[b] = 1
+            points.append(np.zeros(int(lengths[b])))
+            continue
+        try:
+            points.append(_f64(_coords(X)))
+        except ValueError as e:
+            raise ValueError(f"X_tests[{b}] of series {b}: {e}") from e
+    offsets = np.concatenate([[0], np.cumsum([len(p) for p in points])]).astype(np.int64)
+    xtest = np.concatenate(points) if points else np.empty(0)
+    return offsets, np.ascontiguousarray(xtest, dtype=np.float64), at_data
+
+
+def series_added_means(means, test_offsets, test_means, include_mean: bool):
+    """What ``include_mean`` adds to series b's predictions, a list of (m_b,) float64 arrays -- the convention of
+    :func:`tinygp_amd.predict_datasets`: a scalar ``means[b]`` itself; for a vector ``means[b]`` -- it enters the
+    residual only -- ``test_means[b]``, a scalar or (m_b,), which ``include_mean`` then requires.  A ``ValueError`` names
+    the series."""
+    nb = len(test_offsets) - 1
+    counts = np.diff(test_offsets)
+
+    def entries(values, what):
+        values = [None] * nb if values is None else list(values)
+        if len(values) != nb:
+            raise ValueError(f"{what} must hold one entry per series ({nb}); got {len(values)}")
+        return values
+
+    means, test_means = entries(means, "means"), entries(test_means, "test_means")
+    added = []
+    for b, (mean, tmean) in enumerate(zip(means, test_means)):
+        m = int(counts[b])
+        if mean is None or np.ndim(mean) == 0:
+            if tmean is not None:
+                raise ValueError(f"test_means[{b}] is given, but means[{b}] of series {b} is not a vector: a scalar mean "
+                                 "is added to the predictions by itself")
+            added.append(np.zeros(m) if mean is None else np.full(m, np.asarray(mean, dtype=np.float64)))
+        elif tmean is None:
+            if include_mean:
+                raise ValueError(f"means[{b}] of series {b} is a vector: the mean at its test points must be given as "
+                                 f"test_means[{b}] (a scalar or ({m},)), or include_mean=False")
+            added.append(np.zeros(m))
+        else:
+            t = np.asarray(tmean, dtype=np.float64)
+            if t.ndim == 2 and t.shape[1] == 1:
+                t = t[:, 0]
+            if t.shape not in ((), (m,)):
+                raise ValueError(f"test_means[{b}] must have shape ({m},) or be a scalar for series {b}; got {t.shape}")
+            added.append(np.array(np.broadcast_to(t, (m,))))
+    return added
+
+
 class QuasisepSeriesSet:
     """B series on coordinates of their own -- the light curves of a survey, each with its gaps, masks and length --
     evaluated together on the device: one series per grid row of every kernel (``tgp_qsep_series_logprob``), where a
@@ -676,6 +742,57 @@ class QuasisepSeriesSet:
         result = out, {"kernel": kgrad, "noise_diag": gnoise, "mean": alpha, "transform": None}
         return result + (info,) if return_info else result
 
+    def predict(self, kernels, ys, diags, X_tests, *, means=None, test_means=None, return_var: bool = True,
+                include_mean: bool = True, return_info: bool = False):
+        """Value and prediction of the B series in one launch chain (``tgp_qsep_series_predict``): every light curve of
+        a survey interpolated, detrended or scored on held-out points after the fit, where a loop of
+        :meth:`QuasisepSolver.predict_mean_var` pays a handle, an upload, a launch chain and a stream synchronisation
+        per series.
+
+        ``kernels``, ``ys``, ``diags`` as in :meth:`log_probability`.  ``X_tests[b]``: (m_b,) or (m_b, 1), unsorted,
+        with duplicates, anywhere relative to the data, m_b = 0 allowed; ``None`` predicts at the series' own points
+        (nothing is uploaded for it).  ``means[b]``: a scalar is added to the predicted mean when ``include_mean``; a
+        vector (N_b,) enters the residual only and needs ``test_means[b]``, a scalar or (m_b,), which is then what
+        ``include_mean`` adds (the convention of :func:`tinygp_amd.predict_datasets`).
+
+        Returns ``(values (B,), means, variances)``, float64: ``means`` and ``variances`` are lists of B arrays (m_b,)
+        in the caller's order, ``variances`` (of the latent process: no noise added, as
+        :meth:`QuasisepSolver.predict_mean_var`) ``None`` without ``return_var``, whose half of the device work is then
+        skipped; with ``return_info`` the B ``info`` values come fourth.  Member b's value, mean and variance have the
+        bits of ``QuasisepSolver(kernels[b], Xs[b], Diagonal(diags[b]))`` with ``.log_probability(r)`` and
+        ``.predict_mean_var(r, X_tests[b])``, r = ``ys[b] - means[b]``, on a fresh solver, whatever B, its position, the
+        other members' lengths and test points and the split into chains.  A failed or non-finite member gives ``-inf``
+        and NaN predictions and touches no other."""
+        if self._handle is None:
+            raise ValueError("this QuasisepSeriesSet has been closed")
+        leaves, smap, h, P, noise, resid = pack_series(self.lengths, kernels, ys, diags, means)
+        test_offsets, xtest, at_data = pack_series_tests(self.lengths, X_tests)
+        added = series_added_means(means, test_offsets, test_means, include_mean)
+        nb, total = len(self), int(test_offsets[-1])
+        info, out = np.zeros(nb, dtype=np.int32), np.empty(nb)
+        mean = np.empty(max(total, 1))
+        var = np.empty(max(total, 1)) if return_var else None
+        _ffi.check(_ffi.lib().tgp_qsep_series_predict(self._handle, _ffi.ptr(leaves), leaves.shape[1], _ffi.ptr(smap),
+                                                      h.shape[1], _ffi.ptr(h), _ffi.ptr(P), _ffi.ptr(noise),
+                                                      _ffi.ptr(resid), _ffi.ptr(test_offsets),
+                                                      _ffi.ptr(xtest) if total else None, _ffi.ptr(at_data),
+                                                      _ffi.ptr(info), _ffi.ptr(out), _ffi.ptr(mean), _ffi.ptr(var),
+                                                      None), "tgp_qsep_series_predict")
+        failed = (info != 0) | ~np.isfinite(out)
+        out[failed] = -np.inf
+        split = lambda a: [a[lo:hi] for lo, hi in zip(test_offsets[:-1], test_offsets[1:])]  # noqa: E731
+        mus = split(mean)
+        variances = split(var) if return_var else None
+        for b in range(nb):
+            if failed[b]:
+                mus[b] = np.full(len(mus[b]), np.nan)
+                if return_var:
+                    variances[b] = np.full(len(variances[b]), np.nan)
+            elif include_mean:
+                mus[b] = mus[b] + added[b]
+        result = out, mus, variances
+        return result + (info,) if return_info else result
+
     def close(self):
         if getattr(self, "_handle", None):
             _ffi.lib().tgp_qsep_series_destroy(self._handle)
@@ -696,6 +813,21 @@ def log_probability_series(kernels, Xs, ys, *, diags, means=None):
     series = QuasisepSeriesSet(Xs)
     try:
         return series.log_probability(kernels, ys, diags, means=means)
+    finally:
+        series.close()
+
+
+def predict_series(kernels, Xs, ys, X_tests, *, diags, means=None, test_means=None, return_var: bool = True,
+                   include_mean: bool = True, return_info: bool = False):
+    """Condition B quasiseparable GPs on series with coordinates of their own and predict at test points of their own:
+    builds a :class:`QuasisepSeriesSet` on ``Xs``, calls its :meth:`~QuasisepSeriesSet.predict` and closes it.  Member
+    b equals ``QuasisepSolver(kernels[b], Xs[b], Diagonal(diags[b]))`` with ``log_probability`` and
+    ``predict_mean_var`` of ``ys[b] - means[b]`` at ``X_tests[b]`` bit for bit for float64 inputs.  Arguments and result
+    as in :meth:`QuasisepSeriesSet.predict`; keep the set yourself to predict more than once."""
+    series = QuasisepSeriesSet(Xs)
+    try:
+        return series.predict(kernels, ys, diags, X_tests, means=means, test_means=test_means, return_var=return_var,
+                              include_mean=include_mean, return_info=return_info)
     finally:
         series.close()
 
