@@ -853,6 +853,42 @@ int tgp_qsep_series_predict(tgp_qsep_series* set, const double* leaves, int32_t 
                             const double* resid_concat, const int64_t* test_offsets, const double* xtest_concat,
                             const int32_t* at_data, int32_t* info, double* value, double* mean_concat,
                             double* var_concat, int32_t* nchains);
+/* Value and posterior draws (as tgp_qsep_factor_logprob, then tgp_qsep_sample with the residual) of every series of the
+ * set under a model of its own, evaluated together.  Models, noise_concat and resid_concat as in
+ * tgp_qsep_series_logprob; test_offsets and xtest_concat as in tgp_qsep_series_predict: series b with n_b data points
+ * brings m_b = test_offsets[b + 1] - test_offsets[b] test points (unsorted, with duplicates, anywhere relative to its
+ * data, all finite; none is allowed), G_b = n_b + m_b.  at_data (nseries flags, or NULL): a series whose flag is set has
+ * no test points -- its grid is its own t and its count must be 0, for the draws at its data are an output already.
+ * nrhs >= 1 columns of draws.  All arrays are row-major with member b's rows after member b - 1's: xi_concat (G_b J rows
+ * per member; rows p J .. p J + J - 1 belong to point p of [data; test points]) and eps_concat (n_b rows), the standard
+ * normals of tgp_qsep_sample; data_concat (n_b rows) and test_concat (m_b rows), the draws, nrhs columns each; either
+ * output may be NULL and its work is then skipped (both NULL is the value alone).  info, value: as the value call's.  A
+ * series' value, info and column c of its draws have the bits of tgp_qsep_factor_logprob and tgp_qsep_sample on a handle
+ * created on that series alone with that column alone, whatever nseries, its position, the other series' lengths, test
+ * points and flags, nrhs and the split.  A non-positive pivot sets that series' info, gives NaN in its value and in all
+ * its draws and changes no other series by a bit.
+ * A launch chain (one stream synchronisation) runs factor and value, the members' merged grids, then per pass of columns
+ * the prior scan over the grids, v = r - f(X) - sqrt(noise) eps, both solves, the conditional-mean scans forwards and
+ * backwards and the data side, every step one series per grid row.  It holds at most 64 series and at most 1 GiB of
+ * device scratch: after the 64 models, per series what the value call takes, the extent of its merged grid (13), xt, sidx,
+ * order (m_b each), gt, gp (G_b each), and per column of a pass xi (G_b max(J, 2)), f and eps at the data (n_b each) and,
+ * with test_concat, f at the test points (m_b), and per group of 8 columns the scans' work space (192 doubles per entry
+ * of the larger of the two scan pyramids, the data's and the grid's).  Chains are filled in the order given while every
+ * member fits with one column; columns then run in passes of at most 64, a multiple of 8 or below 8 by ones, as many as
+ * the rest of the cap holds ("Batches of series: posterior draws", states the layout and the rule, a
+ * function of the n_b, m_b, J, nrhs and which outputs are wanted alone).  Every array of a pass goes up or comes down as
+ * one copy for the chain's members.  *nchains and *npasses (may be NULL) report the chains and the column passes (summed
+ * over the chains) that ran.  The resident table is re-cut and uploaded whenever the call, J, nrhs, the outputs wanted or
+ * any series' number of test points differs from the previous call's.  Argument errors: null arrays where they are read,
+ * test_offsets that do not start at 0 or that decrease, a test point that is not finite (the message names the series
+ * and the point), nrhs < 1, at_data set for a series whose count is not 0, and a series that exceeds the cap alone with
+ * one column, raised before anything is allocated. */
+int tgp_qsep_series_sample(tgp_qsep_series* set, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                           int32_t J, const double* hvec, const double* Pinf, const double* noise_concat,
+                           const double* resid_concat, const int64_t* test_offsets, const double* xtest_concat,
+                           const int32_t* at_data, int64_t nrhs, const double* xi_concat, const double* eps_concat,
+                           int32_t* info, double* value, double* data_concat, double* test_concat, int32_t* nchains,
+                           int32_t* npasses);
 
 #ifdef __cplusplus
 }

@@ -183,6 +183,9 @@ SIGNATURES = {
     "tgp_qsep_series_grad": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _pi32, _pi32],
     "tgp_qsep_series_predict": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi32],
+    # set, models (6), noise, resid | test_offsets, xtest, at_data | nrhs, xi, eps | info, value, data, test | nchains, npasses
+    "tgp_qsep_series_sample": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _pi32, _pi32],
 }
 
 

@@ -36,7 +36,11 @@
 // a series of their own -- their own slice of t, length, chunk length, chunk count and scan depth -- from a device table.
 // The gradient's kernels take the same two kinds of extent, so a set of series has value and gradient in one launch chain;
 // so does the prediction's emit pass (qs_pred_emit over UniformPExtent / TablePExtent, the members' test points in a
-// small table of their own, QTest), so a set predicts at every member's own test points in one chain as well.
+// small table of their own, QTest), so a set predicts at every member's own test points in one chain as well.  The
+// samples' kernels (qs_prior, qs_cm_fold, qs_cm_emit, qs_smp_locate, qs_smp_place over UniformSExtent / TableSExtent) take
+// a second extent table beside the data's, that of every member's merged grid, and both solves run for a block of columns
+// per member (TableColsExtent): a set draws from every member's posterior in one chain ("sets of series: value and
+// posterior draws" below).
 #include "tgp_common.h"
 
 #include <algorithm>
@@ -333,6 +337,19 @@ struct TableExtent {
   __device__ __forceinline__ Member operator()(int64_t mem, int64_t eblocks = 0) const {
     const QExtent& x = tab[mem];
     return {x.n, x.lc, x.nchunks, x.off, x.off, x.off, x.off, x.work, x.work + x.nchunks * eblocks * WAVE, x.chunks,
+            x.chunks};
+  }
+};
+
+// The members of a table with nrhs right-hand sides each (the solves of the samples): y and the output lie nrhs times the
+// slice offset in, and the scans of the ncg column groups run ncg x twork into the work space, as those of a direction pass.
+struct TableColsExtent {
+  const QExtent* tab;
+  int64_t nrhs, ncg;
+  __device__ __forceinline__ Member operator()(int64_t mem, int64_t eblocks = 0) const {
+    const QExtent& x = tab[mem];
+    const int64_t w = x.twork * ncg;
+    return {x.n, x.lc, x.nchunks, x.off, x.off, x.off * nrhs, x.off, w, w + x.nchunks * eblocks * WAVE, x.chunks,
             x.chunks};
   }
 };
@@ -1300,36 +1317,76 @@ __device__ __forceinline__ double prior_step(const QModel& m, double Pinf, const
   return mm(chol_psd(S, Pinf, J, r, c), xi, J, r, c);
 }
 
-// emit == 0: fold chunk k of column group cg into elem; emit != 0: walk it from its incoming state (prefix) and write
-// f = h^T x to out[point x nrhs + column]
+// What a kernel of the samples knows of the member it serves (blockIdx.y): its data (n points in nchunks chunks of lc),
+// its mt test points and its merged grid (G = n + mt points in ncG chunks of lcG), and where its rows lie from the
+// pointers the kernel was given -- dat: t, alpha and the data side of f; tst: xt, sidx, order and the test side of f;
+// grd: gt, gp and xi (J rows per point) -- every array `nrhs` columns wide.  work, pre: the elements and chunk prefixes of
+// the scan over its data's chunks, gwork, gpre: of the scan over its grid's, with ncg column groups interleaved.
+//   UniformSExtent   the single call: one series, every pointer the member's own
+//   TableSExtent     sets of series: data extent `tab[mem]` of the resident table beside grid extent `grid[mem]` of a
+//                    second table that goes up with the chain (test points change from call to call): the grid's n,
+//                    lc, nchunks and levels are those of G, its off the member's first grid row, so that mt and tst
+//                    are the differences of the two.  Either scan runs in the member's `twork` (the same in both
+//                    tables), ncg times that into the work space, as the scans of a direction pass do.
+struct SMember {
+  int64_t n, lc, nchunks, mt, G, lcG, ncG;
+  int64_t dat, tst, grd;
+  int64_t work, pre, gwork, gpre;
+  int64_t model;  // its model is number `model` of the kernel's (the single call: 0 whatever the block, as PMember's)
+};
+struct UniformSExtent {
+  int64_t n, lc, nchunks, mt, G, lcG, ncG;
+  __device__ __forceinline__ SMember operator()(int64_t, int64_t) const {
+    return {n, lc, nchunks, mt, G, lcG, ncG, 0, 0, 0, 0, 0, 0, 0, 0};
+  }
+};
+struct TableSExtent {
+  const QExtent *tab, *grid;
+  __device__ __forceinline__ SMember operator()(int64_t mem, int64_t ncg) const {
+    const QExtent &x = tab[mem], &g = grid[mem];
+    const int64_t w = x.twork * ncg, eb = ScanAffine::ESZ * ncg * WAVE;
+    return {x.n, x.lc, x.nchunks, g.n - x.n, g.n, g.lc, g.nchunks, x.off, g.off - x.off, g.off, w, w + x.nchunks * eb,
+            w, w + g.nchunks * eb, mem};
+  }
+};
+
+// Member blockIdx.y.  emit == 0: fold chunk k of column group cg into elem; emit != 0: walk it from its incoming state
+// (prefix) and write f = h^T x of point p to fdata[p x nrhs + column], of test point p - n to ftest (may be null: not
+// wanted) likewise
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_prior(int emit, const QModel* __restrict__ mp,
                                                        const double* __restrict__ gt, const int64_t* __restrict__ gp,
-                                                       int64_t G, int64_t lc, int64_t nchunks,
-                                                       const double* __restrict__ xi, int64_t nrhs, int64_t ncg,
+                                                       E ext, const double* __restrict__ xi, int64_t nrhs, int64_t ncg,
                                                        const double* __restrict__ prefix, double* __restrict__ elem,
-                                                       double* __restrict__ out) {
+                                                       double* __restrict__ fdata, double* __restrict__ ftest) {
   const Lane L;
-  if (L.wave >= nchunks * ncg) return;
-  const QModel& m = *mp;
+  const SMember S = ext(blockIdx.y, ncg);
+  if (L.wave >= S.ncG * ncg) return;
+  const QModel& m = mp[S.model];
   const int J = m.J, r = L.r, c = L.c;
+  gt += S.grd, xi += S.grd * J * nrhs;
+  if (gp) gp += S.grd;
   const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
   const bool live = r < J && col < nrhs;
   const double Pinf = m.P[L.lane];
-  double M = (r == c && r < J) ? 1.0 : 0.0, X = emit ? prefix[L.wave * WAVE + L.lane] : 0.0, Phi;
-  const int64_t g0 = k * lc, g1 = min(G, g0 + lc);
+  double M = (r == c && r < J) ? 1.0 : 0.0, X = emit ? prefix[S.gpre + L.wave * WAVE + L.lane] : 0.0, Phi;
+  const int64_t g0 = k * S.lcG, g1 = min(S.G, g0 + S.lcG);
   for (int64_t g = g0; g < g1; ++g) {
     const int64_t p = gp ? gp[g] : g;
     const double W = prior_step(m, Pinf, gt, g, live ? xi[(p * J + r) * nrhs + col] : 0.0, r, c, &Phi);
     X = mm(Phi, X, J, r, c) + W;
     if (emit) {
       const double f = hT(m, X, c);
-      if (r == 0 && col < nrhs) out[p * nrhs + col] = f;
+      if (r == 0 && col < nrhs) {
+        if (p < S.n) fdata[(S.dat + p) * nrhs + col] = f;
+        else if (ftest) ftest[(S.tst + p - S.n) * nrhs + col] = f;
+      }
     } else {
       M = mm(Phi, M, J, r, c);
     }
   }
   if (!emit) {
-    double* e = elem + L.wave * 2 * WAVE;
+    double* e = elem + S.gwork + L.wave * 2 * WAVE;
     e[L.lane] = M, e[WAVE + L.lane] = X;
   }
 }
@@ -1337,27 +1394,33 @@ __global__ __launch_bounds__(WAVE * WPB) void qs_prior(int emit, const QModel* _
 // key of a test point in the sort by value: NaN goes first, where qs_pred_locate puts it (interval -1)
 __host__ __device__ inline double sort_key(double x) { return x != x ? -INFINITY : x; }
 
-// sorted position j holds test point order[j] (sorted by value, ties in the caller's order): its interval as
-// qs_pred_locate finds it and, with a grid to build, its place in the merged grid (after the data of the same value)
-__global__ void qs_smp_locate(const double* __restrict__ t, int64_t n, const double* __restrict__ x,
-                              const int64_t* __restrict__ order, int64_t m, int64_t* __restrict__ sidx,
-                              double* __restrict__ gt, int64_t* __restrict__ gp) {
+// Member blockIdx.y: sorted position j holds its test point order[j] (sorted by value, ties in the caller's order): its
+// interval as qs_pred_locate finds it and, with a grid to build, its place in the merged grid (after the data of the same
+// value)
+template <class E>
+__global__ void qs_smp_locate(E ext, const double* __restrict__ t, const double* __restrict__ x,
+                              const int64_t* __restrict__ order, int64_t* __restrict__ sidx, double* __restrict__ gt,
+                              int64_t* __restrict__ gp) {
   const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (j >= m) return;
+  const SMember S = ext(blockIdx.y, 0);
+  if (j >= S.mt) return;
+  t += S.dat, x += S.tst, order += S.tst, sidx += S.tst;
   const double xv = x[order[j]];
-  const int64_t lo = interval_of(t, n, xv) + 1;
+  const int64_t lo = interval_of(t, S.n, xv) + 1;
   sidx[j] = lo - 1;
-  if (gt) gt[lo + j] = xv, gp[lo + j] = n + order[j];
+  if (gt) gt[S.grd + lo + j] = xv, gp[S.grd + lo + j] = S.n + order[j];
 }
 
-// data point i goes after the test points below it
-__global__ void qs_smp_place(const double* __restrict__ t, int64_t n, const double* __restrict__ x,
-                             const int64_t* __restrict__ order, int64_t m, double* __restrict__ gt,
-                             int64_t* __restrict__ gp) {
+// its data point i goes after the test points below it
+template <class E>
+__global__ void qs_smp_place(E ext, const double* __restrict__ t, const double* __restrict__ x,
+                             const int64_t* __restrict__ order, double* __restrict__ gt, int64_t* __restrict__ gp) {
   const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+  const SMember S = ext(blockIdx.y, 0);
+  if (i >= S.n) return;
+  t += S.dat, x += S.tst, order += S.tst, gt += S.grd, gp += S.grd;
   const double tv = t[i];
-  int64_t lo = 0, hi = m;
+  int64_t lo = 0, hi = S.mt;
   while (lo < hi) {
     const int64_t mid = lo + (hi - lo) / 2;
     if (x[order[mid]] < tv) lo = mid + 1; else hi = mid;
@@ -1365,6 +1428,8 @@ __global__ void qs_smp_place(const double* __restrict__ t, int64_t n, const doub
   gt[i + lo] = tv, gp[i + lo] = i;
 }
 
+// The two element-wise kernels run over rows x nrhs entries whoever the rows belong to: a chain's members lie row after
+// row in arrays of one pitch, so one launch over the chain's rows serves them all.
 // e (n x nrhs): eps in, v = r - f(X) - sqrt(noise) eps out
 __global__ void qs_smp_resid(const double* __restrict__ resid, const double* __restrict__ noise,
                              const double* __restrict__ f, double* __restrict__ e, int64_t n, int64_t nrhs) {
@@ -1393,14 +1458,17 @@ __device__ __forceinline__ double cm_step(int dir, const QModel& m, const double
   return (dir == 0 ? Ph_r : (r < m.J ? m.h[r] : 0.0)) * a;
 }
 
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_cm_fold(int dir, const QModel* __restrict__ mp,
                                                          const double* __restrict__ t, const double* __restrict__ alpha,
-                                                         int64_t n, int64_t lc, int64_t nchunks, int64_t nrhs,
-                                                         int64_t ncg, double* __restrict__ elem) {
+                                                         E ext, int64_t nrhs, int64_t ncg, double* __restrict__ elem) {
   const Lane L;
-  if (L.wave >= nchunks * ncg) return;
-  const QModel& m = *mp;
+  const SMember S = ext(blockIdx.y, ncg);
+  if (L.wave >= S.nchunks * ncg) return;
+  const QModel& m = mp[S.model];
   const int J = m.J, r = L.r, c = L.c;
+  const int64_t n = S.n, lc = S.lc, nchunks = S.nchunks;
+  t += S.dat, alpha += S.dat * nrhs, elem += S.work;
   const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
   const double Ph_r = Xh(m, m.P[L.lane], r);
   double M = (r == c && r < J) ? 1.0 : 0.0, V = 0.0, Phi;
@@ -1432,19 +1500,24 @@ __device__ __forceinline__ void cm_serve(int dir, int accumulate, const QModel& 
   if (writes) *out = (accumulate ? *out : 0.0) + s;
 }
 
-// sidx, order, xt as in qs_pred_emit; out: mt x nrhs.  dir 0 writes (accumulate: adds to) its part, dir 1 adds its own.
+// Member blockIdx.y; sidx, order, xt as in qs_pred_emit; out: mt x nrhs.  dir 0 writes (accumulate: adds to) its part,
+// dir 1 adds its own.
+template <class E>
 __global__ __launch_bounds__(WAVE * WPB) void qs_cm_emit(int dir, int accumulate, const QModel* __restrict__ mp,
                                                          const double* __restrict__ t, const double* __restrict__ alpha,
-                                                         int64_t n, int64_t lc, int64_t nchunks, int64_t nrhs,
-                                                         int64_t ncg, const double* __restrict__ prefix,
+                                                         E ext, int64_t nrhs, int64_t ncg,
+                                                         const double* __restrict__ prefix,
                                                          const double* __restrict__ xt,
                                                          const int64_t* __restrict__ sidx,
-                                                         const int64_t* __restrict__ order, int64_t mt,
-                                                         double* __restrict__ out) {
+                                                         const int64_t* __restrict__ order, double* __restrict__ out) {
   const Lane L;
-  if (L.wave >= nchunks * ncg) return;
-  const QModel& m = *mp;
+  const SMember S = ext(blockIdx.y, ncg);
+  if (L.wave >= S.nchunks * ncg) return;
+  const QModel& m = mp[S.model];
   const int J = m.J, r = L.r, c = L.c;
+  const int64_t n = S.n, lc = S.lc, nchunks = S.nchunks, mt = S.mt;
+  t += S.dat, alpha += S.dat * nrhs, prefix += S.pre;
+  xt += S.tst, sidx += S.tst, order += S.tst, out += S.tst * nrhs;
   const int64_t k = L.wave / ncg, cg = L.wave % ncg, col = cg * 8 + c;
   const bool writes = r == 0 && col < nrhs;
   const double Ph_r = Xh(m, m.P[L.lane], r);
@@ -1597,16 +1670,19 @@ struct tgp_qsep_series {
   std::vector<int64_t> offsets;  // nseries + 1: series b is [offsets[b], offsets[b + 1]) of the concatenated arrays
   std::vector<QExtent> ext;      // the table's host copy; series_fill sets the offsets inside a chain
   std::vector<int64_t> chain0;   // the split the table was cut for: every chain's first member, then nseries
-  std::vector<int64_t> chain_d;  // gradient: every chain's directions per pass
+  std::vector<int64_t> chain_d;  // gradient: every chain's directions per pass; posterior draws: its columns per pass
   // what the resident table's chains were cut for: the call (0: none yet, 1: value, 2: value and gradient, 3: value and
-  // prediction), the state dimension, the directions per member and whether the vectors were wanted (gradient only;
-  // prediction: 1, its scan shares the primal work space), and for a prediction what was wanted (1: mean, 2: variance)
-  // and every member's number of test points
+  // prediction, 4: value and posterior draws), the state dimension, the directions per member and whether the vectors were
+  // wanted (gradient only; prediction: 1, its scan shares the primal work space), for a prediction what was wanted (1:
+  // mean, 2: variance; draws: 1: at the data, 2: at the test points) and every member's number of test points, and for
+  // draws their number of columns
   struct Cut {
     int32_t call = 0, J = 0, P = 0, vectors = 0, want = 0;
     std::vector<int64_t> tests;
+    int64_t cols = 0;
     bool operator==(const Cut& o) const {
-      return call == o.call && J == o.J && P == o.P && vectors == o.vectors && want == o.want && tests == o.tests;
+      return call == o.call && J == o.J && P == o.P && vectors == o.vectors && want == o.want && tests == o.tests &&
+             cols == o.cols;
     }
   } cut;
   int64_t buf_need = 0;          // what the largest of those chains needs, in doubles
@@ -1693,6 +1769,18 @@ int64_t chunk_length(int64_t n) {
   int64_t lc = 16;
   while (lc < 256 && lc * 4096 < n) lc *= 2;
   return lc;
+}
+
+// the extent of a series of n points by itself (the single call's rule: a member's chunks are those of its own solver);
+// where it lies in a chain is the split's to say
+QExtent extent_of(int64_t n) {
+  QExtent x{};
+  x.n = n;
+  x.lc = chunk_length(n);
+  x.nchunks = ceil_div(n, x.lc);
+  x.lev[0] = x.nchunks;
+  for (int l = 0; l < MAXLEV; ++l) x.lev[l + 1] = ceil_div(x.lev[l], GROUP);
+  return x;
 }
 
 template <class S>
@@ -2167,6 +2255,12 @@ struct ChainCall {
   const double* xtest;
   const int32_t* at_data;
   double *mean, *var;
+  // value and posterior draws (sets of series): nrhs columns of standard normals, xi ((N + M) J x nrhs, member after
+  // member, each [data; test points]) and eps (N x nrhs), and of draws at the data (N x nrhs) and at the test points
+  // (M x nrhs; either may be null)
+  int64_t nrhs;
+  const double *xi, *eps;
+  double *data, *test;
   bool vectors() const { return gnoise || alpha; }
   bool predicts() const { return test_offsets && (mean || var); }
   // how many test points its first k members hold, and whether alpha is made on the device
@@ -2184,6 +2278,8 @@ struct ChainCall {
     const int64_t tests_at = tests(b0);
     c.test_offsets = adv(test_offsets, b0), c.at_data = adv(at_data, b0);
     c.xtest = adv(xtest, tests_at), c.mean = adv(mean, tests_at), c.var = adv(var, tests_at);
+    c.xi = adv(xi, (at + tests_at) * J * nrhs), c.eps = adv(eps, at * nrhs);
+    c.data = adv(data, at * nrhs), c.test = adv(test, tests_at * nrhs);
     return c;
   }
 };
@@ -2198,6 +2294,7 @@ struct ChainArrays {
   QTest* tests;
   double *xt, *pt, *mean, *var;
   int64_t *sidx, *order;
+  double* end;  // where a call that needs more goes on carving
 };
 
 // the chain's buffer, carved for the members it has room for
@@ -2229,6 +2326,7 @@ ChainArrays carve(const M& m, double* buf, const ChainCall& a) {
   A.tests = reinterpret_cast<QTest*>(take(pred ? 3 * r.members : 0));
   A.xt = take(mt), A.sidx = reinterpret_cast<int64_t*>(take(mt)), A.order = reinterpret_cast<int64_t*>(take(mt));
   A.pt = take(mt * PT), A.mean = take(a.mean ? mt : 0), A.var = take(a.var ? mt : 0);
+  A.end = p;
   return A;
 }
 
@@ -2493,9 +2591,11 @@ int64_t series_grad_dir(const QExtent& x, int64_t J) { return x.n * (1 + J) + se
 constexpr int64_t SERIES_GRAD_FIXED = BATCH_MAX_MEMBERS * (MODEL_DOUBLES + GRAD_MAX_BATCH * DIR_DOUBLES);
 
 // Cuts the set into chains for `cut` and makes the resident table say where each member lies in its chain.  member(x),
-// dir(x): what series x needs by itself and per direction of a pass; fixed: the fixed part of the buffer.
-template <class Member, class Dir>
-int series_fill(tgp_qsep_series* s, const tgp_qsep_series::Cut& cut, int64_t fixed, Member member, Dir dir) {
+// dir(x): what series x needs by itself and per direction of a pass; fixed: the fixed part of the buffer; tangent_work(x):
+// what its `twork` steps by (the tangent scans' work space per direction; posterior draws: per column group).
+template <class Member, class Dir, class Twork = int64_t (*)(const QExtent&)>
+int series_fill(tgp_qsep_series* s, const tgp_qsep_series::Cut& cut, int64_t fixed, Member member, Dir dir,
+                Twork tangent_work = series_twork) {
   if (s->cut == cut) return TGP_OK;
   const int64_t budget = BATCH_BUDGET - fixed, P = cut.P;
   auto one = [&](const QExtent& x) { return member(x) + (P > 0 ? dir(x) : 0); };
@@ -2520,7 +2620,7 @@ int series_fill(tgp_qsep_series* s, const tgp_qsep_series::Cut& cut, int64_t fix
       used = count = mem = dsum = off = work = chunks = twork = 0;
     }
     x.off = off, x.work = work, x.chunks = chunks, x.keep = 2 * chunks * WAVE, x.twork = twork;
-    off += x.n, work += series_work(x, cut.vectors != 0), chunks += x.nchunks, twork += series_twork(x);
+    off += x.n, work += series_work(x, cut.vectors != 0), chunks += x.nchunks, twork += tangent_work(x);
     mem += member(x), dsum += dir(x);
     used += one(x), ++count;
   }
@@ -2681,8 +2781,9 @@ int place_test_points(tgp_qsep* q, int64_t m, const double* xtest_host, bool gri
   TGP_HIP_TRY(hipMemcpyAsync(tp->xt, xtest_host, size_t(m) * sizeof(double), hipMemcpyHostToDevice, st));
   TGP_HIP_TRY(hipMemcpyAsync(tp->order, h_order.data(), size_t(m) * sizeof(int64_t), hipMemcpyHostToDevice, st));
   TGP_HIP_TRY(hipStreamSynchronize(st));  // h_order leaves scope
-  qs_smp_locate<<<unsigned((m + 255) / 256), 256, 0, st>>>(q->t, n, tp->xt, tp->order, m, tp->sidx, tp->gt, tp->gp);
-  if (grid) qs_smp_place<<<unsigned((n + 255) / 256), 256, 0, st>>>(q->t, n, tp->xt, tp->order, m, tp->gt, tp->gp);
+  const UniformSExtent ext{n, q->lc, q->nchunks, m, 0, 0, 0};
+  qs_smp_locate<<<unsigned((m + 255) / 256), 256, 0, st>>>(ext, q->t, tp->xt, tp->order, tp->sidx, tp->gt, tp->gp);
+  if (grid) qs_smp_place<<<unsigned((n + 255) / 256), 256, 0, st>>>(ext, q->t, tp->xt, tp->order, tp->gt, tp->gp);
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
 }
@@ -2694,12 +2795,13 @@ int cond_mean_cols(tgp_qsep* q, const double* alpha, int64_t cols, int64_t m, co
   const int64_t n = q->n, nc = q->nchunks, ncg = ceil_div(cols, 8);
   TGP_TRY(grow(&q->work, &q->work_elems, scan_work<ScanAffine>(nc, ncg)));
   const unsigned blocks = unsigned(blocks_for(nc * ncg));
+  const UniformSExtent ext{n, q->lc, nc, m, 0, 0, 0};
   for (int dir = 0; dir < 2; ++dir) {
-    qs_cm_fold<<<blocks, WAVE * WPB, 0, st>>>(dir, q->model, q->t, alpha, n, q->lc, nc, cols, ncg, q->work);
+    qs_cm_fold<<<blocks, WAVE * WPB, 0, st>>>(dir, q->model, q->t, alpha, ext, cols, ncg, q->work);
     double* prefix = nullptr;
     TGP_TRY(run_scan<ScanAffine>(q->model, st, nc, ncg, q->work, &prefix));
-    qs_cm_emit<<<blocks, WAVE * WPB, 0, st>>>(dir, accumulate, q->model, q->t, alpha, n, q->lc, nc, cols, ncg, prefix,
-                                              tp.xt, tp.sidx, tp.order, m, out);
+    qs_cm_emit<<<blocks, WAVE * WPB, 0, st>>>(dir, accumulate, q->model, q->t, alpha, ext, cols, ncg, prefix, tp.xt,
+                                              tp.sidx, tp.order, out);
   }
   TGP_HIP_TRY(hipGetLastError());
   return TGP_OK;
@@ -2737,11 +2839,13 @@ int sample(tgp_qsep* q, const double* resid_host, int64_t m, const double* xtest
     TGP_TRY(copy_cols(st, true, xi, xi_host, G * J, nrhs, c0, cols));
     TGP_TRY(copy_cols(st, true, e, eps_host, n, nrhs, c0, cols));
     const unsigned blocks = unsigned(blocks_for(ncG * ncg)), eblocks = unsigned((n * cols + 255) / 256);
-    qs_prior<<<blocks, WAVE * WPB, 0, st>>>(0, q->model, gt, tp.gp, G, lcG, ncG, xi, cols, ncg, nullptr, q->work,
+    const UniformSExtent ext{n, q->lc, q->nchunks, m, G, lcG, ncG};
+    qs_prior<<<blocks, WAVE * WPB, 0, st>>>(0, q->model, gt, tp.gp, ext, xi, cols, ncg, nullptr, q->work, nullptr,
                                             nullptr);
     double* prefix = nullptr;
     TGP_TRY(run_scan<ScanAffine>(q->model, st, ncG, ncg, q->work, &prefix));
-    qs_prior<<<blocks, WAVE * WPB, 0, st>>>(1, q->model, gt, tp.gp, G, lcG, ncG, xi, cols, ncg, prefix, nullptr, f);
+    qs_prior<<<blocks, WAVE * WPB, 0, st>>>(1, q->model, gt, tp.gp, ext, xi, cols, ncg, prefix, nullptr, f,
+                                            f + n * cols);
     qs_smp_resid<<<eblocks, 256, 0, st>>>(resid, q->noise, f, e, n, cols);
     TGP_HIP_TRY(hipGetLastError());
     TGP_TRY(affine(q, TGP_QS_FWD, cols, e, z, nullptr));
@@ -2783,6 +2887,189 @@ int predict_mean(tgp_qsep* q, int64_t nrhs, const double* v_host, int v_is_alpha
     TGP_TRY(copy_cols(st, false, mean, mean_host, m, nrhs, c0, cols));
   }
   TGP_HIP_TRY(hipStreamSynchronize(st));
+  return TGP_OK;
+}
+
+// ---- sets of series: value and posterior draws ------------------------------------------------------------------------------
+// A chain draws for its members as sample() does for one series, every step one series per grid row: the value part, the
+// members' merged grids (their test points sorted by value on the host, as place_test_points sorts them), then per pass of
+// columns the prior scan over the grids, v, both solves, the conditional-mean scans and the data side.  After the value's
+// arrays (carve) the chain's buffer holds, with N data and M test points in the chain, G = N + M, c columns per pass in
+// g = ceil(c / 8) groups:
+//   the grids' extent table (13 B) | xt | sidx | order (M each) | gt | gp (G each) |
+//   xi (G max(J, 2) c; later z and alpha, N c each) | f at the data | eps, later v and the draws at the data (N c each) |
+//   with the test side wanted: f at the test points, later the draws there (M c) | scan work space (g sum wk_b)
+// Every array of a pass has member b's rows after member b - 1's and one pitch, so each goes up or comes down in one copy
+// (copy_cols).  With S4 the sum of a series' MAXLEV table levels, of its data (S4_b) and of its grid (S4G_b), series b
+// with M_b test points needs, in doubles,
+//   fixed_b  = N_b (4 + J) + 256 S4_b + 3 nchunks_b + 3  (the value's)  + 13 + 3 M_b + 2 G_b
+//   col_b(c) = c (G_b max(J, 2) + 2 N_b + [test side] M_b) + ceil(c / 8) wk_b,   wk_b = 192 max(S4_b, S4G_b)
+// Chains are the value's fill over fixed_b + col_b(1); a chain's columns per pass are the most -- at most SAMPLE_MAX_COLS,
+// stepping down as sample_pass_cols does -- with sum fixed_b + sum col_b(c) under the cap less the fixed part.  A function
+// of (N_b, M_b, J, nrhs, which sides are wanted) alone.
+constexpr int64_t EXT_DOUBLES = sizeof(QExtent) / sizeof(double);
+static_assert(sizeof(QExtent) % sizeof(double) == 0, "the grids' extents are laid out in a buffer of doubles");
+
+int64_t series_sample_work(const QExtent& x, const QExtent& g) {
+  return std::max(series_levels(x), series_levels(g)) * (ScanAffine::ESZ + ScanAffine::PSZ) * WAVE;
+}
+int64_t series_sample_fixed(const QExtent& x, const QExtent& g, int64_t J) {
+  return series_need(x, J) + EXT_DOUBLES + 3 * (g.n - x.n) + 2 * g.n;
+}
+int64_t series_sample_cols(const QExtent& x, const QExtent& g, int64_t J, bool want_test, int64_t cols) {
+  return cols * (g.n * std::max<int64_t>(J, 2) + 2 * x.n + (want_test ? g.n - x.n : 0)) +
+         ceil_div(cols, 8) * series_sample_work(x, g);
+}
+
+int series_sample_split(tgp_qsep_series* s, int32_t J, int64_t nrhs, bool want_data, bool want_test,
+                        const int64_t* test_offsets) {
+  tgp_qsep_series::Cut cut{4, J, 0, 0, int32_t(want_data) + 2 * int32_t(want_test), {}, nrhs};
+  cut.tests.resize(size_t(s->nseries));
+  for (int64_t b = 0; b < s->nseries; ++b) cut.tests[size_t(b)] = test_offsets[b + 1] - test_offsets[b];
+  if (s->cut == cut) return TGP_OK;
+  std::vector<QExtent> grid(size_t(s->nseries));
+  for (int64_t b = 0; b < s->nseries; ++b) {
+    grid[size_t(b)] = extent_of(s->ext[size_t(b)].n + cut.tests[size_t(b)]);
+    TGP_ARG_CHECK(grid[size_t(b)].lev[MAXLEV - 1] <= GROUP, "the merged grid of series %lld (%lld points) needs more "
+                  "than %d scan levels", (long long)b, (long long)grid[size_t(b)].n, MAXLEV);
+  }
+  const QExtent* first = s->ext.data();  // series_fill hands the set's own extents over: x is series x - first
+  auto fixed = [&](const QExtent& x) { return series_sample_fixed(x, grid[size_t(&x - first)], J); };
+  auto percol = [&](const QExtent& x, int64_t c) {
+    return series_sample_cols(x, grid[size_t(&x - first)], J, want_test, c);
+  };
+  TGP_TRY(series_fill(
+      s, cut, BATCH_MAX_MEMBERS * MODEL_DOUBLES, [&](const QExtent& x) { return fixed(x) + percol(x, 1); },
+      [](const QExtent&) { return int64_t(0); },
+      [&](const QExtent& x) { return series_sample_work(x, grid[size_t(&x - first)]); }));
+  const int64_t budget = BATCH_BUDGET - BATCH_MAX_MEMBERS * MODEL_DOUBLES;
+  int64_t largest = 0;
+  for (size_t k = 0; k + 1 < s->chain0.size(); ++k) {
+    auto need = [&](int64_t c) {
+      int64_t sum = 0;
+      for (int64_t b = s->chain0[k]; b < s->chain0[k + 1]; ++b) sum += fixed(s->ext[size_t(b)]) + percol(s->ext[size_t(b)], c);
+      return sum;
+    };
+    int64_t cols = std::min(nrhs, SAMPLE_MAX_COLS);
+    while (cols > 1 && need(cols) > budget) cols -= cols > 8 ? (cols % 8 ? cols % 8 : 8) : 1;
+    s->chain_d[k] = cols;
+    largest = std::max(largest, need(cols));
+  }
+  s->buf_need = BATCH_MAX_MEMBERS * MODEL_DOUBLES + largest;
+  return TGP_OK;
+}
+
+// the series of a chain with nrhs right-hand sides each, as launch_affine takes its members
+struct ColsMembers {
+  const double* t;
+  const QExtent* tab;
+  int64_t count;
+  const int64_t* top;
+  int depth;
+  int64_t nrhs, ncg;
+  int64_t chunks() const { return top[0]; }
+  TableColsExtent ext() const { return {tab, nrhs, ncg}; }
+  template <class S>
+  int scan(hipStream_t st, const QModel* models, double* work, int64_t width, bool, double** prefix) const {
+    *prefix = work;
+    return run_scan_table<S>(models, st, tab, count, top, depth, work, width);
+  }
+};
+
+// One launch chain of value and draws over the members m in `buf`, pc columns per pass; one stream synchronisation.  A
+// failed member gets NaN for everything but its info.
+int chain_samples(const TableMembers& m, hipStream_t st, double* buf, const ChainCall& a, int64_t pc, int32_t* passes) {
+  const ChainArrays A = carve(m, buf, a);
+  const Totals h = m.held();
+  const int64_t nb = h.members, N = h.points, J = a.J, Jp = std::max<int64_t>(J, 2), nrhs = a.nrhs;
+  const int64_t Mt = a.tests(nb), Gt = N + Mt;
+  TGP_TRY(chain_value(m, st, A, a));
+  // the members' grids and their test points in sorted order; alive until the synchronisation
+  std::vector<QExtent> grid(static_cast<size_t>(nb));
+  std::vector<int64_t> order(static_cast<size_t>(Mt));
+  int64_t gtop[MAXLEV + 1] = {}, most = 0, longest = 0, wsum = 0;
+  for (int64_t b = 0; b < nb; ++b) {
+    const QExtent& x = m.mine[b];
+    const int64_t at = a.tests(b), cnt = a.tests(b + 1) - at;
+    QExtent& g = grid[size_t(b)];
+    g = extent_of(x.n + cnt);
+    g.off = x.off + at, g.twork = x.twork;
+    wsum += series_sample_work(x, g);
+    for (int l = 0; l <= MAXLEV; ++l) gtop[l] = std::max(gtop[l], g.lev[l]);
+    most = std::max(most, cnt), longest = std::max(longest, x.n);
+    int64_t* o = order.data() + at;
+    const double* xs = a.xtest + at;
+    for (int64_t j = 0; j < cnt; ++j) o[j] = j;
+    std::stable_sort(o, o + cnt, [&](int64_t p, int64_t q) { return sort_key(xs[p]) < sort_key(xs[q]); });
+  }
+  int gdepth = 1;
+  while (gtop[gdepth - 1] > GROUP) ++gdepth;
+  double* p = A.end;
+  auto take = [&](int64_t len) {
+    double* got = p;
+    p += len;
+    return got;
+  };
+  QExtent* gtab = reinterpret_cast<QExtent*>(take(nb * EXT_DOUBLES));
+  double* xt = take(Mt);
+  int64_t *sidx = reinterpret_cast<int64_t*>(take(Mt)), *ord = reinterpret_cast<int64_t*>(take(Mt));
+  double* gt = take(Gt);
+  int64_t* gp = reinterpret_cast<int64_t*>(take(Gt));
+  double *xi = take(Gt * Jp * pc), *fdata = take(N * pc), *e = take(N * pc), *ftest = take(a.test ? Mt * pc : 0);
+  double* work = take(ceil_div(pc, 8) * wsum);
+  if (a.data || a.test) {
+    const TableSExtent sext{m.tab, gtab};
+    TGP_HIP_TRY(hipMemcpyAsync(gtab, grid.data(), size_t(nb) * sizeof(QExtent), hipMemcpyHostToDevice, st));
+    if (Mt > 0) {
+      TGP_HIP_TRY(hipMemcpyAsync(xt, a.xtest, size_t(Mt) * sizeof(double), hipMemcpyHostToDevice, st));
+      TGP_HIP_TRY(hipMemcpyAsync(ord, order.data(), size_t(Mt) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+      qs_smp_locate<<<dim3(unsigned(ceil_div(most, 256)), unsigned(nb)), 256, 0, st>>>(sext, m.t, xt, ord, sidx, gt, gp);
+    }
+    qs_smp_place<<<dim3(unsigned(ceil_div(longest, 256)), unsigned(nb)), 256, 0, st>>>(sext, m.t, xt, ord, gt, gp);
+    TGP_HIP_TRY(hipGetLastError());
+    for (int64_t c0 = 0; c0 < nrhs; c0 += pc, ++*passes) {
+      const int64_t cols = std::min(pc, nrhs - c0), ncg = ceil_div(cols, 8);
+      double *z = xi, *alpha = xi + N * cols;  // take xi's place once it is read
+      TGP_TRY(copy_cols(st, true, xi, a.xi, Gt * J, nrhs, c0, cols));
+      TGP_TRY(copy_cols(st, true, e, a.eps, N, nrhs, c0, cols));
+      const dim3 ggrid(unsigned(blocks_for(gtop[0] * ncg)), unsigned(nb));
+      const dim3 dgrid(unsigned(blocks_for(m.chunks() * ncg)), unsigned(nb));
+      const unsigned eblocks = unsigned(ceil_div(N * cols, 256));
+      qs_prior<<<ggrid, WAVE * WPB, 0, st>>>(0, A.models, gt, gp, sext, xi, cols, ncg, nullptr, work, nullptr, nullptr);
+      TGP_TRY(run_scan_table<ScanAffine>(A.models, st, gtab, nb, gtop, gdepth, work, ncg));
+      qs_prior<<<ggrid, WAVE * WPB, 0, st>>>(1, A.models, gt, gp, sext, xi, cols, ncg, work, nullptr, fdata, ftest);
+      qs_smp_resid<<<eblocks, 256, 0, st>>>(A.resid, A.noise, fdata, e, N, cols);
+      TGP_HIP_TRY(hipGetLastError());
+      const ColsMembers cm{m.t, m.tab, nb, m.top, m.depth, cols, ncg};
+      double* prefix = nullptr;
+      TGP_TRY(launch_affine(cm, st, TGP_QS_FWD, A.models, A.c, A.w, cols, e, work, z, nullptr, &prefix));
+      TGP_TRY(launch_affine(cm, st, TGP_QS_BWD, A.models, A.c, A.w, cols, z, work, alpha, nullptr, &prefix));
+      if (a.test && Mt > 0) {
+        for (int dir = 0; dir < 2; ++dir) {
+          qs_cm_fold<<<dgrid, WAVE * WPB, 0, st>>>(dir, A.models, m.t, alpha, sext, cols, ncg, work);
+          TGP_TRY(run_scan_table<ScanAffine>(A.models, st, m.tab, nb, m.top, m.depth, work, ncg));
+          qs_cm_emit<<<dgrid, WAVE * WPB, 0, st>>>(dir, 1, A.models, m.t, alpha, sext, cols, ncg, work, xt, sidx, ord,
+                                                   ftest);
+        }
+        TGP_HIP_TRY(hipGetLastError());
+        TGP_TRY(copy_cols(st, false, ftest, a.test, Mt, nrhs, c0, cols));
+      }
+      if (a.data) {
+        qs_smp_data<<<eblocks, 256, 0, st>>>(A.noise, fdata, alpha, e, N, cols);
+        TGP_HIP_TRY(hipGetLastError());
+        TGP_TRY(copy_cols(st, false, e, a.data, N, nrhs, c0, cols));
+      }
+    }
+  }
+  std::vector<double> got(size_t(3 * nb));
+  TGP_HIP_TRY(hipMemcpyAsync(got.data(), A.res, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  TGP_HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t b = 0; b < nb; ++b) {
+    member_value(&got[size_t(3 * b)], m.n_of(b), &a.info[b], &a.out[b]);
+    if (a.info[b] == 0) continue;
+    if (a.data) fill_nan(a.data + m.off_of(b) * nrhs, m.n_of(b) * nrhs);
+    if (a.test) fill_nan(a.test + a.tests(b) * nrhs, (a.tests(b + 1) - a.tests(b)) * nrhs);
+  }
   return TGP_OK;
 }
 
@@ -2987,11 +3274,7 @@ int tgp_qsep_series_create(tgp_ctx* ctx, int32_t nseries, const int64_t* offsets
   std::vector<QExtent> ext(size_t(nseries), QExtent{});
   for (int32_t b = 0; b < nseries; ++b) {
     QExtent& x = ext[size_t(b)];
-    x.n = offsets[b + 1] - offsets[b];
-    x.lc = chunk_length(x.n);  // the single call's rule: a member's chunks are those of its own solver
-    x.nchunks = ceil_div(x.n, x.lc);
-    x.lev[0] = x.nchunks;
-    for (int l = 0; l < MAXLEV; ++l) x.lev[l + 1] = ceil_div(x.lev[l], GROUP);
+    x = extent_of(offsets[b + 1] - offsets[b]);
     TGP_ARG_CHECK(x.lev[MAXLEV - 1] <= GROUP, "series %d (n = %lld) needs more than %d scan levels", b,
                   (long long)x.n, MAXLEV);
   }
@@ -3091,6 +3374,54 @@ int tgp_qsep_series_predict(tgp_qsep_series* s, const double* leaves, int32_t nl
   a.info = info, a.out = out;
   a.test_offsets = test_offsets, a.xtest = xtest_concat, a.at_data = at_data, a.mean = mean_concat, a.var = var_concat;
   return series_chains(s, a, nchains, nullptr);
+}
+
+int tgp_qsep_series_sample(tgp_qsep_series* s, const double* leaves, int32_t nleaves, const int32_t* state_map,
+                           int32_t J, const double* hvec, const double* Pinf, const double* noise_concat,
+                           const double* resid_concat, const int64_t* test_offsets, const double* xtest_concat,
+                           const int32_t* at_data, int64_t nrhs, const double* xi_concat, const double* eps_concat,
+                           int32_t* info, double* out, double* data_concat, double* test_concat, int32_t* nchains,
+                           int32_t* npasses) {
+  QS_GUARD(s);
+  if (nchains) *nchains = 0;
+  if (npasses) *npasses = 0;
+  TGP_ARG_CHECK(leaves && state_map && hvec && Pinf, "null model array");
+  TGP_ARG_CHECK(noise_concat && resid_concat && info && out, "null argument");
+  TGP_ARG_CHECK(nrhs >= 1, "need at least one column of draws (got %lld)", (long long)nrhs);
+  TGP_ARG_CHECK(test_offsets != nullptr, "null test offsets");
+  TGP_ARG_CHECK(test_offsets[0] == 0, "the test offsets start at 0 (got %lld)", (long long)test_offsets[0]);
+  const bool draws = data_concat || test_concat;
+  TGP_ARG_CHECK(!draws || (xi_concat && eps_concat), "null standard normals");
+  for (int64_t b = 0; b < s->nseries; ++b) {
+    const int64_t lo = test_offsets[b], cnt = test_offsets[b + 1] - lo;
+    TGP_ARG_CHECK(cnt >= 0, "the test offsets must not decrease (series %lld: %lld after %lld)", (long long)b,
+                  (long long)test_offsets[b + 1], (long long)lo);
+    TGP_ARG_CHECK(!(at_data && at_data[b]) || cnt == 0, "series %lld draws at its own data, which the data side "
+                  "returns: its count of test points must be 0 (got %lld)", (long long)b, (long long)cnt);
+    TGP_ARG_CHECK(cnt == 0 || xtest_concat, "null test points (series %lld brings %lld)", (long long)b, (long long)cnt);
+    for (int64_t j = 0; j < cnt; ++j)
+      TGP_ARG_CHECK(std::isfinite(xtest_concat[lo + j]), "test point %lld of series %lld is not finite: a sample is a "
+                    "recurrence over all points", (long long)j, (long long)b);
+  }
+  std::vector<QModel> models;
+  TGP_TRY(pack_models(&models, s->nseries, leaves, nleaves, state_map, J, hvec, Pinf));
+  TGP_TRY(series_sample_split(s, J, nrhs, data_concat != nullptr, test_concat != nullptr, test_offsets));
+  ChainCall a{};
+  a.nl = nleaves, a.J = J, a.models = models.data(), a.noise = noise_concat, a.resid = resid_concat;
+  a.info = info, a.out = out;
+  a.test_offsets = test_offsets, a.xtest = xtest_concat;
+  a.nrhs = nrhs, a.xi = xi_concat, a.eps = eps_concat, a.data = data_concat, a.test = test_concat;
+  TGP_TRY(grow(&s->buf, &s->buf_elems, s->buf_need));
+  const size_t chains = s->chain0.size() - 1;
+  int32_t passes = 0;
+  for (size_t k = 0; k < chains; ++k) {
+    const int64_t b0 = s->chain0[k], at = s->offsets[size_t(b0)];
+    TGP_TRY(chain_samples(table_members(s, b0, s->chain0[k + 1] - b0, 0), s->ctx->stream, s->buf, a.from(b0, at, at, at),
+                          s->chain_d[k], &passes));
+  }
+  if (nchains) *nchains = int32_t(chains);
+  if (npasses) *npasses = passes;
+  return TGP_OK;
 }
 
 int tgp_qsep_normalization(tgp_qsep* q, double* out) {

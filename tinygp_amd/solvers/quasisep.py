@@ -11,7 +11,8 @@ the gradient of the log-probability (``value_and_grad``; O(N) per parameter) and
 hyper-parameter sets over the one series in one launch chain (``log_probability_batch``; with their gradients:
 ``value_and_grad_batch``).  :class:`QuasisepSeriesSet` evaluates many series, each on coordinates of its own, in one
 launch chain (``tgp_qsep_series_logprob``; with their gradients: ``tgp_qsep_series_grad``; with predictions at test
-points of their own: ``tgp_qsep_series_predict``).  Nothing
+points of their own: ``tgp_qsep_series_predict``; with posterior draws there and at the data:
+``tgp_qsep_series_sample``).  Nothing
 of size N x N is ever formed, except by ``covariance()`` (host, O(N^2), as in the
 reference); the full conditional covariance and conditioning on another kernel keep the reference's dense route.
 
@@ -656,6 +657,46 @@ def series_added_means(means, test_offsets, test_means, include_mean: bool):
     return added
 
 
+def pack_series_sample_tests(lengths, X_tests):
+    """The test points of ``tgp_qsep_series_sample``: as :func:`pack_series_tests`, but a ``None`` entry -- the series'
+    own points -- counts 0 beside its flag (its draws at the data are an output already), and every test point must be
+    finite: a ``ValueError`` names the series whose are not."""
+    X_tests = list(X_tests)
+    offsets, xtest, at_data = pack_series_tests(lengths, [np.empty(0) if X is None else X for X in X_tests])
+    for b, X in enumerate(X_tests):
+        at_data[b] = X is None
+        if not np.all(np.isfinite(xtest[offsets[b]:offsets[b + 1]])):
+            raise ValueError(f"X_tests[{b}] of series {b} must be finite: a sample is a recurrence over all points")
+    return offsets, xtest, at_data
+
+
+def pack_series_normals(lengths, counts, J, xi, eps):
+    """The standard normals of ``tgp_qsep_series_sample`` for series of the given lengths and test-point counts:
+    ``(xi_concat (sum (N_b + M_b) J, R), eps_concat (sum N_b, R), R, one)``, member b's rows after member b - 1's.
+    ``xi[b]``: (N_b + M_b, J, R), ``eps[b]``: (N_b, R), one R for all; or every ``xi[b]`` (N_b + M_b, J) with ``eps[b]``
+    (N_b,): ``one``, R = 1.  A wrong count or shape raises ``ValueError`` naming the member."""
+    nb = len(lengths)
+    xi, eps = [np.asarray(a) for a in xi], [np.asarray(a) for a in eps]
+    if len(xi) != nb or len(eps) != nb:
+        raise ValueError(f"xi and eps must hold one entry per series ({nb}); got {len(xi)} and {len(eps)}")
+    one = xi[0].ndim == 2
+    R = 1 if one else (xi[0].shape[2] if xi[0].ndim == 3 else -1)
+    for b in range(nb):
+        n, g = int(lengths[b]), int(lengths[b] + counts[b])
+        want = (g, J) if one else (g, J, R)
+        if xi[b].shape != want:
+            raise ValueError(f"xi[{b}] must have shape {want} for series {b}"
+                             + ("" if b == 0 else f" (as xi[0] has {xi[0].ndim} dimensions)") + f"; got {xi[b].shape}")
+        if eps[b].shape != ((n,) if one else (n, R)):
+            raise ValueError(f"eps[{b}] must have shape {(n,) if one else (n, R)} for series {b} beside xi[{b}] of shape "
+                             f"{xi[b].shape}; got {eps[b].shape}")
+    if R < 1:
+        raise ValueError(f"xi[0] must have shape (N + M, J) or (N + M, J, R) with R >= 1; got {xi[0].shape}")
+    xi_c = np.concatenate([_f64(a).reshape(-1, R) for a in xi])
+    eps_c = np.concatenate([_f64(a).reshape(-1, R) for a in eps])
+    return np.ascontiguousarray(xi_c), np.ascontiguousarray(eps_c), R, one
+
+
 class QuasisepSeriesSet:
     """B series on coordinates of their own -- the light curves of a survey, each with its gaps, masks and length --
     evaluated together on the device: one series per grid row of every kernel (``tgp_qsep_series_logprob``), where a
@@ -793,6 +834,61 @@ class QuasisepSeriesSet:
         result = out, mus, variances
         return result + (info,) if return_info else result
 
+    def sample_conditional(self, kernels, ys, diags, X_tests, *, xi, eps, means=None, return_data: bool = False,
+                           return_info: bool = False):
+        """Value and posterior draws of the B series in one launch chain (``tgp_qsep_series_sample``): draws of every
+        fitted light curve of a survey, where a loop of :meth:`QuasisepSolver.sample_conditional` pays a handle, an
+        upload, a launch chain and a stream synchronisation per series.
+
+        ``kernels``, ``ys``, ``diags``, ``means`` as in :meth:`log_probability`; ``X_tests`` as in :meth:`predict`
+        (finite; ``None``: the series' own points, whose test-side entry is then its data-side draw).  The draws are a
+        function of the standard normals passed in, as :meth:`QuasisepSolver.sample_conditional` takes them: ``xi``, a
+        list of B arrays (N_b + M_b, J, R), row p for point p of ``[Xs[b]; X_tests[b]]`` (M_b = 0 for ``None``), and
+        ``eps``, a list of B arrays (N_b, R); all ``xi[b]`` (N_b + M_b, J) with ``eps[b]`` (N_b,) give 1-D results.
+
+        Returns ``(values (B,), tests)``, ``tests`` a list of B arrays (M_b, R), float64; with ``return_data`` the list
+        of the draws at the data (N_b, R) comes third, with ``return_info`` the B ``info`` values come last.  No noise
+        is added: the draws are of the latent process, without any mean.  Member b's value and column c of its draws
+        have the bits of ``QuasisepSolver(kernels[b], Xs[b], Diagonal(diags[b]))`` with ``.log_probability(r)`` and
+        ``.sample_conditional(r, X_tests[b], xi=xi[b][..., c], eps=eps[b][:, c], return_data=True)``, r = ``ys[b] -
+        means[b]``, on a fresh solver, whatever B, its position, the other members, R and the split into chains and
+        passes (``self.sample_chains``, ``self.sample_passes``: what the last call took).  A failed or non-finite
+        member gives ``-inf`` and NaN draws and touches no other."""
+        if self._handle is None:
+            raise ValueError("this QuasisepSeriesSet has been closed")
+        leaves, smap, h, P, noise, resid = pack_series(self.lengths, kernels, ys, diags, means)
+        test_offsets, xtest, at_data = pack_series_sample_tests(self.lengths, X_tests)
+        J = h.shape[1]
+        xi_c, eps_c, R, one = pack_series_normals(self.lengths, np.diff(test_offsets), J, xi, eps)
+        nb, total, ntest = len(self), int(self._offsets[-1]), int(test_offsets[-1])
+        info, out = np.zeros(nb, dtype=np.int32), np.empty(nb)
+        want_data = return_data or bool(at_data.any())
+        data = np.empty((total, R)) if want_data else None
+        test = np.empty((max(ntest, 1), R))
+        chains, passes = C.c_int32(0), C.c_int32(0)
+        _ffi.check(_ffi.lib().tgp_qsep_series_sample(self._handle, _ffi.ptr(leaves), leaves.shape[1], _ffi.ptr(smap), J,
+                                                     _ffi.ptr(h), _ffi.ptr(P), _ffi.ptr(noise), _ffi.ptr(resid),
+                                                     _ffi.ptr(test_offsets), _ffi.ptr(xtest) if ntest else None,
+                                                     _ffi.ptr(at_data), R, _ffi.ptr(xi_c), _ffi.ptr(eps_c),
+                                                     _ffi.ptr(info), _ffi.ptr(out), _ffi.ptr(data), _ffi.ptr(test),
+                                                     C.byref(chains), C.byref(passes)), "tgp_qsep_series_sample")
+        self.sample_chains, self.sample_passes = int(chains.value), int(passes.value)
+        failed = (info != 0) | ~np.isfinite(out)
+        out[failed] = -np.inf
+        shape = (lambda a: a[:, 0]) if one else (lambda a: a)
+        cut = lambda a, offs: [shape(a[lo:hi]) for lo, hi in zip(offs[:-1], offs[1:])]  # noqa: E731
+        datas = cut(data, self._offsets) if want_data else None
+        tests = cut(test, test_offsets)
+        for b in range(nb):
+            if at_data[b]:
+                tests[b] = datas[b]
+        for b in np.flatnonzero(failed):
+            tests[b] = np.full(tests[b].shape, np.nan)
+            if want_data:
+                datas[b] = np.full(datas[b].shape, np.nan)
+        result = (out, tests) + ((datas,) if return_data else ())
+        return result + (info,) if return_info else result
+
     def close(self):
         if getattr(self, "_handle", None):
             _ffi.lib().tgp_qsep_series_destroy(self._handle)
@@ -842,3 +938,57 @@ def log_probability_and_grad_series(kernels, Xs, ys, *, diags, means=None, vecto
         return series.value_and_grad(kernels, ys, diags, means=means, vectors=vectors)
     finally:
         series.close()
+
+
+def sample_conditional_series(kernels, Xs, ys, X_tests, *, diags, key, shape=None, means=None, test_means=None,
+                              include_mean: bool = True, normals=None):
+    """Posterior draws of the latent process of B quasiseparable GPs, each conditioned on a series with coordinates of
+    its own, at test points of its own: builds a :class:`QuasisepSeriesSet` on ``Xs``, calls its
+    :meth:`~QuasisepSeriesSet.sample_conditional` and closes it.
+
+    ``key``: an ``int`` seed or a ``numpy.random.Generator``.  With R the product of ``shape``, it draws per member, in
+    member order, ``xi_b = rng.standard_normal((N_b + M_b, J, R))``, then ``eps_b = rng.standard_normal((N_b, R))`` (M_b
+    = 0 for ``X_tests[b] = None``), the order of :meth:`tinygp_amd.GaussianProcess.sample_conditional`: member 0 of a
+    set, drawn with a fresh generator, equals ``GaussianProcess(kernels[0], Xs[0], diag=diags[0],
+    mean=means[0]).sample_conditional(ys[0], X_tests[0], key=key, shape=shape)`` bit for bit for float64 inputs.
+    ``normals``: a list of B pairs ``(xi_b, eps_b)`` of those shapes, which replaces the draw (``key`` is then not
+    used).
+
+    Returns ``(values (B,), samples)``: ``samples[b]`` has shape ``shape + (M_b,)``, or ``shape + (N_b,)`` for a member
+    drawn at its own points.  ``means``, ``test_means``, ``include_mean``: as in :meth:`QuasisepSeriesSet.predict`
+    (:func:`series_added_means`; a member at its own points counts its N_b outputs).  A failed or non-finite member
+    gives ``-inf`` and NaN draws."""
+    from tinygp_amd.kernels.quasisep import Quasisep, _coords
+
+    shape = () if shape is None else tuple(shape)
+    R = int(np.prod(shape, dtype=np.int64))
+    series = QuasisepSeriesSet(Xs)
+    try:
+        nb = len(series)
+        X_tests = list(X_tests)
+        if len(X_tests) != nb:
+            raise ValueError(f"X_tests must hold one entry per series ({nb}); got {len(X_tests)}")
+        counts = [0 if X is None else len(_coords(X)) for X in X_tests]
+        outs = [int(n) if X is None else m for n, X, m in zip(series.lengths, X_tests, counts)]
+        added = series_added_means(means, np.concatenate([[0], np.cumsum(outs)]), test_means, include_mean)
+        if normals is None:
+            first = kernels if isinstance(kernels, Quasisep) else list(kernels)[0]
+            J = first._lower_ssm().J
+            rng = key if isinstance(key, np.random.Generator) else np.random.default_rng(key)
+            normals = []
+            for n, m in zip(series.lengths, counts):
+                xi = rng.standard_normal((int(n) + m, J, R))
+                normals.append((xi, rng.standard_normal((int(n), R))))
+        else:
+            normals = list(normals)
+            if len(normals) != nb:
+                raise ValueError(f"normals must hold one (xi, eps) pair per series ({nb}); got {len(normals)}")
+        values, tests = series.sample_conditional(kernels, ys, diags, X_tests, xi=[p[0] for p in normals],
+                                                  eps=[p[1] for p in normals], means=means)
+    finally:
+        series.close()
+    samples = []
+    for b, out in enumerate(tests):
+        out = np.moveaxis(out, 0, -1).reshape(shape + (out.shape[0],))
+        samples.append(out + added[b] if include_mean else out)
+    return values, samples
