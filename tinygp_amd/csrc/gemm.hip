@@ -990,7 +990,11 @@ int launch_gemm_nt(tgp_ctx* ctx, hipStream_t st, int64_t m, int64_t n, int64_t k
         ctx->d_gemm_ws = nullptr;
         ctx->gemm_ws_bytes = 0;
         TGP_HIP_TRY(hipMalloc(&ctx->d_gemm_ws, need));
-        TGP_HIP_TRY(hipMemset(ctx->d_gemm_ws, 0, need));  // (the per-tile counters reset themselves afterwards)
+        // the per-tile counters (they reset themselves afterwards), zeroed ON THE LAUNCH'S STREAM: a hipMemset runs on the
+        // null stream, which a non-blocking stream does not wait for -- the first split launch of a context could count
+        // its slices on whatever the allocation held.  (The partial tiles are written whole before they are counted.)
+        TGP_HIP_TRY(hipMemsetAsync(static_cast<char*>(ctx->d_gemm_ws) + size_t(slots) * BM * BN * sizeof(T), 0,
+                                   size_t(slots) * sizeof(int), st));
         ctx->gemm_ws_bytes = need;
       }
       g.split_first = g.nblk - R;
