@@ -192,7 +192,8 @@ int tgp_ctx_sync(tgp_ctx* ctx);
  *   "stream_trsv"       1 (default): triangular solves on a resident factor run as ONE streaming
  *                       launch (chol.hip, trsv_fwd/bwd_stream_kernel); 0: one launch pair per block;
  *                       "trsv_groups" (0 = by size: 3 / 4 / 6): workgroups per block row of the forward launch -- G - 1
- *                       helpers stream the raw tiles, the primary applies W_b, tf_b = W_b L[b,b-1] and tf2_b = W_b L[b,b-2]
+ *                       helpers stream the raw tiles, the primary applies W_b, tf_b = W_b L[b,b-1] and tf2_b = W_b L[b,b-2].
+ *                       Any other value is clamped to 2..8 by the solve (negative values count as 0)
  *   "keep_grad_buffers" 1: tgp_solver_grad keeps its (N + 128) x N work matrix between calls whatever its
  *                       size (default: kept up to 4 GiB, released at once above) */
 int tgp_ctx_set_option(tgp_ctx* ctx, const char* key, int64_t value, int64_t* old);

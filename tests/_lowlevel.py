@@ -50,12 +50,15 @@ def trsv(L, y, transpose=False):
         ctx.free(dL), ctx.free(dy)
 
 
-def trsm_right_lt(L, B):
-    """B (m, n) -> B L^-T."""
+def trsm_right_lt(L, B, **options):
+    """B (m, n) -> B L^-T.  Context options (nb_outer, lookahead, ...) by keyword: set for the call, restored behind it."""
     ctx = _ffi.default_ctx()
     dt = L.dtype
     n = L.shape[0]
     m = B.shape[0]
+    old = {}
+    for k, v in options.items():
+        old[k] = ctx.set_option(k, v)
     dL = ctx.upload(_f(L, dt).ravel(order="K"))
     dB = ctx.upload(_f(B, dt).ravel(order="K"))
     try:
@@ -65,6 +68,8 @@ def trsm_right_lt(L, B):
         return ctx.download(dB, (n, m), dt).T
     finally:
         ctx.free(dL), ctx.free(dB)
+        for k, v in old.items():
+            ctx.set_option(k, v)
 
 
 def gemm_nt(A, B, Cm, alpha, beta, lower=False):
